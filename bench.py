@@ -2,7 +2,7 @@
 """Benchmark of the headline metric (BASELINE.json): NMF multiplicative-update
 iterations/s at Y = 65536 x 4096, k = 256, float32, on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -52,6 +52,31 @@ def synth(n_rows, rank_seed, device):
         r1 = min(n_rows, r0 + block)
         Y[r0:r1] += (0.1 * np.abs(rs.randn(r1 - r0, N_FEAT))).astype(np.float32)
     return torch.from_numpy(Y).to(device), torch.from_numpy(D0).to(device)
+
+
+DUMP_X_ROWS = 16384         # --dump-outputs: rows of x written (a fixed, seeded sample when x has more)
+
+
+def dump_outputs(out_dir, D, x, seed=0):
+    """--dump-outputs: what a caller of the timed path receives after its last timed step, as float32 .npy files
+    for an output-by-output comparison of two builds.  D.npy is the whole dictionary [K, F]; x.npy holds the codes
+    [rows, K] whole when rows <= DUMP_X_ROWS, else the rows listed in x_rows.npy (float64 indices: a sample drawn
+    from RandomState(seed), in ascending order, the same for every run with the same arguments).  At the headline
+    shape: 4 MiB + 16 MiB + 128 KiB.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rows = x.shape[0]
+    arrays = {'D': D.detach().float().cpu().numpy()}
+    if rows <= DUMP_X_ROWS:
+        arrays['x'] = x.detach().float().cpu().numpy()
+    else:
+        idx = np.sort(np.random.RandomState(seed).choice(rows, DUMP_X_ROWS, replace=False))
+        arrays['x'] = x[torch.from_numpy(idx).to(x.device)].float().cpu().numpy()
+        arrays['x_rows'] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def pmc_traffic(kernel_key):
@@ -590,7 +615,12 @@ def main():
     ap.add_argument('--rows', type=int, default=0,
                     help='(analysis only) rows of Y on this GPU instead of 65536/N: time one '
                          'shard of a larger run without the collective')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the D and x they produced to DIR/<name>.npy (float32; '
+                         'x as a fixed, seeded row sample at the full shape; rank 0 only)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` as ONE command: this parent has made no GPU call (torch is not even
@@ -715,6 +745,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     prof = read_profile()
+    # the outputs of the last timed step, before the breakdown pass below iterates D and x further
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, Dcur, state['x'])
 
     # After the timed region: a short untimed pass with every kernel group bracketed, for the
     # per-kernel breakdown (kernel_ms_avg); it does not enter `value`.
@@ -797,6 +831,8 @@ def main():
         }
         if phase_ms is not None:
             out['phase_ms'] = phase_ms
+        if dumped is not None:
+            out['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         # dominant kernel: the fused Y.D^T GEMM + MU quotient (2.N.K.F flop per launch)
         dom = prof.get('x_update')
         if world == 1 and not args.rows:
