@@ -1,0 +1,5 @@
+// C ABI: dcp_tm_*_c128, structured template matching (see include/decomp_hip.h and template_impl.hpp;
+// reference decomp/template_matching.py).
+#include "template_impl.hpp"
+
+DCP_TM_DEFINE(c128, dcp::c128)

@@ -1,0 +1,878 @@
+// 1-D convolutional template learning (decomp/template_matching.py) without the im2col matrices.
+//
+// Geometry (reference _coef_size / _temp2mat / _coef2mat, restated in closed form):
+//   C   = floor((S + 2 pad - N) / s) + 1,   pad = N - 1 (SAME) | N - S (VALID),   Q = s (C - 1) - pad
+//   A[(t, c), n]     = D[t, n - s c + Q]          when 0 <= n - s c + Q < S     (_temp2mat, [T, C, N])
+//   X[b, (t, k), n]  = x[b, t, c]                 when n - s c + Q == k         (_coef2mat, [B, T, S, N])
+//
+// LASSO (ista / acc_ista / fista, lasso.py:97-189,274-415) on the operator A without forming it.  In the
+// reference's scaled variables x' = x rho (rho[t, c] = |A_(t,c)|, the boundary-truncated row norm) one
+// iteration is
+//   pass 1  r[b, n]    = y[b, n] - sum_(t, c) (v'[b, t, c] / rho[t, c]) D[t, n - s c + Q]          (= y - v'A')
+//   pass 2  g[b, t, c] = (1 / rho[t, c]) sum_k r[b, s c - Q + k] conj(D[t, k])                    (= r A'^H)
+//           x'_new     = prox(v' + g / L, alpha N / (rho L)),  momentum and the |dx'| - tol rho test fused in
+// i.e. (y - v'A')A'^H in place of the reference's yA'^H - v'A'A'^H (the same quantity).  1/L is the
+// Gershgorin bound of the banded Gram A'A'^H, built by the prepare kernels from the lag correlations
+// Corr[t, t', m] = sum_k D[t, k] conj(D[t', k + m]): an entry whose column's support lies inside the signal
+// IS Corr / (rho_i rho_j); only the boundary columns sum their truncated overlap explicitly.
+//
+// Dictionary statistics (template_matching.py:177-187) without X [B, T S, N]:
+//   yX[t, k]                = sum_b sum_c x[b, t, c] y[b, s c - Q + k]                     (no conjugate)
+//   XXt[(t, k), (t', k')]   = sum_b sum_(c in W(k, d)) x[b, t, c] conj(x[b, t', c + d]),  d = (k - k') / s
+// (zero unless k = k' mod s).  The window W(k, d) of c keeps s c - Q + k inside [0, N); every W(k, d) holds
+// the common core [cl(d), ch(d)], so an entry is  M[t, t', d] + head edge terms + tail edge terms  with the
+// interior sum M computed once per lag and at most ~S/s edge terms per side: additions only, no prefix
+// differences, fixed summation order everywhere (two runs are bitwise identical).
+#pragma once
+#include "lasso_impl.hpp"
+
+namespace dcp {
+
+DCP_HD long tm_floor_div(long a, long b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
+DCP_HD long tm_ceil_div(long a, long b) { return -tm_floor_div(-a, b); }
+
+struct TmGeom {
+    long B = 1, T = 0, S = 0, N = 0, C = 0, s = 1, Q = 0;
+    long dh = 0;   // largest |lag| in units of c: floor((S - 1) / s)
+    DCP_HD long nd() const { return 2 * dh + 1; }
+    // c of the coefficients whose taps cover sample n: [c_first(n), c_last(n)] (clipped to [0, C))
+    DCP_HD long c_first(long n) const { long c = tm_ceil_div(n + Q - S + 1, s); return c < 0 ? 0 : c; }
+    DCP_HD long c_last(long n) const { long c = tm_floor_div(n + Q, s); return c > C - 1 ? C - 1 : c; }
+    // window of c for tap k and lag d:  0 <= s c - Q + k < N,  0 <= c < C,  0 <= c + d < C
+    DCP_HD void window(long k, long d, long* lo, long* hi) const {
+        long a = tm_ceil_div(Q - k, s), b = tm_floor_div(N - 1 + Q - k, s);
+        if (a < 0) a = 0;
+        if (a < -d) a = -d;
+        if (b > C - 1) b = C - 1;
+        if (b > C - 1 - d) b = C - 1 - d;
+        *lo = a;
+        *hi = b;
+    }
+    // core shared by every tap (intersection over k) and the union of all windows, for lag d.  An empty
+    // core is reported as cl = hi(union) + 1, ch = hi(union): every term is then a head term.
+    DCP_HD void core(long d, long* cl, long* ch, long* ul, long* uh) const {
+        long l0, h0, l1, h1;
+        window(0, d, &l0, &h0);
+        window(S - 1, d, &l1, &h1);
+        *ul = l1;   // lo(k) decreases with k, hi(k) too
+        *uh = h0;
+        *cl = l0;
+        *ch = h1;
+        if (*cl > *ch) { *cl = *uh + 1; *ch = *uh; }
+    }
+};
+
+// reference _coef_size (template_matching.py:102-112); false when the geometry is out of scope
+inline bool tm_geom(TmGeom& g, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding) {
+    if (B <= 0 || T <= 0 || S <= 0 || N <= 0 || stride <= 0 || S > N) return false;
+    if ((B | T | S | N) > 0x7fffffffLL) return false;
+    const long pad = padding ? N - 1 : N - S;
+    g.B = B; g.T = T; g.S = S; g.N = N; g.s = stride;
+    g.C = tm_floor_div(S + 2 * pad - N, stride) + 1;
+    if (g.C <= 0) return false;
+    g.Q = stride * (g.C - 1) - pad;
+    g.dh = (S - 1) / stride;
+    return true;
+}
+
+template <class T>
+DCP_HD T div_real(T v, real_t<T> d) {
+    if constexpr (scalar_traits<T>::is_complex) return T{v.re / d, v.im / d};
+    else return v / d;
+}
+
+// ---- dense helpers ------------------------------------------------------------------------------
+// out[t, c, n] = A[(t, c), n]   (_temp2mat)
+template <class T>
+__global__ void __launch_bounds__(256) tm_temp2mat_kernel(const T* __restrict__ D, TmGeom g, T* __restrict__ out) {
+    const long total = g.T * g.C * g.N;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+        const long n = i % g.N, c = (i / g.N) % g.C, t = i / (g.N * g.C);
+        const long k = n - g.s * c + g.Q;
+        out[i] = (k >= 0 && k < g.S) ? D[t * g.S + k] : zero_of<T>();
+    }
+}
+
+// out[b, t, k, n] = X[b, (t, k), n]   (_coef2mat)
+template <class T>
+__global__ void __launch_bounds__(256) tm_coef2mat_kernel(const T* __restrict__ x, TmGeom g, T* __restrict__ out) {
+    const long total = g.B * g.T * g.S * g.N;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+        const long n = i % g.N, k = (i / g.N) % g.S, bt = i / (g.N * g.S);
+        const long num = n - k + g.Q;   // = s c
+        T v = zero_of<T>();
+        if (num >= 0 && num % g.s == 0 && num / g.s < g.C) v = x[bt * g.C + num / g.s];
+        out[i] = v;
+    }
+}
+
+// ---- pass 1: r = y - v A'  (y == nullptr: r = x A, i.e. predict) ----------------------------------
+// One workgroup per 256 samples of one signal.  Per template, D[t, :] and the coefficients whose taps reach
+// the tile (the tile plus an S-wide halo, in units of c) are staged in LDS; lds_ok == 0 (a template too long
+// for LDS) reads them from global memory through the same (flat) pointers.
+template <class T>
+__global__ void __launch_bounds__(256) tm_residual_kernel(const T* __restrict__ y, const T* __restrict__ v,
+                                                          const real_t<T>* __restrict__ rinv,
+                                                          const T* __restrict__ D, TmGeom g, int lds_ok,
+                                                          T* __restrict__ r) {
+    extern __shared__ __attribute__((aligned(16))) char tm_smem[];
+    T* sD = reinterpret_cast<T*>(tm_smem);
+    const long b = blockIdx.y;
+    const long n0 = (long)blockIdx.x * 256;
+    const long n = n0 + threadIdx.x;
+    const long n1 = (n0 + 255 < g.N - 1) ? n0 + 255 : g.N - 1;
+    const long clo = g.c_first(n0), chi = g.c_last(n1);
+    T* sU = sD + g.S;
+    T acc = zero_of<T>();
+    for (long t = 0; t < g.T; ++t) {
+        const T* dsrc = D + t * g.S;
+        const T* vrow = v + (b * g.T + t) * g.C;
+        // usrc[c - uoff] = v[b, t, c] (/ rho[t, c] when staged).  The offset stays an index: a pointer rebased below
+        // the start of LDS wraps in the 32-bit LDS address space and leaves the aperture once it is used as flat.
+        const T* usrc;
+        long uoff = 0;
+        if (lds_ok) {
+            __syncthreads();
+            for (long k = threadIdx.x; k < g.S; k += 256) sD[k] = dsrc[k];
+            for (long c = clo + threadIdx.x; c <= chi; c += 256) {
+                T u = vrow[c];
+                if (rinv != nullptr) u = scale(u, rinv[t * g.C + c]);
+                sU[c - clo] = u;
+            }
+            __syncthreads();
+            dsrc = sD;
+            usrc = sU;
+            uoff = clo;
+        } else {
+            usrc = vrow;
+        }
+        if (n < g.N) {
+            const long c1 = g.c_last(n);
+            for (long c = g.c_first(n); c <= c1; ++c) {
+                T u = usrc[c - uoff];
+                if (!lds_ok && rinv != nullptr) u = scale(u, rinv[t * g.C + c]);
+                acc = madd(acc, u, dsrc[n - g.s * c + g.Q]);
+            }
+        }
+    }
+    if (n < g.N) r[b * g.N + n] = (y != nullptr) ? sub(y[b * g.N + n], acc) : acc;
+}
+
+// ---- pass 2: g = r A'^H with the proximal step in the epilogue -------------------------------------
+// One workgroup per 256 coefficients of one (signal, template); the samples they read (the tile's span plus
+// the S-wide halo) and conj(D[t, :]) are staged in LDS when they fit.
+template <class T, int PROX>
+struct TmStep {
+    const T* V;          // the point fed to the step (v')
+    const T* P;          // the iterate the stop test compares with (x0')
+    T* Nw;               // x0'_new
+    T* Vn;               // next v' (momentum), nullable
+    const real_t<T>* rinv;
+    const real_t<T>* alphak;   // alpha N / rho
+    const real_t<T>* tolk;     // tol rho
+    const real_t<T>* scal;     // scal[0] = 1 / L
+    real_t<T> coef;
+    int check;
+    int* flag;
+};
+
+template <class T, int PROX>
+__global__ void __launch_bounds__(256) tm_corr_step_kernel(const T* __restrict__ r, const T* __restrict__ D,
+                                                           TmGeom g, int lds_ok, TmStep<T, PROX> ep) {
+    typedef real_t<T> R;
+    extern __shared__ __attribute__((aligned(16))) char tm_smem[];
+    T* sD = reinterpret_cast<T*>(tm_smem);
+    T* sR = sD + g.S;
+    const long t = blockIdx.y, b = blockIdx.z;
+    const long c0 = (long)blockIdx.x * 256;
+    const long c = c0 + threadIdx.x;
+    const long c1 = (c0 + 255 < g.C - 1) ? c0 + 255 : g.C - 1;
+    long nlo = g.s * c0 - g.Q, nhi = g.s * c1 - g.Q + g.S - 1;
+    if (nlo < 0) nlo = 0;
+    if (nhi > g.N - 1) nhi = g.N - 1;
+    const T* rrow = r + b * g.N;
+    const T* dsrc = D + t * g.S;
+    const T* rsrc = rrow;   // rsrc[n - roff] = r[b, n] (an index offset, as in tm_residual_kernel)
+    long roff = 0;
+    if (lds_ok) {
+        for (long k = threadIdx.x; k < g.S; k += 256) sD[k] = conj_of(dsrc[k]);
+        for (long m = nlo + threadIdx.x; m <= nhi; m += 256) sR[m - nlo] = rrow[m];
+        __syncthreads();
+        rsrc = sR;
+        roff = nlo;
+    }
+    if (c >= g.C) return;
+    const long base = g.s * c - g.Q;
+    long k0 = -base, k1 = g.N - 1 - base;
+    if (k0 < 0) k0 = 0;
+    if (k1 > g.S - 1) k1 = g.S - 1;
+    T acc = zero_of<T>();
+    for (long k = k0; k <= k1; ++k) acc = madd(acc, rsrc[base + k - roff], lds_ok ? sD[k] : conj_of(dsrc[k]));
+    const long tc = t * g.C + c;
+    const long i = (b * g.T + t) * g.C + c;
+    const R Linv = ep.scal[0];
+    const T z = add(ep.V[i], scale(scale(acc, ep.rinv[tc]), Linv));
+    const T xn = prox_apply<PROX>(z, Linv * ep.alphak[tc]);
+    const T d = sub(xn, ep.P[i]);
+    if (ep.check && !((absval(d) - ep.tolk[tc]) < R(0))) *ep.flag = 1;
+    ep.Nw[i] = xn;
+    if (ep.Vn != nullptr) ep.Vn[i] = add(xn, scale(d, ep.coef));
+}
+
+// ---- prepare ------------------------------------------------------------------------------------
+// rho[t, c] = |A_(t,c)| over its taps inside [0, N); alpha_k = (alpha / rho) N; tol_k = tol rho; clears the flag
+template <class T>
+__global__ void __launch_bounds__(256) tm_rownorm_kernel(const T* __restrict__ D, TmGeom g, real_t<T> alpha,
+                                                         real_t<T> tol, real_t<T>* __restrict__ rho,
+                                                         real_t<T>* __restrict__ rinv, real_t<T>* __restrict__ alphak,
+                                                         real_t<T>* __restrict__ tolk, int* __restrict__ flag) {
+    typedef real_t<T> R;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *flag = 0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < g.T * g.C; i += (long)gridDim.x * 256L) {
+        const long t = i / g.C, c = i % g.C;
+        const long base = g.s * c - g.Q;
+        long k0 = -base, k1 = g.N - 1 - base;
+        if (k0 < 0) k0 = 0;
+        if (k1 > g.S - 1) k1 = g.S - 1;
+        R acc = 0;
+        for (long k = k0; k <= k1; ++k) acc += abs2(D[t * g.S + k]);
+        const R nr = sqrt(acc);
+        rho[i] = nr;
+        rinv[i] = R(1) / nr;
+        alphak[i] = (alpha / nr) * R(g.N);
+        tolk[i] = tol * nr;
+    }
+}
+
+// out[i] = x[i] * rho[tc]  (mul) or x[i] / rho[tc]
+template <class T>
+__global__ void __launch_bounds__(256) tm_scale_kernel(const T* __restrict__ x, const real_t<T>* __restrict__ rho,
+                                                       long total, long TC, int mul, T* __restrict__ out) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+        const real_t<T> s = rho[i % TC];
+        out[i] = mul ? scale(x[i], s) : div_real(x[i], s);
+    }
+}
+
+// corr[(t * T + t') * (2S - 1) + m + S - 1] = sum_k D[t, k] conj(D[t', k + m])
+template <class T>
+__global__ void __launch_bounds__(256) tm_lagcorr_kernel(const T* __restrict__ D, TmGeom g, T* __restrict__ corr) {
+    const long t = blockIdx.x / g.T, tp = blockIdx.x % g.T;
+    const long W = 2 * g.S - 1;
+    for (long j = threadIdx.x; j < W; j += 256) {
+        const long m = j - (g.S - 1);
+        long k0 = m < 0 ? -m : 0, k1 = m > 0 ? g.S - 1 - m : g.S - 1;
+        T acc = zero_of<T>();
+        for (long k = k0; k <= k1; ++k) acc = madd(acc, D[t * g.S + k], conj_of(D[tp * g.S + k + m]));
+        corr[blockIdx.x * W + j] = acc;
+    }
+}
+
+// Columns j = (t', c') with c' in [lo, hi] are Toeplitz: every row c within dh of c' exists and has all its taps
+// inside the signal, so their entries are Corr / (|D_t| |D_t'|) (rho of a full row is the same number, bit for bit,
+// for every c) and their column sum depends on t' alone.  lo > hi: no such column.
+DCP_HD void tm_toeplitz_cols(const TmGeom& g, long* lo, long* hi) {
+    long a = tm_ceil_div(g.Q, g.s), b = tm_floor_div(g.N - g.S + g.Q, g.s);   // rows with every tap inside
+    if (a < 0) a = 0;
+    if (b > g.C - 1) b = g.C - 1;
+    *lo = a + g.dh;
+    *hi = b - g.dh;
+}
+
+// One workgroup per column j = (t', c'):  sum_i |(A'A'^H)[i, j]|  (eigen.py:20 on the banded Gram), the band's
+// (t, c) split over the threads and summed by a fixed-order tree.
+//   mode 0: block t' sums the representative Toeplitz column (t', lo) into tsum[t'];
+//   mode 1: block number e of template t' sums its e-th non-Toeplitz column (c' < lo, then c' > hi) into colsum.
+template <class T>
+__global__ void __launch_bounds__(256) tm_gram_colsum_kernel(const T* __restrict__ D, const T* __restrict__ corr,
+                                                             const real_t<T>* __restrict__ rinv, TmGeom g, long lo,
+                                                             long hi, int mode, real_t<T>* __restrict__ tsum,
+                                                             real_t<T>* __restrict__ colsum) {
+    typedef real_t<T> R;
+    __shared__ R sh[4];
+    const long W = 2 * g.S - 1;
+    long tp, cp;
+    if (mode == 0) {
+        tp = blockIdx.x;
+        cp = lo;
+    } else {
+        const long nb = lo <= hi ? g.C - (hi - lo + 1) : g.C;
+        tp = blockIdx.x / nb;
+        const long e = blockIdx.x % nb;
+        cp = (lo <= hi && e >= lo) ? hi + 1 + (e - lo) : e;
+    }
+    const long j = tp * g.C + cp;
+    const long bj = g.s * cp - g.Q;                  // first sample of column j's taps
+    const bool inside = bj >= 0 && bj + g.S - 1 <= g.N - 1;
+    long ca = cp - g.dh, cb = cp + g.dh;
+    if (ca < 0) ca = 0;
+    if (cb > g.C - 1) cb = g.C - 1;
+    const long nc = cb - ca + 1;
+    R acc = 0;
+    for (long q = threadIdx.x; q < g.T * nc; q += 256) {
+        const long t = q / nc, c = ca + q % nc;
+        const long m = g.s * (c - cp);               // G_ij = sum_k D[t, k] conj(D[t', k + m]) over n inside
+        T v;
+        if (inside) {
+            v = corr[(t * g.T + tp) * W + m + g.S - 1];
+        } else {
+            const long bi = g.s * c - g.Q;
+            long k0 = m < 0 ? -m : 0, k1 = m > 0 ? g.S - 1 - m : g.S - 1;
+            if (k0 < -bi) k0 = -bi;
+            if (k1 > g.N - 1 - bi) k1 = g.N - 1 - bi;
+            v = zero_of<T>();
+            for (long k = k0; k <= k1; ++k) v = madd(v, D[t * g.S + k], conj_of(D[tp * g.S + k + m]));
+        }
+        acc += absval(v) * rinv[t * g.C + c] * rinv[j];
+    }
+    const R tot = block_sum_256(acc, sh);
+    if (threadIdx.x == 0) {
+        if (mode == 0) tsum[tp] = tot;
+        else colsum[j] = tot;
+    }
+}
+
+// colsum[(t', c')] = tsum[t'] for the Toeplitz columns c' in [lo, hi]
+template <class R>
+__global__ void __launch_bounds__(256) tm_gram_fill_kernel(TmGeom g, long lo, long hi, const R* __restrict__ tsum,
+                                                           R* __restrict__ colsum) {
+    const long w = hi - lo + 1;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < g.T * w; i += (long)gridDim.x * 256L)
+        colsum[(i / w) * g.C + lo + i % w] = tsum[i / w];
+}
+
+// scal[0] = 1 / max(v) (+ jitter on the max: scal[1] = max + jitter)   (one workgroup, fixed order)
+template <class R>
+__global__ void __launch_bounds__(256) tm_max_kernel(const R* __restrict__ v, long n, R jitter, R* __restrict__ scal) {
+    __shared__ R sh[4];
+    R best = 0;
+    for (long i = threadIdx.x; i < n; i += 256) best = (v[i] > best || v[i] != v[i]) ? v[i] : best;
+    const R m = block_max_256(best, sh);
+    if (threadIdx.x == 0) {
+        scal[0] = R(1) / (m + jitter);
+        scal[1] = m + jitter;
+    }
+}
+
+// ---- dictionary statistics ----------------------------------------------------------------------
+// mpart[((b T + t) T + t') nd + (d + dh)] = sum_(c in core(d)) x[b, t, c] conj(x[b, t', c + d])
+template <class T>
+__global__ void __launch_bounds__(256) tm_stats_core_kernel(const T* __restrict__ x, TmGeom g, T* __restrict__ mpart) {
+    const long tp = blockIdx.x, t = blockIdx.y, b = blockIdx.z;
+    const T* xa = x + (b * g.T + t) * g.C;
+    const T* xb = x + (b * g.T + tp) * g.C;
+    const long nd = g.nd();
+    for (long j = threadIdx.x; j < nd; j += 256) {
+        const long d = j - g.dh;
+        long cl, ch, ul, uh;
+        g.core(d, &cl, &ch, &ul, &uh);
+        T acc = zero_of<T>();
+        for (long c = cl; c <= ch; ++c) acc = madd(acc, xa[c], conj_of(xb[c + d]));
+        mpart[((b * g.T + t) * g.T + tp) * nd + j] = acc;
+    }
+}
+
+// Edge terms, summed over the batch in order:  eh[.., e] at c = cl - 1 - e,  et[.., e] at c = ch + 1 + e
+template <class T>
+__global__ void __launch_bounds__(256) tm_stats_edge_kernel(const T* __restrict__ x, TmGeom g, long hmax,
+                                                            T* __restrict__ eh, T* __restrict__ et) {
+    const long tp = blockIdx.x, t = blockIdx.y;
+    const long nd = g.nd();
+    for (long q = threadIdx.x; q < nd * hmax * 2; q += 256) {
+        const long side = q / (nd * hmax), j = (q / hmax) % nd, e = q % hmax;
+        const long d = j - g.dh;
+        long cl, ch, ul, uh;
+        g.core(d, &cl, &ch, &ul, &uh);
+        const long c = side == 0 ? cl - 1 - e : ch + 1 + e;
+        T acc = zero_of<T>();
+        if (side == 0 ? (c >= ul) : (c <= uh)) {
+            for (long b = 0; b < g.B; ++b)
+                acc = madd(acc, x[(b * g.T + t) * g.C + c], conj_of(x[(b * g.T + tp) * g.C + c + d]));
+        }
+        T* dst = side == 0 ? eh : et;
+        dst[((t * g.T + tp) * nd + j) * hmax + e] = acc;
+    }
+}
+
+// yxpart[(b T + t) S + k] = sum_c x[b, t, c] y[b, s c - Q + k]
+template <class T>
+__global__ void __launch_bounds__(256) tm_stats_yx_kernel(const T* __restrict__ y, const T* __restrict__ x, TmGeom g,
+                                                          T* __restrict__ yxpart) {
+    const long t = blockIdx.x, b = blockIdx.y;
+    for (long k = threadIdx.x; k < g.S; k += 256) {
+        long lo, hi;
+        g.window(k, 0, &lo, &hi);
+        T acc = zero_of<T>();
+        for (long c = lo; c <= hi; ++c) acc = madd(acc, x[(b * g.T + t) * g.C + c], y[b * g.N + g.s * c - g.Q + k]);
+        yxpart[(b * g.T + t) * g.S + k] = acc;
+    }
+}
+
+// One workgroup per row i = (t, k):  XXt[i, :] and yX[i], written (acc_it == 0) or added as stat / acc_it
+template <class T>
+__global__ void __launch_bounds__(256) tm_stats_assemble_kernel(const T* __restrict__ mpart, const T* __restrict__ eh,
+                                                                const T* __restrict__ et,
+                                                                const T* __restrict__ yxpart, TmGeom g, long hmax,
+                                                                int acc_it, T* __restrict__ XXt, T* __restrict__ yX) {
+    typedef real_t<T> R;
+    const long t = blockIdx.x / g.S, k = blockIdx.x % g.S;
+    const long TS = g.T * g.S, nd = g.nd();
+    for (long jcol = threadIdx.x; jcol < TS; jcol += 256) {
+        const long tp = jcol / g.S, kp = jcol % g.S;
+        T val = zero_of<T>();
+        if ((k - kp) % g.s == 0) {
+            const long d = (k - kp) / g.s, j = d + g.dh;
+            long lo, hi, cl, ch, ul, uh;
+            g.window(k, d, &lo, &hi);
+            g.core(d, &cl, &ch, &ul, &uh);
+            if (lo <= hi) {
+                const long base = (t * g.T + tp) * nd + j;
+                const long hend = hi < cl - 1 ? hi : cl - 1;
+                for (long c = lo; c <= hend; ++c) val = add(val, eh[base * hmax + (cl - 1 - c)]);
+                if (cl <= ch && lo <= cl && hi >= ch) {
+                    T m = zero_of<T>();
+                    for (long b = 0; b < g.B; ++b) m = add(m, mpart[((b * g.T + t) * g.T + tp) * nd + j]);
+                    val = add(val, m);
+                }
+                const long tbeg = lo > ch + 1 ? lo : ch + 1;
+                for (long c = tbeg; c <= hi; ++c) val = add(val, et[base * hmax + (c - ch - 1)]);
+            }
+        }
+        const long o = blockIdx.x * TS + jcol;
+        XXt[o] = acc_it ? add(XXt[o], div_real(val, R(acc_it))) : val;
+    }
+    if (threadIdx.x == 0) {
+        T s = zero_of<T>();
+        for (long b = 0; b < g.B; ++b) s = add(s, yxpart[(b * g.T + t) * g.S + k]);
+        yX[blockIdx.x] = acc_it ? add(yX[blockIdx.x], div_real(s, R(acc_it))) : s;
+    }
+}
+
+// ---- D update -------------------------------------------------------------------------------------
+// Per index j of D_flat: colabs[j] = sum_i |XXt[i, j]|, step[j] = yX[j] - sum_i XXt[j, i] D[i]
+template <class T>
+__global__ void __launch_bounds__(256) tm_dupdate_rows_kernel(const T* __restrict__ XXt, const T* __restrict__ yX,
+                                                              const T* __restrict__ D, long n,
+                                                              real_t<T>* __restrict__ colabs, T* __restrict__ step) {
+    typedef real_t<T> R;
+    __shared__ R sh[4];
+    const long j = blockIdx.x;
+    R ca = 0, re = 0, im = 0;
+    for (long i = threadIdx.x; i < n; i += 256) {
+        ca += absval(XXt[i * n + j]);
+        const T p = mul(XXt[j * n + i], D[i]);
+        if constexpr (scalar_traits<T>::is_complex) { re += p.re; im += p.im; }
+        else re += p;
+    }
+    const R tca = block_sum_256(ca, sh);
+    const R tre = block_sum_256(re, sh);
+    R tim = 0;
+    if constexpr (scalar_traits<T>::is_complex) tim = block_sum_256(im, sh);
+    if (threadIdx.x == 0) {
+        colabs[j] = tca;
+        T dot;
+        if constexpr (scalar_traits<T>::is_complex) dot = T{tre, tim};
+        else dot = tre;
+        step[j] = sub(yX[j], dot);
+    }
+}
+
+// U = D + step / L  with L = scal[1]
+template <class T>
+__global__ void __launch_bounds__(256) tm_dupdate_apply_kernel(const T* __restrict__ D, const T* __restrict__ step,
+                                                               const real_t<T>* __restrict__ scal, long n,
+                                                               T* __restrict__ U) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L)
+        U[i] = add(D[i], div_real(step[i], scal[1]));
+}
+
+// ---- minibatch windows (template_matching.py:219-253) ---------------------------------------------
+// yw[j, n] = y[ib[j], in[j] + n];  xw[j, t, c] = x[ib[j], t, in[j] + c]
+template <class T>
+__global__ void __launch_bounds__(256) tm_gather_kernel(const T* __restrict__ y, const T* __restrict__ x,
+                                                        const int64_t* __restrict__ ib, const int64_t* __restrict__ in,
+                                                        long m, long N, long T_, long C, long w, long cw,
+                                                        T* __restrict__ yw, T* __restrict__ xw) {
+    const long ny = m * w, nx = m * T_ * cw;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < ny + nx; i += (long)gridDim.x * 256L) {
+        if (i < ny) {
+            const long j = i / w, n = i % w;
+            yw[i] = y[ib[j] * N + in[j] + n];
+        } else {
+            const long q = i - ny;
+            const long j = q / (T_ * cw), t = (q / cw) % T_, c = q % cw;
+            xw[q] = x[(ib[j] * T_ + t) * C + in[j] + c];
+        }
+    }
+}
+
+// x[ib[j], t, in[j] + c] = xw[j, t, c], the last window that covers an element wins (sequential write-back)
+template <class T>
+__global__ void __launch_bounds__(256) tm_scatter_kernel(const T* __restrict__ xw, const int64_t* __restrict__ ib,
+                                                         const int64_t* __restrict__ in, long m, long T_, long C,
+                                                         long cw, T* __restrict__ x) {
+    const long nx = m * T_ * cw;
+    for (long q = blockIdx.x * 256L + threadIdx.x; q < nx; q += (long)gridDim.x * 256L) {
+        const long j = q / (T_ * cw), t = (q / cw) % T_, c = q % cw;
+        const long b = ib[j], pos = in[j] + c;
+        bool later = false;
+        for (long jj = j + 1; jj < m && !later; ++jj) later = ib[jj] == b && in[jj] <= pos && pos < in[jj] + cw;
+        if (!later) x[(b * T_ + t) * C + pos] = xw[q];
+    }
+}
+
+// =================================================================================================
+// Host side
+// =================================================================================================
+constexpr size_t kTmLdsBytes = 48 * 1024;
+
+inline int tm_grid(long n) {
+    long g = (n + 255) / 256;
+    if (g > 65536) g = 65536;
+    return (int)(g < 1 ? 1 : g);
+}
+
+template <class T>
+inline int tm_launch_residual(dcp_handle* h, const T* y, const T* v, const real_t<T>* rinv, const T* D,
+                              const TmGeom& g, T* r) {
+    const long span = (255 + g.S - 1) / g.s + 2;
+    size_t bytes = (size_t)(g.S + span) * sizeof(T);
+    const int lds_ok = bytes <= kTmLdsBytes;
+    if (!lds_ok) bytes = 0;
+    hipLaunchKernelGGL((tm_residual_kernel<T>), dim3((g.N + 255) / 256, g.B), dim3(256), bytes, h->stream, y, v,
+                       rinv, D, g, lds_ok, r);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
+template <class T, int PROX>
+inline int tm_launch_step(dcp_handle* h, const T* r, const T* D, const TmGeom& g, const TmStep<T, PROX>& ep) {
+    const long span = 255 * g.s + g.S;
+    size_t bytes = (size_t)(g.S + span) * sizeof(T);
+    const int lds_ok = bytes <= kTmLdsBytes;
+    if (!lds_ok) bytes = 0;
+    hipLaunchKernelGGL((tm_corr_step_kernel<T, PROX>), dim3((g.C + 255) / 256, g.T, g.B), dim3(256), bytes,
+                       h->stream, r, D, g, lds_ok, ep);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
+// Structured solve_fastpath for ista / acc_ista / fista (+ _pos).  Y [B, N], D [T, S], X [B, T, C]
+// (in: initial estimate, out: solution).  The stop test of a check iteration (i % 10 == 0) is published to
+// pinned host memory and read one iteration late, as lasso_solve does.
+template <class T, int PROX>
+inline int tm_lasso_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, real_t<T> alpha,
+                          real_t<T> tol, int maxiter, int method, int* it_out) {
+    typedef real_t<T> R;
+    hipStream_t st = h->stream;
+    const long TC = g.T * g.C, BX = g.B * TC;
+    WsPlan plan;
+    for (int q = 0; q < 5; ++q) plan.add<R>(TC);          // rho, rinv, alphak, tolk, colsum
+    plan.add<R>(g.T);                                     // Toeplitz column sums
+    plan.add<T>(g.T * g.T * (2 * g.S - 1));              // lag correlations
+    plan.add<R>(4);
+    plan.add<int>(4);
+    plan.add<T>(g.B * g.N);                               // residual
+    for (int q = 0; q < 4; ++q) plan.add<T>(BX);          // iterates
+    DCP_TRY(ws_reserve(h, plan.total));
+    ws_reset(h);
+    R* rho = ws_alloc<R>(h, TC);
+    R* rinv = ws_alloc<R>(h, TC);
+    R* alphak = ws_alloc<R>(h, TC);
+    R* tolk = ws_alloc<R>(h, TC);
+    R* colsum = ws_alloc<R>(h, TC);
+    R* tsum = ws_alloc<R>(h, g.T);
+    T* corr = ws_alloc<T>(h, g.T * g.T * (2 * g.S - 1));
+    R* scal = ws_alloc<R>(h, 4);
+    int* flag = ws_alloc<int>(h, 4);
+    T* r = ws_alloc<T>(h, g.B * g.N);
+    T* xb[4];
+    for (int q = 0; q < 4; ++q) xb[q] = ws_alloc<T>(h, BX);
+    if (!xb[3]) return fail(h, DCP_ERR_INTERNAL, "template lasso workspace");
+    void* hostv = nullptr;
+    DCP_TRY(host_scratch(h, 64, &hostv));
+    int* host_flag = reinterpret_cast<int*>(hostv);
+
+    // ---- prepare: row norms, scaled alpha / tol, x' = x rho, 1 / Gershgorin(A'A'^H) ----
+    hipLaunchKernelGGL((tm_rownorm_kernel<T>), dim3(tm_grid(TC)), dim3(256), 0, st, D, g, alpha, tol, rho, rinv,
+                       alphak, tolk, flag);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    hipLaunchKernelGGL((tm_scale_kernel<T>), dim3(tm_grid(BX)), dim3(256), 0, st, (const T*)X, (const R*)rho, BX, TC,
+                       1, xb[0]);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    hipLaunchKernelGGL((tm_lagcorr_kernel<T>), dim3(g.T * g.T), dim3(256), 0, st, D, g, corr);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    {   // Gershgorin of A'A'^H: the Toeplitz columns once per template, the boundary columns one by one
+        long lo, hi;
+        tm_toeplitz_cols(g, &lo, &hi);
+        if (lo <= hi) {
+            hipLaunchKernelGGL((tm_gram_colsum_kernel<T>), dim3(g.T), dim3(256), 0, st, D, (const T*)corr,
+                               (const R*)rinv, g, lo, hi, 0, tsum, colsum);
+            DCP_LAUNCH_OK(h, hipGetLastError());
+            hipLaunchKernelGGL((tm_gram_fill_kernel<R>), dim3(tm_grid(g.T * (hi - lo + 1))), dim3(256), 0, st, g, lo,
+                               hi, (const R*)tsum, colsum);
+            DCP_LAUNCH_OK(h, hipGetLastError());
+        }
+        const long nb = lo <= hi ? g.C - (hi - lo + 1) : g.C;
+        if (nb > 0) {
+            hipLaunchKernelGGL((tm_gram_colsum_kernel<T>), dim3(g.T * nb), dim3(256), 0, st, D, (const T*)corr,
+                               (const R*)rinv, g, lo, hi, 1, tsum, colsum);
+            DCP_LAUNCH_OK(h, hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL((tm_max_kernel<R>), dim3(1), dim3(256), 0, st, (const R*)colsum, TC, R(0), scal);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+
+    const bool mom = method != DCP_LASSO_ISTA;
+    T* P = xb[0];
+    T* V = xb[0];
+    T* lastP = xb[0];
+    T* lastNw = xb[0];
+    T* result = xb[0];
+    int it = maxiter - 1;
+    double beta = 1.0;
+    bool converged = false;
+    int pend_i = -1;
+    T* pend_x = nullptr;
+    auto resolve = [&](bool* stop) -> int {
+        *stop = false;
+        if (pend_i < 0) return DCP_OK;
+        DCP_TRY(poll_host_flag(h, host_flag));
+        if (*host_flag == 0) {
+            it = pend_i;
+            result = pend_x;
+            converged = true;
+            *stop = true;
+        }
+        pend_i = -1;
+        return DCP_OK;
+    };
+    for (int i = 0; i < maxiter; ++i) {
+        T* Nw = nullptr;
+        T* Vn = nullptr;
+        for (int q = 0; q < 4; ++q) {
+            T* c = xb[q];
+            if (c == P || c == V) continue;
+            if (Nw == nullptr) Nw = c;
+            else if (Vn == nullptr) Vn = c;
+        }
+        R coef = R(0);
+        double beta_new = beta;
+        if (method == DCP_LASSO_ACC_ISTA) {
+            coef = (R)((double)i / (double)(i + 3));                    // lasso.py:353
+        } else if (method == DCP_LASSO_FISTA) {
+            beta_new = 0.5 * (1.0 + sqrt(1.0 + 4.0 * beta * beta));     // lasso.py:411
+            coef = (R)((beta - 1.0) / beta_new);
+        }
+        const int check = (i % 10 == 0) ? 1 : 0;
+        const bool had_pending = pend_i >= 0;
+        DCP_TRY(tm_launch_residual<T>(h, Y, V, rinv, D, g, r));
+        TmStep<T, PROX> ep{V, P, Nw, mom ? Vn : nullptr, rinv, alphak, tolk, scal, coef, check, flag};
+        DCP_TRY((tm_launch_step<T, PROX>(h, r, D, g, ep)));
+        if (had_pending) {
+            bool stop = false;
+            DCP_TRY(resolve(&stop));
+            if (stop) break;
+        }
+        if (check) {
+            *reinterpret_cast<volatile int*>(host_flag) = -1;
+            hipLaunchKernelGGL(flag_publish_kernel<void>, dim3(1), dim3(64), 0, st, flag, host_flag);
+            DCP_LAUNCH_OK(h, hipGetLastError());
+            pend_i = i;
+            pend_x = Nw;
+        }
+        lastP = P;
+        lastNw = Nw;
+        P = Nw;
+        V = mom ? Vn : Nw;
+        beta = beta_new;
+    }
+    if (!converged) {
+        bool stop = false;
+        DCP_TRY(resolve(&stop));
+    }
+    // on exhaustion ista / fista return the latest iterate, acc_ista the one before it (lasso.py:357)
+    if (!converged) result = (method == DCP_LASSO_ACC_ISTA) ? lastP : lastNw;
+    hipLaunchKernelGGL((tm_scale_kernel<T>), dim3(tm_grid(BX)), dim3(256), 0, st, (const T*)result, (const R*)rho, BX,
+                       TC, 0, X);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    DCP_HIP_OK(h, hipStreamSynchronize(st));
+    *it_out = it;
+    return DCP_OK;
+}
+
+inline long tm_hmax(const TmGeom& g) {
+    long hm = 1;
+    for (long d = -g.dh; d <= g.dh; ++d) {
+        long cl, ch, ul, uh;
+        g.core(d, &cl, &ch, &ul, &uh);
+        if (cl - ul > hm) hm = cl - ul;
+        if (uh - ch > hm) hm = uh - ch;
+    }
+    return hm;
+}
+
+// Statistics of x (written, or added as stat / acc_it to the running sums XXt [TS, TS], yX [TS]) and the
+// D update D <- l2(D + (yX - XXt D) / (Gershgorin(XXt) + 1e-15)); *maxdiff = max |D - D_new|.
+template <class T>
+inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
+                    double* maxdiff) {
+    typedef real_t<T> R;
+    hipStream_t st = h->stream;
+    const long nd = g.nd(), TS = g.T * g.S, hmax = tm_hmax(g);
+    WsPlan plan;
+    plan.add<T>(g.B * g.T * g.T * nd);
+    plan.add<T>(g.T * g.T * nd * hmax);
+    plan.add<T>(g.T * g.T * nd * hmax);
+    plan.add<T>(g.B * TS);
+    plan.add<R>(TS);
+    plan.add<T>(TS);
+    plan.add<T>(TS);
+    plan.add<T>(TS);
+    plan.add<R>(g.T);
+    plan.add<R>(4);
+    DCP_TRY(ws_reserve(h, plan.total));
+    ws_reset(h);
+    T* mpart = ws_alloc<T>(h, g.B * g.T * g.T * nd);
+    T* eh = ws_alloc<T>(h, g.T * g.T * nd * hmax);
+    T* et = ws_alloc<T>(h, g.T * g.T * nd * hmax);
+    T* yxpart = ws_alloc<T>(h, g.B * TS);
+    R* colabs = ws_alloc<R>(h, TS);
+    T* step = ws_alloc<T>(h, TS);
+    T* U = ws_alloc<T>(h, TS);
+    T* Dn = ws_alloc<T>(h, TS);
+    R* rowmax = ws_alloc<R>(h, g.T);
+    R* scal = ws_alloc<R>(h, 4);
+    if (!scal) return fail(h, DCP_ERR_INTERNAL, "template dstep workspace");
+    {
+        ProfScope ps(h, DCP_PROF_STATS);
+        hipLaunchKernelGGL((tm_stats_core_kernel<T>), dim3(g.T, g.T, g.B), dim3(256), 0, st, X, g, mpart);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        hipLaunchKernelGGL((tm_stats_edge_kernel<T>), dim3(g.T, g.T), dim3(256), 0, st, X, g, hmax, eh, et);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        hipLaunchKernelGGL((tm_stats_yx_kernel<T>), dim3(g.T, g.B), dim3(256), 0, st, Y, X, g, yxpart);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        hipLaunchKernelGGL((tm_stats_assemble_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)mpart, (const T*)eh,
+                           (const T*)et, (const T*)yxpart, g, hmax, acc_it, XXt, yX);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL((tm_dupdate_rows_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)XXt, (const T*)yX,
+                       (const T*)D, TS, colabs, step);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    hipLaunchKernelGGL((tm_max_kernel<R>), dim3(1), dim3(256), 0, st, (const R*)colabs, TS, R(1.0e-15), scal);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    hipLaunchKernelGGL((tm_dupdate_apply_kernel<T>), dim3(tm_grid(TS)), dim3(256), 0, st, (const T*)D,
+                       (const T*)step, (const R*)scal, TS, U);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    // D_new = l2(U) (normalize.py:2-10) into its own buffer (the kernel's ref and out are restrict), rowmax[t] =
+    // max |D - D_new| over the row; then D <- D_new
+    hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(g.T), dim3(256), 0, st, (const T*)U, g.S, g.S, 0, (const T*)D,
+                       g.S, Dn, g.S, rowmax);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    DCP_HIP_OK(h, hipMemcpyAsync(D, Dn, (size_t)TS * sizeof(T), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL((tm_max_kernel<R>), dim3(1), dim3(256), 0, st, (const R*)rowmax, g.T, R(0), scal + 2);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    void* hostv = nullptr;
+    DCP_TRY(host_scratch(h, 64, &hostv));
+    DCP_HIP_OK(h, hipMemcpyAsync(hostv, scal + 3, sizeof(R), hipMemcpyDeviceToHost, st));
+    DCP_HIP_OK(h, hipStreamSynchronize(st));
+    *maxdiff = (double)*reinterpret_cast<R*>(hostv);
+    return DCP_OK;
+}
+
+}  // namespace dcp
+
+// ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip) ------------------------------
+#define DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding)                                    \
+    dcp::TmGeom g;                                                                                  \
+    if (!(h)) return DCP_ERR_INVALID;                                                               \
+    if (!dcp::tm_geom(g, B, T_, S, N, stride, padding))                                             \
+        return dcp::fail(h, DCP_ERR_INVALID, "template geometry: need 0 < S <= N, stride > 0, C > 0"); \
+    DCP_HIP_OK(h, hipSetDevice((h)->device))
+
+#define DCP_TM_DEFINE(SFX, TYPE)                                                                              \
+    extern "C" int dcp_tm_temp2mat_##SFX(dcp_handle* h, const void* D, int64_t T_, int64_t S, int64_t N,       \
+                                          int64_t stride, int padding, void* out) {                           \
+        DCP_TM_GEOM_OR_FAIL(h, g, 1, T_, S, N, stride, padding);                                              \
+        if (!D || !out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                                  \
+        hipLaunchKernelGGL((dcp::tm_temp2mat_kernel<TYPE>), dim3(dcp::tm_grid(g.T * g.C * g.N)), dim3(256), 0, \
+                           h->stream, (const TYPE*)D, g, (TYPE*)out);                                         \
+        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
+        return DCP_OK;                                                                                         \
+    }                                                                                                          \
+    extern "C" int dcp_tm_coef2mat_##SFX(dcp_handle* h, const void* X, int64_t B, int64_t T_, int64_t S,      \
+                                          int64_t N, int64_t stride, int padding, void* out) {                \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        if (!X || !out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                                  \
+        hipLaunchKernelGGL((dcp::tm_coef2mat_kernel<TYPE>), dim3(dcp::tm_grid(g.B * g.T * g.S * g.N)),         \
+                           dim3(256), 0, h->stream, (const TYPE*)X, g, (TYPE*)out);                           \
+        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
+        return DCP_OK;                                                                                         \
+    }                                                                                                          \
+    extern "C" int dcp_tm_predict_##SFX(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T_,   \
+                                         int64_t S, int64_t N, int64_t stride, int padding, void* out) {      \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        if (!X || !D || !out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                            \
+        return dcp::tm_launch_residual<TYPE>(h, (const TYPE*)nullptr, (const TYPE*)X,                          \
+                                             (const dcp::real_t<TYPE>*)nullptr, (const TYPE*)D, g,             \
+                                             (TYPE*)out);                                                      \
+    }                                                                                                          \
+    extern "C" int dcp_tm_lasso_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,        \
+                                       int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,         \
+                                       double alpha, double tol, int maxiter, int method, int positive,       \
+                                       int* it_out) {                                                          \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        typedef dcp::real_t<TYPE> R;                                                                           \
+        if (!Y || !D || !X || !it_out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                  \
+        if (method != DCP_LASSO_ISTA && method != DCP_LASSO_ACC_ISTA && method != DCP_LASSO_FISTA)             \
+            return dcp::fail(h, DCP_ERR_INVALID, "structured solver: ista, acc_ista or fista");               \
+        if (positive && dcp::scalar_traits<TYPE>::is_complex)                                                  \
+            return dcp::fail(h, DCP_ERR_INVALID, "positive solvers need a real dtype (lasso.py:92)");          \
+        if (dcp::scalar_traits<TYPE>::is_complex)                                                              \
+            return dcp::tm_lasso_solve<TYPE, dcp::PROX_COMPLEX>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X,  \
+                                                                g, (R)alpha, (R)tol, maxiter, method, it_out); \
+        if (positive)                                                                                          \
+            return dcp::tm_lasso_solve<TYPE, dcp::PROX_POSITIVE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, \
+                                                                 g, (R)alpha, (R)tol, maxiter, method,        \
+                                                                 it_out);                                      \
+        return dcp::tm_lasso_solve<TYPE, dcp::PROX_REAL>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g,       \
+                                                         (R)alpha, (R)tol, maxiter, method, it_out);          \
+    }                                                                                                          \
+    extern "C" int dcp_tm_dstep_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt,        \
+                                       void* yX, int64_t B, int64_t T_, int64_t S, int64_t N, int64_t stride, \
+                                       int padding, int acc_it, double* maxdiff) {                             \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        if (!Y || !X || !D || !XXt || !yX || !maxdiff) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
+        if (acc_it < 0) return dcp::fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");                           \
+        return dcp::tm_dstep<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt, (TYPE*)yX, g,      \
+                                   acc_it, maxdiff);                                                           \
+    }                                                                                                          \
+    extern "C" int dcp_tm_gather_windows_##SFX(dcp_handle* h, const void* Y, const void* X,                   \
+                                                const int64_t* idx_b, const int64_t* idx_n, int64_t m,        \
+                                                int64_t B, int64_t T_, int64_t S, int64_t N, int64_t w,       \
+                                                int64_t stride, int padding, void* Yw, void* Xw) {            \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        dcp::TmGeom gw;                                                                                        \
+        if (!dcp::tm_geom(gw, m, T_, S, w, stride, padding) || w > N)                                          \
+            return dcp::fail(h, DCP_ERR_INVALID, "window geometry");                                           \
+        if (!Y || !X || !idx_b || !idx_n || !Yw || !Xw) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
+        hipLaunchKernelGGL((dcp::tm_gather_kernel<TYPE>), dim3(dcp::tm_grid(m * (w + g.T * gw.C))), dim3(256), \
+                           0, h->stream, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, (long)m, g.N, g.T, g.C, \
+                           (long)w, gw.C, (TYPE*)Yw, (TYPE*)Xw);                                               \
+        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
+        return DCP_OK;                                                                                         \
+    }                                                                                                          \
+    extern "C" int dcp_tm_scatter_windows_##SFX(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, \
+                                                 const int64_t* idx_n, int64_t m, int64_t B, int64_t T_,      \
+                                                 int64_t S, int64_t N, int64_t w, int64_t stride,             \
+                                                 int padding) {                                                \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        dcp::TmGeom gw;                                                                                        \
+        if (!dcp::tm_geom(gw, m, T_, S, w, stride, padding) || w > N)                                          \
+            return dcp::fail(h, DCP_ERR_INVALID, "window geometry");                                           \
+        if (!Xw || !X || !idx_b || !idx_n) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");              \
+        hipLaunchKernelGGL((dcp::tm_scatter_kernel<TYPE>), dim3(dcp::tm_grid(m * g.T * gw.C)), dim3(256), 0,   \
+                           h->stream, (const TYPE*)Xw, idx_b, idx_n, (long)m, g.T, g.C, gw.C, (TYPE*)X);       \
+        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
+        return DCP_OK;                                                                                         \
+    }

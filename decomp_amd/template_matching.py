@@ -1,0 +1,364 @@
+"""1-D convolutional template learning -- drop-in for ``decomp.template_matching`` on MI355X.
+
+Same entry points, argument meaning, return convention and error behaviour as the reference's
+decomp/template_matching.py.  The reference builds the convolution as dense im2col matrices
+(``_temp2mat`` [T, C, N], ``_coef2mat`` [B, T, S, N]) and has no GPU path; here nothing of that
+size is formed on the hot path (include/decomp_hip.h ``dcp_tm_*``, decomp_amd/csrc/template_impl.hpp):
+
+  * the LASSO step with 'ista', 'acc_ista', 'fista' (and their '_pos' forms) runs on the structured
+    operator: one iteration is a residual pass over the signal and a correlation pass over the
+    coefficients, the proximal step fused into the second;
+  * the dictionary step's statistics XXt [T S, T S] and yX [T S] are built from lag correlations of
+    the coefficients, and D is updated by one fused chain of small kernels.
+
+'cd', 'parallel_cd' and 'admm' have no structured form: for them ``_temp2mat`` is materialised on the
+device and the dense ``dcp_lasso_*`` solvers of decomp_amd.lasso run on it.  That path is correct but
+dense (memory T C N, work per iteration of the dense solvers).
+
+The outer loop reads one number per iteration from the device, max|dD|, for the reference's stop test.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _arrays, _hip, lasso
+from ._arrays import get_array_module
+from .utils import assertion, normalize
+from .utils.exceptions import DtypeMismatchError
+from .utils.data import minibatch_index
+
+_JITTER = 1.0e-15
+_STRUCTURED = ('ista', 'acc_ista', 'fista')
+_DENSE = ('cd', 'parallel_cd', 'admm')
+
+
+def solve(y, D, alpha, stride=1, padding='SAME', x=None, tol=1.0e-4,
+          minibatch=None, size_of_minibatch=None, maxiter=1000,
+          lasso_method='acc_ista', lasso_iter=10, lasso_tol=1.0e-5,
+          mask=None, random_seed=None):
+    """
+    Learn templates with lasso regularisation,
+        argmin_{x, D} |y - x * D|^2 + alpha |x|   s.t. |D_t|^2 <= 1,
+    where x * D is the 1-D convolution of the coefficients x [..., T, C] with the templates D [T, S].
+
+    y: [N] or [B, N]; D: initial templates [T, S]; x: optional initial coefficients [T, C] / [B, T, C]
+    with C = _coef_size(S, N, stride, padding).  float or complex, all of one dtype.
+    minibatch: number of windows of ``size_of_minibatch`` samples drawn per iteration
+    (RandomState(random_seed)); None solves on the whole batch.
+    Returns (it, D, x) as the reference does.  NumPy in -> NumPy out; torch GPU tensors stay on the device.
+    """
+    get_array_module(y, D, x)                                         # template_matching.py:48
+    rng = np.random.RandomState(random_seed)
+    x_given = x
+    if x is None:
+        coef_size = _coef_size(D.shape[-1], y.shape[-1], stride=stride, padding=padding)
+        if len(y.shape) == 2:
+            shape = (y.shape[0], D.shape[0], coef_size)
+        else:
+            shape = (D.shape[0], coef_size)
+        x = lasso._ZerosLike(shape, _arrays.np_dtype(y))
+
+    assertion.assert_dtypes(y=y, D=D, x=x)
+    assertion.assert_dtypes(mask=mask, dtypes='f')
+    assertion.assert_shapes('y', y, 'mask', mask)
+
+    if minibatch is not None and size_of_minibatch is None:
+        raise ValueError('size_of_minibatch should be specified with '
+                         'minibatch calculation.')
+
+    return solve_fastpath(y, D, alpha, x_given if x_given is not None else x, stride, padding,
+                          tol, minibatch, size_of_minibatch, maxiter,
+                          lasso_method, lasso_iter, lasso_tol, rng, None, mask=mask)
+
+
+def solve_fastpath(y, D, alpha, x, stride, padding, tol,
+                   minibatch, size_of_minibatch, maxiter,
+                   lasso_method, lasso_iter, lasso_tol, rng, xp,
+                   mask=None):
+    """No defaults and no validation (``x`` may be the zeros placeholder of ``solve``); ``xp`` is
+    accepted for signature compatibility, the array kind is taken from ``y``."""
+    if mask is not None:
+        raise NotImplementedError('Template matching with mask is not '
+                                  'yet implemented.')
+    import torch
+    kind = 'torch' if _arrays.is_torch(y) else 'numpy'
+    yd = _arrays.to_device(y)
+    one_d = yd.dim() == 1
+    y2 = yd.unsqueeze(0) if one_d else yd
+    if isinstance(x, lasso._ZerosLike):
+        xd = torch.zeros(((1,) if one_d else ()) + tuple(x.shape), dtype=yd.dtype, device=yd.device)
+    else:
+        xd = _arrays.to_device(x, yd.device.index, copy=True)
+        if one_d:
+            xd = xd.unsqueeze(0)
+    Dd = _arrays.to_device(D, yd.device.index)
+
+    if minibatch is None:
+        it, Dn, xn = solve_batch(y2, Dd, alpha, xd, stride, padding, tol, maxiter,
+                                 lasso_method, lasso_iter, lasso_tol, xp)
+    else:
+        it, Dn, xn = solve_minibatch(y2, Dd, alpha, xd, stride, padding, tol,
+                                     minibatch, size_of_minibatch, maxiter,
+                                     lasso_method, lasso_iter, lasso_tol, rng, xp)
+    if one_d:
+        xn = xn.squeeze(0)
+    return it, _arrays.to_caller(Dn, kind), _arrays.to_caller(xn, kind)
+
+
+def _coef_size(template_size, size, stride=1, padding='VALID'):
+    """Number of coefficients per template for a signal of ``size`` samples."""
+    if padding == 'VALID':
+        pad = size - template_size
+    else:  # 'SAME'
+        pad = size - 1
+    return int(np.floor((template_size + 2 * pad - size) / stride + 1))
+
+
+def _pad_code(padding):
+    return 0 if padding == 'VALID' else 1
+
+
+def _call(t, name, *args):
+    """dcp_tm_<name>_<dtype of t>.  Tensor arguments are passed as device pointers; every floating or complex
+    one must have t's dtype and every one must live on t's device (the kernel reads them as t's dtype), which
+    is checked here rather than trusted."""
+    fn_name = 'dcp_tm_%s_%s' % (name, _arrays.suffix(t))
+    conv = []
+    for a in args:
+        if _arrays.is_torch(a):
+            if (a.is_floating_point() or a.is_complex()) and a.dtype != t.dtype:
+                raise DtypeMismatchError('%s: an argument is %s, the problem is %s' % (fn_name, a.dtype, t.dtype))
+            if a.device != t.device:
+                raise ValueError('%s: arguments on %s and %s' % (fn_name, a.device, t.device))
+            if not a.is_contiguous():
+                raise ValueError('%s: arguments must be contiguous' % fn_name)
+            a = _arrays.ptr(a)
+        conv.append(a)
+    lib, h = _arrays.lib_handle(t)
+    _hip.check(h, getattr(lib, fn_name)(h, *conv), fn_name)
+
+
+def _same_device(*tensors):
+    devs = set(t.device for t in tensors if t is not None)
+    if len(devs) > 1:
+        raise ValueError('all arrays must live on one device, given %s' % sorted(str(d) for d in devs))
+
+
+def _temp2mat(D, size, stride, padding, xp=None):
+    """The im2col operator of the templates, [T, C, size] (A[(t, c), n] = D[t, n - stride c + Q])."""
+    import torch
+    kind = get_array_module(D)
+    Dd = _arrays.to_device(D)
+    T, S = Dd.shape
+    C = _coef_size(S, size, stride, padding)
+    out = torch.empty((T, C, size), dtype=Dd.dtype, device=Dd.device)
+    _call(Dd, 'temp2mat', Dd, T, S, size, stride, _pad_code(padding), out)
+    return _arrays.to_caller(out, kind)
+
+
+def _coef2mat(x_orig, size, template_size, stride, padding, xp=None):
+    """The im2col matrix of the coefficients: [T, S, size] for x [T, C], [B, T, S, size] for x [B, T, C]."""
+    import torch
+    kind = get_array_module(x_orig)
+    xd = _arrays.to_device(x_orig)
+    x3 = xd.unsqueeze(0) if xd.dim() == 2 else xd
+    B, T, C = x3.shape
+    if C != _coef_size(template_size, size, stride, padding):
+        raise ValueError('x has %d coefficients per template, the geometry needs %d'
+                         % (C, _coef_size(template_size, size, stride, padding)))
+    out = torch.empty((B, T, template_size, size), dtype=xd.dtype, device=xd.device)
+    _call(x3, 'coef2mat', x3, B, T, template_size, size, stride, _pad_code(padding),
+          out)
+    if xd.dim() == 2:
+        out = out.squeeze(0)
+    return _arrays.to_caller(out, kind)
+
+
+def predict(x, D, size, stride=1, padding='SAME'):
+    """The signal x * D: x [..., T, C], D [T, S] -> [..., size] (mixed dtypes compute in the promoted one)."""
+    import torch
+    kind = get_array_module(x, D)
+    xd = _arrays.to_device(x)
+    Dd = _arrays.to_device(D, xd.device.index)
+    _same_device(xd, Dd)
+    # mixed dtypes compute in the promoted one, as the reference's tensordot does
+    dt = torch.promote_types(xd.dtype, Dd.dtype)
+    xd, Dd = xd.to(dt).contiguous(), Dd.to(dt).contiguous()
+    T, S = Dd.shape
+    C = _coef_size(S, size, stride, padding)
+    if tuple(xd.shape[-2:]) != (T, C):
+        raise ValueError('shape-mismatch for sum: x%s with templates [%d, %d] over %d samples'
+                         % (tuple(xd.shape), T, S, size))
+    lead = tuple(xd.shape[:-2])
+    x3 = xd.reshape((-1, T, C))
+    B = x3.shape[0]
+    out = torch.empty((B, size), dtype=xd.dtype, device=xd.device)
+    _call(x3, 'predict', x3, Dd, B, T, S, size, stride, _pad_code(padding),
+          out)
+    return _arrays.to_caller(out.reshape(lead + (size,)), kind)
+
+
+def _lasso(y, D, x, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol):
+    """solve_fastpath of lasso.py on the template operator; x [B, T, C] is updated in place."""
+    base = lasso_method[:-4] if lasso_method.endswith('_pos') else lasso_method
+    positive = lasso_method.endswith('_pos')
+    B, N = y.shape
+    T, S = D.shape
+    if base in _STRUCTURED:
+        it = ctypes.c_int(0)
+        _call(y, 'lasso', y, D, x, B, T, S, N, stride,
+              _pad_code(padding), float(alpha), float(lasso_tol), int(lasso_iter),
+              lasso._METHOD_CODE[base], 1 if positive else 0, ctypes.byref(it))
+        return it.value
+    if base in _DENSE:
+        A = _temp2mat(D, N, stride, padding).reshape(-1, N)
+        it, xn = lasso.solve_fastpath(y, A, alpha, x.reshape(B, -1), lasso_tol, lasso_iter,
+                                      lasso_method, None)
+        x.copy_(xn.reshape(x.shape))
+        return it
+    raise NotImplementedError('Method ' + base + ' is not yet implemented.')
+
+
+def _dstep(y, x, D, XXt, yX, stride, padding, acc_it):
+    """Statistics of (y, x) into XXt / yX (written, or added / acc_it) and the update of D in place;
+    returns max|D - D_new|."""
+    B, N = y.shape
+    T, S = D.shape
+    out = ctypes.c_double(0.0)
+    _call(y, 'dstep', y, x, D, XXt, yX,
+          B, T, S, N, stride, _pad_code(padding), int(acc_it), ctypes.byref(out))
+    return out.value
+
+
+def _device_args(y, D, x):
+    assertion.assert_dtypes(y=y, D=D, x=x)
+    kind = 'torch' if _arrays.is_torch(y) else 'numpy'
+    yd = _arrays.to_device(y)
+    dev = yd.device.index
+    Dd = _arrays.to_device(D, dev).contiguous()
+    xd = _arrays.to_device(x, dev, copy=True).contiguous()
+    _same_device(yd, Dd, xd)
+    return kind, yd.contiguous(), Dd, xd
+
+
+def _draw_windows(rng, B, N, w, m, C, cw):
+    """The rows and starts of one minibatch (minibatch_index((B, N - w), m, rng)).  A window's coefficients
+    are x[b, :, start:start + cw] with the SAMPLE start: with stride > 1 (or a padding that makes C < N) such a
+    slice can run past the C coefficients of the signal; the reference then fails inside np.stack with a
+    ValueError, and so does this (checked before anything is gathered)."""
+    rows, starts = minibatch_index((B, N - w), m, rng)
+    if cw <= 0 or np.any(np.asarray(starts) + cw > C):
+        raise ValueError('a window of %d samples takes %d coefficients from its start; the signal has only %d '
+                         'coefficients (stride > 1 minibatch windows can run past them)' % (w, cw, C))
+    return rows, starts
+
+
+def solve_batch(y, D, alpha, x, stride, padding, tol, maxiter,
+                lasso_method, lasso_iter, lasso_tol, xp):
+    """
+    Alternates, on the whole batch y [B, N]:
+      x <- the LASSO solution of y = x * D (lasso_iter iterations of lasso_method from the current x);
+      D <- l2(D + (yX - XXt D) / L), one gradient step on the templates.
+    Stops when max|dD| < tol.  D is normalised (strictly) once at entry.
+    """
+    import torch
+    kind, y, D, x = _device_args(y, D, x)
+    D = normalize.l2_strict(D, axis=-1)
+    T, S = D.shape
+    XXt = torch.empty((T * S, T * S), dtype=D.dtype, device=D.device)
+    yX = torch.empty((T * S,), dtype=D.dtype, device=D.device)
+    for it in range(1, maxiter):
+        Dprev = D.clone()
+        try:
+            _lasso(y, D, x, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
+            diff = _dstep(y, x, D, XXt, yX, stride, padding, 0)
+            if diff < tol:
+                return it, _arrays.to_caller(D, kind), _arrays.to_caller(x, kind)
+        except KeyboardInterrupt:
+            return it, _arrays.to_caller(Dprev, kind), _arrays.to_caller(x, kind)
+    return maxiter, _arrays.to_caller(D, kind), _arrays.to_caller(x, kind)
+
+
+class Minibatcher(object):
+    def __init__(self, array, size_of_minibatch, xp=None):
+        """
+        Windows of a [batch, n_sequence] or [batch, channels, n_sequence] array: ``self[index]`` for
+        index = (rows, starts) stacks array[row, ..., start:start + size_of_minibatch];
+        ``self[index] = values`` writes them back one after the other (the last window wins).
+        """
+        self.array = array
+        self.size_of_minibatch = size_of_minibatch
+        self.xp = xp
+
+    def _stack(self, parts):
+        if _arrays.is_torch(self.array):
+            import torch
+            return torch.stack(parts, 0)
+        return np.stack(parts, axis=0)
+
+    def __getitem__(self, index):
+        w = self.size_of_minibatch
+        if len(self.array.shape) == 2:
+            return self._stack([self.array[i0, i1:i1 + w] for i0, i1 in zip(*index)])
+        if len(self.array.shape) == 3:
+            return self._stack([self.array[i0, :, i1:i1 + w] for i0, i1 in zip(*index)])
+
+    def __setitem__(self, index, values):
+        w = self.size_of_minibatch
+        if len(self.array.shape) == 2:
+            for (i0, i1), val in zip(index, values):
+                self.array[i0, i1:i1 + w] = val
+        if len(self.array.shape) == 3:
+            for (i0, i1), val in zip(zip(*index), values):
+                self.array[i0, :, i1:i1 + w] = val
+
+    @property
+    def shape(self):
+        return self.array.shape
+
+    @property
+    def dtype(self):
+        return self.array.dtype
+
+
+def solve_minibatch(y, D, alpha, x, stride, padding, tol,
+                    minibatch, size_of_minibatch, maxiter,
+                    lasso_method, lasso_iter, lasso_tol, rng, xp):
+    """
+    As ``solve_batch`` on ``minibatch`` windows of ``size_of_minibatch`` samples per iteration
+    (rows and starts drawn by minibatch_index((B, N - size_of_minibatch), minibatch, rng)); each
+    window's coefficients are the slice x[b, :, start:start + _coef_size(S, size_of_minibatch)] and
+    are written back in draw order (so with stride > 1 a window can run past the coefficients: ValueError,
+    as in the reference, see _draw_windows).  The statistics are accumulated as XXt_sum += XXt / it,
+    yX_sum += yX / it (it = 1, 2, ...).  Returns the full x.
+    """
+    import torch
+    kind, y, D, x = _device_args(y, D, x)
+    D = normalize.l2_strict(D, axis=-1)
+    B, N = y.shape
+    T, S = D.shape
+    C = x.shape[-1]
+    w = int(size_of_minibatch)
+    cw = _coef_size(S, w, stride=stride, padding=padding)
+    m = int(minibatch)
+    yX_sum = torch.zeros((T * S,), dtype=D.dtype, device=D.device)
+    XXt_sum = torch.zeros((T * S, T * S), dtype=D.dtype, device=D.device)
+    yw = torch.empty((m, w), dtype=y.dtype, device=y.device)
+    xw = torch.empty((m, T, cw), dtype=y.dtype, device=y.device)
+    for it in range(1, maxiter):
+        Dprev = D.clone()
+        try:
+            rows, starts = _draw_windows(rng, B, N, w, m, C, cw)
+            ib = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(y.device)
+            inn = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int64)).to(y.device)
+            _call(y, 'gather_windows', y, x, ib, inn, m,
+                  B, T, S, N, w, stride, _pad_code(padding), yw, xw)
+            _lasso(yw, D, xw, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
+            _call(y, 'scatter_windows', xw, x, ib, inn, m,
+                  B, T, S, N, w, stride, _pad_code(padding))
+            diff = _dstep(yw, xw, D, XXt_sum, yX_sum, stride, padding, it)
+            if diff < tol:
+                return it, _arrays.to_caller(D, kind), _arrays.to_caller(x, kind)
+        except KeyboardInterrupt:
+            return it, _arrays.to_caller(Dprev, kind), _arrays.to_caller(x, kind)
+    return maxiter, _arrays.to_caller(D, kind), _arrays.to_caller(x, kind)

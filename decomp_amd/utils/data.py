@@ -17,6 +17,15 @@ import numpy as np
 from .. import _arrays, _hip
 
 
+def minibatch_index(shape, minibatch, rng):
+    """Random minibatch indices (data.py:11-15): one array of ``minibatch`` draws
+    rng.randint(0, s) per axis length s of ``shape``, axes in order; with minibatch None and a 1-D
+    shape, the whole axis (a tuple of slices)."""
+    if minibatch is None and len(shape) == 1:
+        return tuple(slice(None, None, None) for _ in shape)
+    return tuple(rng.randint(0, s, minibatch) for s in shape)
+
+
 def _gather_rows(t, index_dev):
     """t[index] for a [N, ...] device array (rows gathered by the HIP kernel)."""
     import torch

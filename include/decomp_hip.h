@@ -515,6 +515,51 @@ int dcp_dict_mask_step_c128(dcp_handle* h, const void* Y, const double* mask, vo
                             double alpha, int lasso_method, int lasso_iter, double lasso_tol,
                             double* maxdiff, int* lasso_it);
 
+/* ---- template matching (decomp/template_matching.py) ------------------------------------- */
+/* 1-D convolutional templates D [T, S] over signals Y [B, N]; coefficients X [B, T, C] with
+ * C = floor((S + 2 pad - N) / stride) + 1, pad = N - 1 (padding = 1, 'SAME') or N - S (padding = 0,
+ * 'VALID'); 0 < S <= N.  Device pointers in the problem dtype (complex: interleaved pairs).  The
+ * im2col operator A [T C, N] (A[(t, c), n] = D[t, n - stride c + Q], Q = stride (C - 1) - pad) is never
+ * formed except by dcp_tm_temp2mat_*.  Enqueued on the handle's stream; lasso and dstep synchronise it.
+ *   temp2mat:  out [T, C, N] = _temp2mat(D)           coef2mat: out [B, T, S, N] = _coef2mat(X)
+ *   predict:   out [B, N] = X . A
+ *   lasso:     solve_fastpath (lasso.py:97-189) of Y on A for method DCP_LASSO_ISTA / _ACC_ISTA / _FISTA
+ *              (+ positive, real dtypes), X in: initial estimate, out: solution; *it_out as dcp_lasso_*.
+ *   dstep:     the statistics XXt [T S, T S], yX [T S] of (Y, X) (template_matching.py:177-182),
+ *              written (acc_it == 0) or added as stat / acc_it to XXt / yX (the running sums, :238-239),
+ *              then D <- l2(D + (yX - XXt D) / (Gershgorin(XXt) + 1e-15)) in place; *maxdiff = max|dD|.
+ *   gather_windows:  Yw [m, w] = Y[idx_b[j], idx_n[j] : + w], Xw [m, T, cw] = X[idx_b[j], :, idx_n[j] : + cw]
+ *              (cw = coefficients of a w-sample window; the caller keeps idx_n[j] + cw <= C, idx_n[j] + w <= N)
+ *   scatter_windows: X[idx_b[j], :, idx_n[j] : + cw] = Xw[j] in order j = 0 .. m - 1 (the last window wins). */
+int dcp_tm_temp2mat_f32(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_temp2mat_f64(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_temp2mat_c64(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_temp2mat_c128(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_coef2mat_f32(dcp_handle* h, const void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_coef2mat_f64(dcp_handle* h, const void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_coef2mat_c64(dcp_handle* h, const void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_coef2mat_c128(dcp_handle* h, const void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_predict_f32(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_predict_f64(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_predict_c64(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_predict_c128(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_lasso_f32(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol, int maxiter, int method, int positive, int* it_out);
+int dcp_tm_lasso_f64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol, int maxiter, int method, int positive, int* it_out);
+int dcp_tm_lasso_c64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol, int maxiter, int method, int positive, int* it_out);
+int dcp_tm_lasso_c128(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol, int maxiter, int method, int positive, int* it_out);
+int dcp_tm_dstep_f32(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, double* maxdiff);
+int dcp_tm_dstep_f64(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, double* maxdiff);
+int dcp_tm_dstep_c64(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, double* maxdiff);
+int dcp_tm_dstep_c128(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, double* maxdiff);
+int dcp_tm_gather_windows_f32(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
+int dcp_tm_gather_windows_f64(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
+int dcp_tm_gather_windows_c64(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
+int dcp_tm_gather_windows_c128(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
+int dcp_tm_scatter_windows_f32(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding);
+int dcp_tm_scatter_windows_f64(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding);
+int dcp_tm_scatter_windows_c64(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding);
+int dcp_tm_scatter_windows_c128(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding);
+
 #ifdef __cplusplus
 }
 #endif
