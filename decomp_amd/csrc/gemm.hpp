@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "gemm_generic.hpp"
+#include "gemm_mfma_bf16x6.hpp"
 #include "gemm_mfma_f32.hpp"
 #include "gemm_mfma_f64.hpp"
 #include "scalar.hpp"
@@ -581,6 +582,50 @@ inline hipError_t gemm(hipStream_t stream, const GemmArgs<T>& a, const Epi& epi)
             return launch_gemm_generic<T, Epi>(stream, p, a.conjA, a.conjB, epi);
         else
             return launch_gemm_generic<T, Epi>(stream, p, false, false, epi);
+    }
+}
+
+// float32 products on the split-bf16 core (gemm_mfma_bf16x6.hpp): NT (Y.D^T) and TN (x^T [Y | x]) on the
+// tile the fp32 front end would pick (256 x 256 or 128 x 128), fast path only.  x6_tier() is -1 when the
+// problem has no bf16x6 form; gemm_bf16x6() then returns hipErrorInvalidValue (callers check x6_tier first).
+enum { X6_NONE = -1, X6_LARGE = 0, X6_HUGE = 1 };
+
+template <int FORM>
+inline GemmProblem x6_problem(const GemmArgs<float>& a) {
+    GemmProblem p;
+    p.A = a.A; p.lda = a.lda; p.B = a.B; p.ldb = a.ldb;
+    p.B2 = a.B2; p.ldb2 = a.ldb2; p.n_b1 = a.n_b1;
+    p.A2 = a.A2; p.lda2 = a.lda2; p.m_a1 = a.m_a1;
+    p.M = a.M; p.N = a.N; p.K = a.K;
+    p.ksplits = a.ksplits; p.klen = a.klen;
+    p.tiles_m = p.tiles_n = 0;
+    p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
+    return p;
+}
+
+template <int FORM>
+inline int x6_tier(const GemmArgs<float>& a) {
+    if (FORM == FORM_NN) return X6_NONE;
+    const int tier = pick_tier<FORM>(a.M, a.N, a.K, a.tile, a.split_planned, true);
+    const GemmProblem p = x6_problem<FORM>(a);
+    if (FORM == FORM_NT && tier == TIER_HUGE && x6_eligible<X6Huge>(p)) return X6_HUGE;
+    if ((tier == TIER_LARGE || (FORM == FORM_NT && (tier == TIER_MID || tier == TIER_HUGE))) &&
+        x6_eligible<X6Large>(p))
+        return X6_LARGE;
+    return X6_NONE;
+}
+
+template <int FORM, class Epi>
+inline hipError_t gemm_bf16x6(hipStream_t stream, const GemmArgs<float>& a, const Epi& epi) {
+    constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
+    constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
+    if constexpr (FORM == FORM_NN) {
+        return hipErrorInvalidValue;
+    } else {
+        const int t = x6_tier<FORM>(a);
+        if (t == X6_HUGE) return launch_gemm_bf16x6<X6Huge, AL, BL, Epi>(stream, x6_problem<FORM>(a), epi);
+        if (t == X6_LARGE) return launch_gemm_bf16x6<X6Large, AL, BL, Epi>(stream, x6_problem<FORM>(a), epi);
+        return hipErrorInvalidValue;
     }
 }
 

@@ -1,0 +1,299 @@
+// Split-bf16 ("bf16x6") GEMM core for float32 operands on gfx950 (MI355X).
+//
+//   C(m, n) = sum_k A(m, k) * B(k, n)        (float32 in, float32 accumulate)
+//
+// The fp32 MFMA (v_mfma_f32_32x32x2_f32) runs at 1/16 of the bf16 MFMA rate and gfx950 has no xf32.
+// This core splits every fp32 operand, with round-to-nearest, into three bf16 planes
+//     a = h + m + l + r,   h = bf16(a),  m = bf16(a - h),  l = bf16(a - h - m)
+// (|m| <= 2^-9 |a|, |l| <= 2^-18 |a|, |r| <= 2^-27 |a|; bf16 has the exponent range of fp32, so no
+// scaling) and accumulates the six products  lh + hl + mm + mh + hm + hh  per 16-deep K block with
+// v_mfma_f32_32x32x16_bf16 into the fp32 accumulator.  A bf16 x bf16 product is exact in fp32; the
+// dropped terms (ml, lm, ll and the r parts) sum to about 2^-26 sum|a||b|, under the 2^-24 unit roundoff
+// of the fp32 accumulation itself, so the error has the norm-wise form and size of the fp32 core's.
+// Six bf16 MFMAs (6 x 32 cycles) do the work of sixteen fp32 ones (16 x 64 cycles).
+//
+// Same problem description (GemmProblem), tile map (xcd_remap, mt_fast, two-segment B, split-K ranges)
+// and epilogue functors as gemm_mfma_f32.hpp; only the aligned fast path (whole tiles, 16-deep K blocks,
+// 16-byte aligned K-major operands) exists here -- x6_eligible() says when, and the callers keep the fp32
+// core otherwise.
+//
+// Staging: fp32 panels go global -> registers (the next K block's loads are issued before this block's
+// MFMAs), are split into the three planes in registers (v_cvt_pk_bf16_f32 and an fp32 residual) and
+// written to the other LDS buffer; one barrier per K block.  Global -> LDS DMA cannot transform data.
+//   KMAJOR panel (reduction index contiguous): one 16-byte load = 4 k of one row.
+//   XMAJOR panel (row index contiguous: x^T, [Y | x] of the reduction over samples): four 4-byte loads =
+//     4 k of one row, consecutive lanes on consecutive rows (each load instruction reads 256 contiguous
+//     bytes); the transpose happens in the registers, so both forms write the same LDS image.
+// LDS image of one plane: [rows][16 k] bf16, 32 bytes per row, two 16-byte chunks (k 0..7, 8..15);
+// chunk q of row r sits at chunk q ^ ((r >> 3) & 1).  A lane (l31, h) of the 32x32x16 MFMA reads
+// chunk h of its row with one ds_read_b128; the four ds_read_b128 lane groups of MI355X_MICROARCH
+// then each hit 16 distinct 16-byte slots (conflict free).
+#pragma once
+#include "gemm_mfma_f32.hpp"
+
+namespace dcp {
+
+typedef __bf16 x6_bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 x6_bf16x8 __attribute__((ext_vector_type(8)));
+
+// 64-row wave tiles of 32x32 accumulator blocks, 16-deep K blocks
+template <int BM_, int BN_, int WM_, int WN_, int MINW_>
+struct X6Cfg {
+    static constexpr int BM = BM_, BN = BN_, BK = 16, WM = WM_, WN = WN_, MINW = MINW_;
+    static constexpr int NWAVES = (BM_ / WM_) * (BN_ / WN_);
+    static constexpr int NTHREADS = 64 * NWAVES;
+};
+typedef X6Cfg<256, 256, 64, 64, 1> X6Huge;    // 16 waves, 2 x 48 KiB of planes
+typedef X6Cfg<128, 128, 64, 64, 2> X6Large;   // 4 waves, 2 x 24 KiB of planes
+
+template <int ROWS>
+struct X6Panel {
+    static constexpr int PLANE_BYTES = ROWS * 32;
+    static constexpr int BYTES = 3 * PLANE_BYTES;
+};
+
+// byte offset of chunk q (8 k) of row r inside one plane
+__device__ __forceinline__ int x6_chunk(int r, int q) { return r * 32 + ((q ^ ((r >> 3) & 1)) << 4); }
+
+// the three planes of 4 fp32 values
+__device__ __forceinline__ void x6_split(f32x4 a, x6_bf16x4& h, x6_bf16x4& m, x6_bf16x4& l) {
+    h = __builtin_convertvector(a, x6_bf16x4);
+    const f32x4 r1 = a - __builtin_convertvector(h, f32x4);      // exact: a - round(a)
+    m = __builtin_convertvector(r1, x6_bf16x4);
+    const f32x4 r2 = r1 - __builtin_convertvector(m, f32x4);     // exact
+    l = __builtin_convertvector(r2, x6_bf16x4);
+}
+
+// G = groups of 4 k per thread per K block
+template <int LAY, int ROWS, int NT, int G>
+__device__ __forceinline__ void x6_gload(f32x4 (&r)[G], const float* __restrict__ p, long ld, int row0, int k0,
+                                         int tid) {
+    static_assert(G * NT * 4 == ROWS * 16, "panel must be a whole number of 4-k groups per thread");
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        const int idx = tid + i * NT;
+        if (LAY == KMAJOR) {
+            const int row = idx >> 2, kq = idx & 3;
+            r[i] = *reinterpret_cast<const f32x4*>(p + (long)(row0 + row) * ld + (k0 + 4 * kq));
+        } else {
+            const int row = idx % ROWS, kq = idx / ROWS;
+            const float* q = p + (long)(k0 + 4 * kq) * ld + (row0 + row);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[i][e] = q[(long)e * ld];
+        }
+    }
+}
+
+template <int LAY, int ROWS, int NT, int G>
+__device__ __forceinline__ void x6_lds_store(char* s, const f32x4 (&r)[G], int tid) {
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        const int idx = tid + i * NT;
+        int row, kq;
+        if (LAY == KMAJOR) { row = idx >> 2; kq = idx & 3; }
+        else { row = idx % ROWS; kq = idx / ROWS; }
+        const int off = x6_chunk(row, kq >> 1) + ((kq & 1) << 3);
+        x6_bf16x4 h, m, l;
+        x6_split(r[i], h, m, l);
+        *reinterpret_cast<x6_bf16x4*>(s + off) = h;
+        *reinterpret_cast<x6_bf16x4*>(s + X6Panel<ROWS>::PLANE_BYTES + off) = m;
+        *reinterpret_cast<x6_bf16x4*>(s + 2 * X6Panel<ROWS>::PLANE_BYTES + off) = l;
+    }
+}
+
+template <class Cfg, int ALAY, int BLAY, class Epi>
+__global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(GemmProblem p, Epi epi) {
+    constexpr int BM = Cfg::BM, BN = Cfg::BN, BK = Cfg::BK, WM = Cfg::WM, WN = Cfg::WN;
+    constexpr int TM = WM / 32, TN = WN / 32;
+    constexpr int WAVES_N = BN / WN;
+    constexpr int NT = Cfg::NTHREADS;
+    constexpr int GA = BM * BK / 4 / NT, GB = BN * BK / 4 / NT;
+    constexpr int PA = X6Panel<BM>::PLANE_BYTES, PB = X6Panel<BN>::PLANE_BYTES;
+    constexpr int BUF = X6Panel<BM>::BYTES + X6Panel<BN>::BYTES;   // one buffer: A planes, then B planes
+    static_assert(epi_mode<Epi>::value == 0 && !epi_rowbits<Epi>::value, "bf16x6 core: plain real epilogues");
+
+    extern __shared__ __attribute__((aligned(16))) char x6_smem[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    const int l31 = lane & 31, h = lane >> 5;
+
+    // ---- tile decode: as gemm_mfma_kernel (XCD aware, two-segment B, split-K) ----
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles = p.tiles_m * p.tiles_n;
+    const int split = lid / tiles;
+    const int t = lid - split * tiles;
+    int mt, nt;
+    if (p.mt_fast) {
+        mt = t % p.tiles_m;
+        nt = t / p.tiles_m;
+    } else {
+        nt = t % p.tiles_n;
+        mt = t / p.tiles_n;
+    }
+    const int m0 = mt * BM;
+    const int kbeg = split * p.klen;
+    const int kend = min(p.K, kbeg + p.klen);
+    const float* Bp = p.B;
+    long ldb = p.ldb;
+    int nB0 = nt * BN;
+    int n0 = nB0;
+    if (nt >= p.tiles_n1) {
+        Bp = p.B2;
+        ldb = p.ldb2;
+        nB0 = (nt - p.tiles_n1) * BN;
+        n0 = p.n_b1 + nB0;
+    }
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+
+    f32x4 ra[GA], rb[GB];
+    const int nkb = (kend - kbeg) / BK;   // whole K blocks (x6_eligible)
+    if (nkb > 0) {
+        x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, kbeg, tid);
+        x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, kbeg, tid);
+        x6_lds_store<ALAY, BM, NT>(x6_smem, ra, tid);
+        x6_lds_store<BLAY, BN, NT>(x6_smem + X6Panel<BM>::BYTES, rb, tid);
+    }
+    __syncthreads();
+
+    // fragment byte offsets inside a plane (the same for every K block and buffer)
+    int aoff[TM], boff[TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) aoff[i] = x6_chunk(wm * WM + i * 32 + l31, h);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) boff[j] = x6_chunk(wn * WN + j * 32 + l31, h);
+
+    for (int kb = 0; kb < nkb; ++kb) {
+        const int cur = kb & 1;
+        const char* sA = x6_smem + cur * BUF;
+        const char* sB = sA + X6Panel<BM>::BYTES;
+        const bool more = (kb + 1) < nkb;
+        if (more) {   // next block's global loads land during this block's MFMAs
+            const int k0 = kbeg + (kb + 1) * BK;
+            x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k0, tid);
+            x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k0, tid);
+        }
+        // B fragments of the block first, then the A fragments of one 32-row block at a time: at four waves
+        // per SIMD (128 VGPRs) all of them at once would spill
+        x6_bf16x8 fb[3][TN];
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) fb[pl][j] = *reinterpret_cast<const x6_bf16x8*>(sB + pl * PB + boff[j]);
+        // small terms first, hh last; plane index 0 = h, 1 = m, 2 = l
+        constexpr int TA[6] = {2, 0, 1, 1, 0, 0};
+        constexpr int TB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            x6_bf16x8 fa[3];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) fa[pl] = *reinterpret_cast<const x6_bf16x8*>(sA + pl * PA + aoff[i]);
+#pragma unroll
+            for (int tt = 0; tt < 6; ++tt)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[TA[tt]], fb[TB[tt]][j], acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (more) {
+            char* nxt = x6_smem + (cur ^ 1) * BUF;
+            x6_lds_store<ALAY, BM, NT>(nxt, ra, tid);
+            x6_lds_store<BLAY, BN, NT>(nxt + X6Panel<BM>::BYTES, rb, tid);
+        }
+        __syncthreads();
+    }
+
+    // ---- epilogue: the 32x32x16 bf16 MFMA has the C layout of the fp32 one:
+    //      col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----
+    if constexpr (epi_vec4<Epi>::value) {
+        // functors with a 16-byte form always use it here (x6_epi_ok): the per-element form of a loading
+        // epilogue (EpiMuNum) would be compiled beside it and spill at four waves per SIMD
+        const int tq = l31 & 3, col0 = (l31 & ~3);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 x;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x[e] = acc[i][j][4 * g + e];
+                    const f32x4 y = quad_transpose(x, tq);
+                    epi.vec4(m0 + wm * WM + i * 32 + 8 * g + 4 * h + tq, n0 + wn * WN + j * 32 + col0, y, split);
+                }
+    } else {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = n0 + wn * WN + j * 32 + l31;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    epi(row, col, acc[i][j][r], split);
+                }
+            }
+    }
+}
+
+// the epilogue functor's 16-byte form, when it has one, must be usable (aligned arrays, leading dims % 4 == 0)
+template <class Epi>
+inline bool x6_epi_ok(const Epi& epi) {
+    if constexpr (epi_vec4<Epi>::value) return epi.vec_ok();
+    else return true;
+}
+
+// Whole tiles, whole 16-deep K blocks in every split, 16-byte aligned operands with leading dims % 4 == 0
+// (the XMAJOR loads are 4-byte, but the same rule keeps one test for both forms), no stacked A.
+template <class Cfg>
+inline bool x6_eligible(const GemmProblem& p) {
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const int n1 = p.B2 != nullptr ? p.n_b1 : p.N;
+    bool ok = p.M > 0 && p.N > 0 && p.K > 0 && (p.M % Cfg::BM) == 0 && (n1 % Cfg::BN) == 0 &&
+              ((p.N - n1) % Cfg::BN) == 0 && (p.K % 16) == 0 && p.A2 == nullptr && (p.lda % 4) == 0 &&
+              (p.ldb % 4) == 0 && al16(p.A) && al16(p.B);
+    if (p.B2 != nullptr) ok = ok && (p.ldb2 % 4) == 0 && al16(p.B2);
+    if (p.ksplits > 1) ok = ok && (p.klen % 16) == 0 && p.klen > 0;
+    return ok;
+}
+
+// Host launch.  Returns hipErrorInvalidValue when the problem is not eligible (callers check first).
+template <class Cfg, int ALAY, int BLAY, class Epi>
+inline hipError_t launch_gemm_bf16x6(hipStream_t stream, GemmProblem p, const Epi& epi) {
+    if (!x6_eligible<Cfg>(p) || !x6_epi_ok(epi)) return hipErrorInvalidValue;
+    if (p.B2 == nullptr) p.n_b1 = p.N;
+    p.m_a1 = p.M;
+    p.tiles_m1 = p.tiles_m = p.M / Cfg::BM;
+    p.tiles_n1 = p.n_b1 / Cfg::BN;
+    p.tiles_n = p.tiles_n1 + (p.N - p.n_b1) / Cfg::BN;
+    if (p.ksplits < 1) p.ksplits = 1;
+    if (p.ksplits == 1) p.klen = p.K;
+    p.vec_epi = epi_vec4<Epi>::value ? 1 : 0;
+    p.al_mask = 0;
+    const int grid = p.tiles_m * p.tiles_n * p.ksplits;
+    if (grid <= 0) return hipSuccess;
+    constexpr int lds_bytes = 2 * (X6Panel<Cfg::BM>::BYTES + X6Panel<Cfg::BN>::BYTES);
+    const void* fn = reinterpret_cast<const void*>(&gemm_bf16x6_kernel<Cfg, ALAY, BLAY, Epi>);
+    if constexpr (lds_bytes > 65536) {
+        static DynLdsRaised raised;   // per instantiation
+        std::atomic<bool>& done = raised.on_current_device();
+        if (!done) {
+            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+            if (e != hipSuccess) return e;
+            done = true;
+        }
+    }
+    hipLaunchKernelGGL((gemm_bf16x6_kernel<Cfg, ALAY, BLAY, Epi>), dim3(grid), dim3(Cfg::NTHREADS), lds_bytes,
+                       stream, p, epi);
+    return hipGetLastError();
+}
+
+}  // namespace dcp

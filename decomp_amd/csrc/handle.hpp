@@ -65,6 +65,9 @@ struct dcp_handle {
     std::vector<hipEvent_t> prof_pool;
     double prof_ms[DCP_PROF_NLABELS] = {0};
     long long prof_cnt[DCP_PROF_NLABELS] = {0};
+    // float32 products of the NMF Gram path (dcp_set_f32_product_mode): 0 = split-bf16 core (bf16x6,
+    // gemm_mfma_bf16x6.hpp), 1 = the exact fp32 MFMA core
+    int f32_product_mode = 0;
 };
 
 namespace dcp {

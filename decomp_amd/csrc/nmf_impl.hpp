@@ -167,6 +167,18 @@ inline int column_sums(dcp_handle* h, const T* a, long ld, long rows, long cols,
     return DCP_OK;
 }
 
+// The two large float32 products of the Gram path (Y.D^T with its quotient or split-F slabs, x^T [Y | x]) run
+// on the split-bf16 core unless the handle asks for the exact fp32 products (dcp_set_f32_product_mode) or the
+// problem has no bf16x6 form (ragged or unaligned tiles: x6_tier); float64 always takes gemm().
+template <int FORM, class T, class Epi>
+inline hipError_t nmf_product(dcp_handle* h, hipStream_t st, const GemmArgs<T>& a, const Epi& epi, bool split_ok) {
+    if constexpr (std::is_same<T, float>::value) {
+        if (split_ok && h->f32_product_mode == 0 && x6_tier<FORM>(a) != X6_NONE && x6_epi_ok(epi))
+            return gemm_bf16x6<FORM>(st, a, epi);
+    }
+    return gemm<FORM>(st, a, epi);
+}
+
 // ---- x update + local statistics ------------------------------------------------------
 // Ypre: Y already multiplied by the mask (or Y itself when there is no mask).
 template <class T>
@@ -284,13 +296,13 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
         if (psplits <= 1) {
             // enough row tiles to fill the chip: quotient fused into the GEMM epilogue
             pg.ksplits = 1;
-            DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, pg, EpiMuNum<T>{Xin, K, xden, ld_xden, Xout, K})));
+            DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiMuNum<T>{Xin, K, xden, ld_xden, Xout, K}, gram)));
         } else {
             // few rows per GPU (a shard of a multi-GPU run): split the F reduction so that all
             // CUs work, then sum the slabs in order inside the quotient kernel
             if ((size_t)pg.ksplits * N * K > w.slab_count)
                 return fail(h, DCP_ERR_INTERNAL, "nmf x-update slab plan mismatch");
-            DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, pg, EpiSlab<T>{w.slabs, K, (long)N * K})));
+            DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiSlab<T>{w.slabs, K, (long)N * K}, gram)));
             if (split_gram) {
                 GemmArgs<T> q;   // x_new = x * max(sum slabs, 0) / max(x G, eps)
                 q.A = Xin; q.lda = K; q.B = w.G; q.ldb = K; q.M = N; q.N = K; q.K = K;
@@ -330,7 +342,7 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
         return fail(h, DCP_ERR_INTERNAL, "nmf slab plan mismatch");
     {
         ProfScope ps(h, DCP_PROF_STATS);
-        DCP_LAUNCH_OK(h, (gemm<FORM_TN>(st, sa, EpiSlab<T>{w.slabs, Wg, (long)K * Wg})));
+        DCP_LAUNCH_OK(h, (nmf_product<FORM_TN>(h, st, sa, EpiSlab<T>{w.slabs, Wg, (long)K * Wg}, gram)));
     }
     ProfScope ps(h, DCP_PROF_STATS_SUM);
     if (Wg == W) {

@@ -561,6 +561,56 @@ int dcp_gemm_f32(dcp_handle* h, int form, const float* A, const float* B, float*
                  int64_t N, int64_t K, int ksplits, int tile) {
     return gemm_api<float>(h, form, A, B, C, M, N, K, ksplits, tile);
 }
+int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B, float* C, int64_t M, int64_t N,
+                        int64_t K, int ksplits) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!A || !B || !C) return fail(h, DCP_ERR_INVALID, "null array pointer");
+    if (M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
+        return fail(h, DCP_ERR_INVALID, "bad sizes");
+    if (form != FORM_NT && form != FORM_TN) return fail(h, DCP_ERR_INVALID, "bf16x6: form must be 0 (NT) or 2 (TN)");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    GemmArgs<float> a;
+    a.A = A; a.B = B; a.M = (int)M; a.N = (int)N; a.K = (int)K;
+    a.lda = (form == FORM_TN) ? M : K;
+    a.ldb = (form == FORM_NT) ? K : N;
+    float* slabs = nullptr;
+    if (ksplits > 1) {   // the same split plan as dcp_gemm_f32
+        const long kblocks = (K + 15) / 16;
+        const long s = ksplits > kblocks ? kblocks : ksplits;
+        a.klen = (int)(((kblocks + s - 1) / s) * 16);
+        a.ksplits = (int)((K + a.klen - 1) / a.klen);
+        a.split_planned = true;
+        WsPlan plan;
+        plan.add<float>((size_t)a.ksplits * M * N);
+        DCP_TRY(ws_reserve(h, plan.total));
+        ws_reset(h);
+        slabs = ws_alloc<float>(h, (size_t)a.ksplits * M * N);
+        if (!slabs) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+    }
+    const bool ok = (form == FORM_NT) ? x6_tier<FORM_NT>(a) != X6_NONE : x6_tier<FORM_TN>(a) != X6_NONE;
+    if (!ok) return fail(h, DCP_ERR_INVALID, "bf16x6: no split-bf16 kernel for this shape (tiles, alignment)");
+    hipError_t e;
+    if (slabs) {
+        EpiSlab<float> epi{slabs, (long)N, (long)M * N};
+        e = (form == FORM_NT) ? gemm_bf16x6<FORM_NT>(h->stream, a, epi) : gemm_bf16x6<FORM_TN>(h->stream, a, epi);
+        if (e != hipSuccess) return fail(h, DCP_ERR_HIP, hipGetErrorString(e));
+        hipLaunchKernelGGL((reduce_slabs_kernel<float>), dim3(grid_for(M * N)), dim3(256), 0, h->stream, slabs,
+                           (long)(M * N), a.ksplits, (long)(M * N), C);
+        DCP_HIP_OK(h, hipGetLastError());
+    } else {
+        EpiStore<float> epi{C, (long)N};
+        e = (form == FORM_NT) ? gemm_bf16x6<FORM_NT>(h->stream, a, epi) : gemm_bf16x6<FORM_TN>(h->stream, a, epi);
+        if (e != hipSuccess) return fail(h, DCP_ERR_HIP, hipGetErrorString(e));
+    }
+    return DCP_OK;
+}
+int dcp_set_f32_product_mode(dcp_handle* h, int mode) {
+    if (!h) return DCP_ERR_INVALID;
+    const int prev = h->f32_product_mode;
+    if (mode > 1) return fail(h, DCP_ERR_INVALID, "f32 product mode must be 0 (bf16x6) or 1 (fp32)");
+    if (mode >= 0) h->f32_product_mode = mode;
+    return prev;
+}
 int dcp_gemm_f64(dcp_handle* h, int form, const double* A, const double* B, double* C, int64_t M,
                  int64_t N, int64_t K, int ksplits, int tile) {
     return gemm_api<double>(h, form, A, B, C, M, N, K, ksplits, tile);

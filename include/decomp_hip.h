@@ -170,6 +170,19 @@ int dcp_gemm_c64(dcp_handle* h, int form, const void* A, const void* B, void* C,
 int dcp_gemm_c128(dcp_handle* h, int form, const void* A, const void* B, void* C,
                   int64_t M, int64_t N, int64_t K, int ksplits, int tile);
 
+/* Test hook (not a reference interface): C[M,N] = op(A) . op(B) on the split-bf16 core ("bf16x6": each
+ * float32 operand split into three bf16 planes, six bf16 MFMA products per K block, fp32 accumulation; error of
+ * the fp32 core's size).  form: 0 = NT, 2 = TN, as dcp_gemm_f32; ksplits >= 1 as there.  Only whole 128 x 128
+ * (or 256 x 256) tiles, K % 16 == 0 and 16-byte aligned operands: other shapes return DCP_ERR_INVALID. */
+int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B, float* C,
+                        int64_t M, int64_t N, int64_t K, int ksplits);
+
+/* How the float32 NMF multiplicative-update step (l2 loss, no mask) forms its two large products, Y.D^T and
+ * x^T [Y | x], on this handle: mode 0 (default) = split-bf16 core (bf16x6, see dcp_gemm_bf16x6_f32), mode 1 =
+ * the exact fp32 MFMA core.  Every other product, dtype and loss always uses its usual core.  mode < 0 only
+ * queries.  Returns the previous mode, or a negative error code. */
+int dcp_set_f32_product_mode(dcp_handle* h, int mode);
+
 /* Test hook (not a reference interface): the reduction-over-samples products (form 2) run the "pair" LDS schedule
  * of the fp32 MFMA core unless DCP_TN_PLAIN is set in the environment (read once); on != 0 selects the plain
  * schedule, on == 0 the pair schedule, on < 0 only queries.  Returns the previous setting (1 = plain).  Process-wide;
