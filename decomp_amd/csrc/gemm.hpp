@@ -585,10 +585,14 @@ inline hipError_t gemm(hipStream_t stream, const GemmArgs<T>& a, const Epi& epi)
     }
 }
 
-// float32 products on the split-bf16 core (gemm_mfma_bf16x6.hpp): NT (Y.D^T) and TN (x^T [Y | x]) on the
-// tile the fp32 front end would pick (256 x 256 or 128 x 128), fast path only.  x6_tier() is -1 when the
-// problem has no bf16x6 form; gemm_bf16x6() then returns hipErrorInvalidValue (callers check x6_tier first).
+// float32 products on the split-bf16 core (gemm_mfma_bf16x6.hpp): NT (Y.D^T) and TN (x^T [Y | x]), fast path
+// only.  NT takes the tile the fp32 front end would pick (256 x 256 or 128 x 128).  TN takes 256 x 256 where the
+// fp32 front end picks 128 x 128, when the tiles are whole and every split is at least kX6HugeTnMinK deep (one
+// 16-wave workgroup per CU: plan its splits with plan_splits_x6_tn), 128 x 128 otherwise (ragged 256-tiles,
+// small shards).  x6_tier() is -1 when the problem has no bf16x6 form; gemm_bf16x6() then returns
+// hipErrorInvalidValue (callers check x6_tier first).
 enum { X6_NONE = -1, X6_LARGE = 0, X6_HUGE = 1 };
+constexpr int kX6HugeTnMinK = 1024;
 
 template <int FORM>
 inline GemmProblem x6_problem(const GemmArgs<float>& a) {
@@ -603,12 +607,48 @@ inline GemmProblem x6_problem(const GemmArgs<float>& a) {
     return p;
 }
 
+// TN on 256 x 256 by shape alone (no pointers): whole tiles in both B segments (columns < n1, >= n1) and deep
+// enough splits
+template <class T>
+inline bool x6_huge_tn_shape(const GemmArgs<T>& a, int n1, int klen) {
+    return std::is_same<T, float>::value && a.A2 == nullptr && a.M > 0 && a.N > 0 && a.K > 0 &&
+           a.M % X6Huge::BM == 0 && n1 % X6Huge::BN == 0 && (a.N - n1) % X6Huge::BN == 0 && klen >= kX6HugeTnMinK &&
+           pick_tier<FORM_TN>(a.M, a.N, a.K, a.tile, true, true) == TIER_LARGE;
+}
+
+// Split-K plan of a TN product that will run on the 256 x 256 bf16x6 tile: one round of 16-wave workgroups
+// (one per CU, 256 CUs), every split at least 512 deep.  Returns false (and leaves `a` alone) when the product
+// would not take that tile; the caller then plans for the fp32 front end (plan_splits).  n1: width of the
+// first B segment (a.N without a second one).
+template <class T>
+inline bool plan_splits_x6_tn(GemmArgs<T>& a, int n1, int max_splits) {
+    if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.M % X6Huge::BM || n1 % X6Huge::BN || (a.N - n1) % X6Huge::BN)
+        return false;
+    const long tiles = (long)(a.M / X6Huge::BM) * (n1 / X6Huge::BN + (a.N - n1) / X6Huge::BN);
+    const long kblocks = ceil_div(a.K, 16);
+    long smax = kblocks / 32;
+    if (smax < 1) smax = 1;
+    if (smax > max_splits) smax = max_splits;
+    long s = 256 / tiles;
+    if (s > smax) s = smax;
+    if (s < 1) s = 1;
+    const int klen = (int)(((kblocks + s - 1) / s) * 16);
+    if (!x6_huge_tn_shape(a, n1, klen)) return false;
+    a.split_planned = true;
+    a.klen = klen;
+    a.ksplits = ceil_div(a.K, klen);
+    return true;
+}
+
 template <int FORM>
 inline int x6_tier(const GemmArgs<float>& a) {
     if (FORM == FORM_NN) return X6_NONE;
     const int tier = pick_tier<FORM>(a.M, a.N, a.K, a.tile, a.split_planned, true);
     const GemmProblem p = x6_problem<FORM>(a);
     if (FORM == FORM_NT && tier == TIER_HUGE && x6_eligible<X6Huge>(p)) return X6_HUGE;
+    if (FORM == FORM_TN && tier == TIER_LARGE && x6_huge_tn_shape(a, a.B2 != nullptr ? a.n_b1 : a.N, a.ksplits > 1 ? a.klen : a.K) &&
+        x6_eligible<X6Huge>(p))
+        return X6_HUGE;
     if ((tier == TIER_LARGE || (FORM == FORM_NT && (tier == TIER_MID || tier == TIER_HUGE))) &&
         x6_eligible<X6Large>(p))
         return X6_LARGE;

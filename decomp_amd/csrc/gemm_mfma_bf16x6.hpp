@@ -21,13 +21,16 @@
 // MFMAs), are split into the three planes in registers (v_cvt_pk_bf16_f32 and an fp32 residual) and
 // written to the other LDS buffer; one barrier per K block.  Global -> LDS DMA cannot transform data.
 //   KMAJOR panel (reduction index contiguous): one 16-byte load = 4 k of one row.
-//   XMAJOR panel (row index contiguous: x^T, [Y | x] of the reduction over samples): four 4-byte loads =
-//     4 k of one row, consecutive lanes on consecutive rows (each load instruction reads 256 contiguous
-//     bytes); the transpose happens in the registers, so both forms write the same LDS image.
-// LDS image of one plane: [rows][16 k] bf16, 32 bytes per row, two 16-byte chunks (k 0..7, 8..15);
-// chunk q of row r sits at chunk q ^ ((r >> 3) & 1).  A lane (l31, h) of the 32x32x16 MFMA reads
-// chunk h of its row with one ds_read_b128; the four ds_read_b128 lane groups of MI355X_MICROARCH
-// then each hit 16 distinct 16-byte slots (conflict free).
+//     LDS image of one plane: [rows][16 k] bf16, 32 bytes per row, two 16-byte chunks (k 0..7, 8..15);
+//     chunk q of row r sits at chunk q ^ ((r >> 3) & 1).  A lane (l31, h) of the 32x32x16 MFMA reads
+//     chunk h of its row with one ds_read_b128; the four ds_read_b128 lane groups of MI355X_MICROARCH
+//     then each hit 16 distinct 16-byte slots (conflict free).
+//   XMAJOR panel (row index contiguous: x^T, [Y | x] of the reduction over samples): one 16-byte load =
+//     4 consecutive rows at one k (a wave reads 1 KiB of one k row).  LDS image of one plane: [16 k][rows]
+//     bf16 in 8-byte granules of 4 rows; granule g of k row k sits at g ^ (8 (k & 3)).  The split writes
+//     each plane's granule with one ds_write_b64; the fragment is read back transposed with two
+//     ds_read_b64_tr_b16 (k 8h..8h+3 and 8h+4..8h+7).  A 32-lane half of one such read takes 4 k rows
+//     x 8 granules; the XOR puts them on 32 distinct bank pairs (conflict free).
 #pragma once
 #include "gemm_mfma_f32.hpp"
 
@@ -64,11 +67,11 @@ __device__ __forceinline__ void x6_split(f32x4 a, x6_bf16x4& h, x6_bf16x4& m, x6
     l = __builtin_convertvector(r2, x6_bf16x4);
 }
 
-// G = groups of 4 k per thread per K block
+// G = groups of 4 values per thread per K block (KMAJOR: 4 k of one row; XMAJOR: 4 rows at one k)
 template <int LAY, int ROWS, int NT, int G>
 __device__ __forceinline__ void x6_gload(f32x4 (&r)[G], const float* __restrict__ p, long ld, int row0, int k0,
                                          int tid) {
-    static_assert(G * NT * 4 == ROWS * 16, "panel must be a whole number of 4-k groups per thread");
+    static_assert(G * NT * 4 == ROWS * 16, "panel must be a whole number of 4-value groups per thread");
 #pragma unroll
     for (int i = 0; i < G; ++i) {
         const int idx = tid + i * NT;
@@ -76,12 +79,17 @@ __device__ __forceinline__ void x6_gload(f32x4 (&r)[G], const float* __restrict_
             const int row = idx >> 2, kq = idx & 3;
             r[i] = *reinterpret_cast<const f32x4*>(p + (long)(row0 + row) * ld + (k0 + 4 * kq));
         } else {
-            const int row = idx % ROWS, kq = idx / ROWS;
-            const float* q = p + (long)(k0 + 4 * kq) * ld + (row0 + row);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) r[i][e] = q[(long)e * ld];
+            const int g = idx % (ROWS / 4), k = idx / (ROWS / 4);
+            r[i] = *reinterpret_cast<const f32x4*>(p + (long)(k0 + k) * ld + (row0 + 4 * g));
         }
     }
+}
+
+// XMAJOR image: byte offset of granule g (rows 4g .. 4g+3) of k row k inside one plane
+template <int ROWS>
+__device__ __forceinline__ int x6_granule(int k, int g) {
+    static_assert(ROWS >= 128, "the XOR swizzle needs 32 granules per k row");
+    return k * (ROWS * 2) + ((g ^ ((k & 3) << 3)) << 3);
 }
 
 template <int LAY, int ROWS, int NT, int G>
@@ -89,16 +97,42 @@ __device__ __forceinline__ void x6_lds_store(char* s, const f32x4 (&r)[G], int t
 #pragma unroll
     for (int i = 0; i < G; ++i) {
         const int idx = tid + i * NT;
-        int row, kq;
-        if (LAY == KMAJOR) { row = idx >> 2; kq = idx & 3; }
-        else { row = idx % ROWS; kq = idx / ROWS; }
-        const int off = x6_chunk(row, kq >> 1) + ((kq & 1) << 3);
+        int off;
+        if (LAY == KMAJOR) {
+            const int row = idx >> 2, kq = idx & 3;
+            off = x6_chunk(row, kq >> 1) + ((kq & 1) << 3);
+        } else {
+            off = x6_granule<ROWS>(idx / (ROWS / 4), idx % (ROWS / 4));
+        }
         x6_bf16x4 h, m, l;
         x6_split(r[i], h, m, l);
         *reinterpret_cast<x6_bf16x4*>(s + off) = h;
         *reinterpret_cast<x6_bf16x4*>(s + X6Panel<ROWS>::PLANE_BYTES + off) = m;
         *reinterpret_cast<x6_bf16x4*>(s + 2 * X6Panel<ROWS>::PLANE_BYTES + off) = l;
     }
+}
+
+// Byte offset, inside one plane, of this lane's part of the 32x32x16 operand fragment of rows r0 .. r0+31
+// (lane (l31, h) holds row l31, k 8h .. 8h+7).  KMAJOR: the ds_read_b128 address.  XMAJOR: the address of
+// the first ds_read_b64_tr_b16 -- lane 4q+p of each 16-lane group names k row 8h + q, granule of rows
+// r0 + 16 ((lane >> 4) & 1) + 4p .. +3, and receives its row's four k; the second read is 4 k rows on.
+template <int LAY, int ROWS>
+__device__ __forceinline__ int x6_frag_off(int r0, int lane) {
+    const int l31 = lane & 31, h = lane >> 5;
+    if (LAY == KMAJOR) return x6_chunk(r0 + l31, h);
+    const int q = (lane >> 2) & 3, pq = lane & 3, gh = (lane >> 4) & 1;
+    return x6_granule<ROWS>(8 * h + q, (r0 >> 2) + 4 * gh + pq);
+}
+
+template <int LAY, int ROWS>
+__device__ __forceinline__ x6_bf16x8 x6_frag(const char* plane, int off) {
+    if (LAY == KMAJOR) return *reinterpret_cast<const x6_bf16x8*>(plane + off);
+    typedef short s16x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    // (every lane takes part: the gather crosses lanes, so EXEC must be all ones here)
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(plane + off));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(plane + off + 4 * ROWS * 2));
+    return __builtin_bit_cast(x6_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
 template <class Cfg, int ALAY, int BLAY, class Epi>
@@ -167,9 +201,9 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
     // fragment byte offsets inside a plane (the same for every K block and buffer)
     int aoff[TM], boff[TN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) aoff[i] = x6_chunk(wm * WM + i * 32 + l31, h);
+    for (int i = 0; i < TM; ++i) aoff[i] = x6_frag_off<ALAY, BM>(wm * WM + i * 32, lane);
 #pragma unroll
-    for (int j = 0; j < TN; ++j) boff[j] = x6_chunk(wn * WN + j * 32 + l31, h);
+    for (int j = 0; j < TN; ++j) boff[j] = x6_frag_off<BLAY, BN>(wn * WN + j * 32, lane);
 
     for (int kb = 0; kb < nkb; ++kb) {
         const int cur = kb & 1;
@@ -187,7 +221,7 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) fb[pl][j] = *reinterpret_cast<const x6_bf16x8*>(sB + pl * PB + boff[j]);
+            for (int j = 0; j < TN; ++j) fb[pl][j] = x6_frag<BLAY, BN>(sB + pl * PB, boff[j]);
         // small terms first, hh last; plane index 0 = h, 1 = m, 2 = l
         constexpr int TA[6] = {2, 0, 1, 1, 0, 0};
         constexpr int TB[6] = {0, 2, 1, 0, 1, 0};
@@ -195,7 +229,7 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
         for (int i = 0; i < TM; ++i) {
             x6_bf16x8 fa[3];
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) fa[pl] = *reinterpret_cast<const x6_bf16x8*>(sA + pl * PA + aoff[i]);
+            for (int pl = 0; pl < 3; ++pl) fa[pl] = x6_frag<ALAY, BM>(sA + pl * PA, aoff[i]);
 #pragma unroll
             for (int tt = 0; tt < 6; ++tt)
 #pragma unroll
@@ -252,7 +286,7 @@ inline bool x6_epi_ok(const Epi& epi) {
 }
 
 // Whole tiles, whole 16-deep K blocks in every split, 16-byte aligned operands with leading dims % 4 == 0
-// (the XMAJOR loads are 4-byte, but the same rule keeps one test for both forms), no stacked A.
+// (both forms load 16 bytes: 4 k of one row or 4 rows at one k), no stacked A.
 template <class Cfg>
 inline bool x6_eligible(const GemmProblem& p) {
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };

@@ -80,6 +80,12 @@ inline size_t nmf_slab_elems(const NmfShape<T>& s) {
     a.M = (int)s.K; a.N = (int)W; a.K = (int)s.N;
     plan_splits<FORM_TN>(a, kSplitTarget, kMaxSplits);
     size_t stats_slabs = (size_t)a.ksplits * s.K * W;
+    if (s.lik == DCP_LIK_L2 && !s.masked) {   // the Gram path may plan for the 256 x 256 bf16x6 tile instead
+        GemmArgs<T> b;
+        b.M = (int)s.K; b.N = (int)W; b.K = (int)s.N;
+        if (plan_splits_x6_tn(b, (int)s.F, kMaxSplits) && (size_t)b.ksplits * s.K * W > stats_slabs)
+            stats_slabs = (size_t)b.ksplits * s.K * W;
+    }
     GemmArgs<T> g;
     g.M = (int)s.K; g.N = (int)s.K; g.K = (int)s.F;
     plan_splits<FORM_NT>(g, 512, kMaxSplits, 16);
@@ -337,7 +343,10 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
         }
     }
     const int Wg = sa.N;  // width produced by the GEMM (KL no-mask: F, the rest is filled below)
-    plan_splits<FORM_TN>(sa, kSplitTarget, kMaxSplits);
+    // the bf16x6 path takes the 256 x 256 tile where it can (x6_tier) and is planned for its residency
+    const bool x6_allowed = std::is_same<T, float>::value && h->f32_product_mode == 0;
+    if (!(gram && x6_allowed && plan_splits_x6_tn(sa, sa.n_b1, kMaxSplits)))
+        plan_splits<FORM_TN>(sa, kSplitTarget, kMaxSplits);
     if ((size_t)sa.ksplits * K * Wg > w.slab_count)
         return fail(h, DCP_ERR_INTERNAL, "nmf slab plan mismatch");
     {
