@@ -10,6 +10,11 @@
 // v_mfma_f32_32x32x16_bf16 into the fp32 accumulator.  A bf16 x bf16 product is exact in fp32; the
 // dropped terms (ml, lm, ll and the r parts) sum to about 2^-26 sum|a||b|, under the 2^-24 unit roundoff
 // of the fp32 accumulation itself, so the error has the norm-wise form and size of the fp32 core's.
+// Except for tiny operands: below 2^-126 a bf16 is subnormal, on a 2^-133 grid, so once |a| < ~2^-108 (l) or
+// ~2^-117 (m) the planes hold a only to ~2^-134 absolutely.  The MFMA keeps bf16 subnormal inputs, and the bound
+// gains an absolute floor:  |C - C64| <= (fp32 size) sum_k |a||b| + 2^-133 (sum_k |a_ik| + sum_k |b_kj|).
+// It is the plain relative bound down to 2^-113; at 2^-120 the relative error reaches ~6e-6, at 2^-126 ~5e-4
+// (K = 256, random signs; DESIGN section 4, tests/test_gpu_bf16x6_range.py).
 // Six bf16 MFMAs (6 x 32 cycles) do the work of sixteen fp32 ones (16 x 64 cycles).
 //
 // Same problem description (GemmProblem), tile map (xcd_remap, mt_fast, two-segment B, split-K ranges)

@@ -169,6 +169,9 @@ def test_mode_switch_default_and_query():
 
 
 def test_golden_solve_same_stop_iteration_both_modes():
+    """The golden fixtures' solves stop at the same iteration in both product modes.  These shapes are far below a
+    whole bf16x6 tile, so both modes run the fp32 core here and this only checks that the mode switch changes
+    nothing else; test_gpu_bf16x6_loop.py compares the stop iteration at a shape that takes the core."""
     import decomp_amd
     import os
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'nmf_golden.npz'))
