@@ -22,9 +22,15 @@
 // 16-byte aligned K-major operands) exists here -- x6_eligible() says when, and the callers keep the fp32
 // core otherwise.
 //
-// Staging: fp32 panels go global -> registers (the next K block's loads are issued before this block's
-// MFMAs), are split into the three planes in registers (v_cvt_pk_bf16_f32 and an fp32 residual) and
-// written to the other LDS buffer; one barrier per K block.  Global -> LDS DMA cannot transform data.
+// Staging: fp32 panels go global -> registers, are split into the three planes in registers
+// (v_cvt_pk_bf16_f32 and an fp32 residual) and written to the other LDS buffer; one barrier per K block.
+// Global -> LDS DMA cannot transform data.  The loads run two blocks ahead and the split runs inside the
+// MFMA stream: during block kb a wave issues the first 2 TN products of each 32-row A block, then splits and
+// stores one panel of block kb + 1 (A panel in the first A block, B panel in the second) and issues that
+// panel's loads for block kb + 2, then the other 4 TN products.  Only MFMAs remain between the last staging
+// and the barrier, so the waves of a SIMD no longer meet the barrier with the matrix pipe idle while all of
+// them split (the 62 % pipe-busy body of round 6).  The register ring stays one block deep: the split frees
+// ra / rb before the loads refill them.
 //   KMAJOR panel (reduction index contiguous): one 16-byte load = 4 k of one row.
 //     LDS image of one plane: [rows][16 k] bf16, 32 bytes per row, two 16-byte chunks (k 0..7, 8..15);
 //     chunk q of row r sits at chunk q ^ ((r >> 3) & 1).  A lane (l31, h) of the 32x32x16 MFMA reads
@@ -38,6 +44,7 @@
 //     x 8 granules; the XOR puts them on 32 distinct bank pairs (conflict free).
 #pragma once
 #include "gemm_mfma_f32.hpp"
+#include <type_traits>
 
 namespace dcp {
 
@@ -193,6 +200,15 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
+    // Pipeline (one barrier per K block): on entry to block kb, buffer kb & 1 holds block kb's planes and
+    // ra / rb hold block kb + 1's fp32 values.  Block kb's MFMAs run in two groups of 6 TN, one per 32-row A
+    // block; the split and the ds_writes of block kb + 1's A panel follow the first 2 TN MFMAs of the first
+    // group, those of its B panel the first 2 TN of the second, each followed by that panel's loads for block
+    // kb + 2.  The
+    // other buffer was last read in block kb - 1, before the barrier that ended it, so it may be written
+    // now.  The loads of the last block re-read block nkb - 1 (in bounds; never used), which keeps the
+    // interior branch free.
+    static_assert(TM == 2, "one panel's staging per 32-row A block");
     f32x4 ra[GA], rb[GB];
     const int nkb = (kend - kbeg) / BK;   // whole K blocks (x6_eligible)
     if (nkb > 0) {
@@ -200,6 +216,9 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
         x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, kbeg, tid);
         x6_lds_store<ALAY, BM, NT>(x6_smem, ra, tid);
         x6_lds_store<BLAY, BN, NT>(x6_smem + X6Panel<BM>::BYTES, rb, tid);
+        const int k1 = kbeg + min(1, nkb - 1) * BK;
+        x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k1, tid);
+        x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k1, tid);
     }
     __syncthreads();
 
@@ -210,16 +229,15 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
 #pragma unroll
     for (int j = 0; j < TN; ++j) boff[j] = x6_frag_off<BLAY, BN>(wn * WN + j * 32, lane);
 
-    for (int kb = 0; kb < nkb; ++kb) {
+    // products (of six) that go out before a group's staging
+    constexpr int STAGE_AFTER = 2;
+    auto kblock = [&](int kb, auto stage_tag) {
+        constexpr bool STAGE = decltype(stage_tag)::value;
         const int cur = kb & 1;
         const char* sA = x6_smem + cur * BUF;
         const char* sB = sA + X6Panel<BM>::BYTES;
-        const bool more = (kb + 1) < nkb;
-        if (more) {   // next block's global loads land during this block's MFMAs
-            const int k0 = kbeg + (kb + 1) * BK;
-            x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k0, tid);
-            x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k0, tid);
-        }
+        char* nxt = x6_smem + (cur ^ 1) * BUF;
+        const int k2 = kbeg + min(kb + 2, nkb - 1) * BK;
         // B fragments of the block first, then the A fragments of one 32-row block at a time: at four waves
         // per SIMD (128 VGPRs) all of them at once would spill
         x6_bf16x8 fb[3][TN];
@@ -230,25 +248,47 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
         // small terms first, hh last; plane index 0 = h, 1 = m, 2 = l
         constexpr int TA[6] = {2, 0, 1, 1, 0, 0};
         constexpr int TB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
+        auto group = [&](auto i_tag) {
+            constexpr int i = decltype(i_tag)::value;
             x6_bf16x8 fa[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) fa[pl] = x6_frag<ALAY, BM>(sA + pl * PA, aoff[i]);
+            auto mfmas = [&](int t0, int t1) {
 #pragma unroll
-            for (int tt = 0; tt < 6; ++tt)
+                for (int tt = t0; tt < t1; ++tt)
 #pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[TA[tt]], fb[TB[tt]][j], acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] =
+                            __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[TA[tt]], fb[TB[tt]][j], acc[i][j], 0, 0, 0);
+            };
+            if constexpr (STAGE) {
+                // the first products go out, then this wave splits and stores one panel of block kb + 1 and
+                // issues its loads for block kb + 2 while they (and the other waves' MFMAs) run; the sched
+                // barriers keep hipcc from sinking the staging to the end of the group
+                mfmas(0, STAGE_AFTER);
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (i == 0) {
+                    x6_lds_store<ALAY, BM, NT>(nxt, ra, tid);
+                    x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k2, tid);
+                } else {
+                    x6_lds_store<BLAY, BN, NT>(nxt + X6Panel<BM>::BYTES, rb, tid);
+                    x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k2, tid);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(STAGE_AFTER, 6);
+            } else {
+                mfmas(0, 6);
+            }
             __builtin_amdgcn_sched_barrier(0);
-        }
-        if (more) {
-            char* nxt = x6_smem + (cur ^ 1) * BUF;
-            x6_lds_store<ALAY, BM, NT>(nxt, ra, tid);
-            x6_lds_store<BLAY, BN, NT>(nxt + X6Panel<BM>::BYTES, rb, tid);
-        }
+        };
+        group(std::integral_constant<int, 0>{});
+        group(std::integral_constant<int, 1>{});
+    };
+    for (int kb = 0; kb + 1 < nkb; ++kb) {
+        kblock(kb, std::true_type{});
         __syncthreads();
     }
+    if (nkb > 0) kblock(nkb - 1, std::false_type{});
 
     // ---- epilogue: the 32x32x16 bf16 MFMA has the C layout of the fp32 one:
     //      col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----
