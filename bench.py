@@ -2,7 +2,7 @@
 """Benchmark of the headline metric (BASELINE.json): NMF multiplicative-update
 iterations/s at Y = 65536 x 4096, k = 256, float32, on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,9 +13,12 @@ synthetic (SURVEY 8d recipe) and resident in HBM before the timed region.
 
 Rank 0 prints one JSON line.  `roofline` is the dominant kernel (the fused
 Y.D^T + quotient GEMM) timed with HIP events on the solver's own stream inside the timed
-steps; `cpu_baseline` is the NumPy oracle (the reference's formulation) timed at the FULL shape
-on this host's cores and `parity` the per-iteration residual of the HIP path against that same
-oracle run, on the timed run's own Y (N = 1, rank 0 only).
+steps.  A plain run stops there: set-up, warm-up, timed steps, --dump-outputs, the line.
+--full adds what takes work of its own after the timed steps: the per-kernel breakdown pass
+(`kernel_ms_avg`, `roofline_stats_gemm`, `phase_ms`), `cpu_baseline` -- the NumPy oracle (the
+reference's formulation) timed at the FULL shape on this host's cores -- with `parity`, the
+per-iteration residual of the HIP path against that same oracle run on the timed run's own Y
+(N = 1, rank 0 only), and `secondary`, the side measurements of the other BASELINE configs.
 """
 import argparse
 import ctypes
@@ -605,9 +608,14 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline figure, also run the per-kernel breakdown pass, the full-shape '
+                         'oracle parity gate with the CPU baseline and the side measurements of the other '
+                         'BASELINE configs')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: skip the oracle parity gate and the CPU baseline')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the few-second side measurements of the other BASELINE configs')
+                    help='with --full: skip the few-second side measurements of the other BASELINE configs')
     ap.add_argument('--no-kernel-events', action='store_true',
                     help='(analysis only) do not bracket kernel groups with hipEvents in the timed steps')
     ap.add_argument('--force-sharded', action='store_true',
@@ -750,25 +758,27 @@ def main():
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(args.dump_outputs, Dcur, state['x'])
 
-    # After the timed region: a short untimed pass with every kernel group bracketed, for the
+    # --full only: after the timed region, a short untimed pass with every kernel group bracketed, for the
     # per-kernel breakdown (kernel_ms_avg); it does not enter `value`.
-    if Dcur is not D:
-        D.copy_(Dcur)
-    _hip.check(h, lib.dcp_profile_reset(h), 'profile_reset')
-    _hip.check(h, lib.dcp_profile_select(h, 0xffffffff), 'profile_select')
-    _hip.check(h, lib.dcp_profile_enable(h, 1), 'profile_enable')
-    Dcur = run(min(10, args.steps))
-    barrier()
-    _hip.check(h, lib.dcp_profile_enable(h, 0), 'profile_enable')
-    breakdown = read_profile()
-    prof_stats = breakdown.get('stats')
+    breakdown, prof_stats = {}, None
+    if args.full:
+        if Dcur is not D:
+            D.copy_(Dcur)
+        _hip.check(h, lib.dcp_profile_reset(h), 'profile_reset')
+        _hip.check(h, lib.dcp_profile_select(h, 0xffffffff), 'profile_select')
+        _hip.check(h, lib.dcp_profile_enable(h, 1), 'profile_enable')
+        Dcur = run(min(10, args.steps))
+        barrier()
+        _hip.check(h, lib.dcp_profile_enable(h, 0), 'profile_enable')
+        breakdown = read_profile()
+        prof_stats = breakdown.get('stats')
 
     # Multi-GPU (or --force-sharded): where one step's time goes on THIS rank -- local statistics (x update +
     # x^T [Y | x]), the exchange (ONE all-reduce of [K, F+K]; its time includes waiting for the slowest rank)
     # and the replicated D update; max over ranks reported.  In-library loop: the hipEvent brackets of the
     # breakdown pass above (the all-reduce has its own label); Python loop: torch events around its three calls.
     phase_ms = None
-    if sharded_run:
+    if args.full and sharded_run:
         if in_library:
             def grp(*names):
                 return sum(breakdown[n]['ms_avg'] for n in names if n in breakdown)
@@ -827,8 +837,9 @@ def main():
             'algorithmic_tflops': W / (elapsed / args.steps) / 1e12,
             'mfma_roofline_frac_whole_step': W / (elapsed / args.steps) / 1e12 / (PEAK_F32_MFMA_TFLOPS * world),
             'finite': finite,
-            'kernel_ms_avg': {k: round(v['ms_avg'], 4) for k, v in breakdown.items()},
         }
+        if args.full:
+            out['kernel_ms_avg'] = {k: round(v['ms_avg'], 4) for k, v in breakdown.items()}
         if phase_ms is not None:
             out['phase_ms'] = phase_ms
         if dumped is not None:
@@ -856,10 +867,10 @@ def main():
                                           'achieved': ach, 'peak': PEAK_F32_MFMA_TFLOPS,
                                           'unit': 'TFLOP/s', 'frac': ach / PEAK_F32_MFMA_TFLOPS,
                                           'launch_ms': st['ms_avg']}
-        if world == 1 and not args.rows and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.rows and not args.no_cpu_baseline:
             # full-shape oracle parity gate + measured CPU baseline (same Y as the timed run)
             out['parity'], out['cpu_baseline'] = parity_and_cpu_baseline(torch, lib, h, Y, D0)
-        if world == 1 and not args.rows and not args.no_secondary:
+        if args.full and world == 1 and not args.rows and not args.no_secondary:
             try:
                 del Y
                 torch.cuda.empty_cache()

@@ -27,7 +27,7 @@ def main():
     ks = sorted(glob.glob(os.path.join(src, 'kt', '*', '*_kernel_stats.csv')), key=os.path.getmtime)[-1]
     rows = list(csv.DictReader(open(ks)))
     with open(os.path.join(out_dir, tag + '_kernel_stats.csv'), 'w') as f:
-        f.write('# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py   (default: --gpus 1 --steps 50 --warmup 5)\n')
+        f.write('# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full   (--gpus 1 --steps 50 --warmup 5)\n')
         f.write('Name,Calls,TotalDurationNs,AverageNs,Percentage,MinNs,MaxNs\n')
         for r in rows:
             f.write('"%s",%s,%s,%s,%s,%s,%s\n' % (short(r['Name'])[:160], r['Calls'], r['TotalDurationNs'],
