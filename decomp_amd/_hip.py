@@ -15,7 +15,7 @@ OK = 0
 ERR_NAMES = {-1: 'DCP_ERR_INVALID', -2: 'DCP_ERR_HIP', -3: 'DCP_ERR_NOMEM',
              -4: 'DCP_ERR_INTERNAL', -5: 'DCP_ERR_UNSUPPORTED', -6: 'DCP_ERR_REF_TYPEERROR',
              -7: 'DCP_ERR_COMM'}
-LIK_L2, LIK_KL = 0, 1
+LIK_L2, LIK_KL, LIK_BETA = 0, 1, 2
 PROF_NLABELS = 10
 PROF_XUPDATE, PROF_STATS = 2, 4
 LASSO_ISTA, LASSO_ACC_ISTA, LASSO_FISTA, LASSO_CD = 0, 1, 2, 3
@@ -112,6 +112,9 @@ SIGNATURES = {
     'dcp_nmf_grad_x_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
     'dcp_nmf_gauss_logp_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_f64)]),
     'dcp_nmf_gauss_logp_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_f64)]),
+    'dcp_set_nmf_beta': (_c_int, [_c_vp, _c_f64]),
+    'dcp_nmf_beta_divergence_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _P(_c_f64)]),
+    'dcp_nmf_beta_divergence_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _P(_c_f64)]),
     'dcp_nmf_apply_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_f64, _c_vp, _c_i64, _c_i64, _P(_c_f64)]),
     'dcp_nmf_apply_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_f64, _c_vp, _c_i64, _c_i64, _P(_c_f64)]),
     'dcp_axpby_f32': (_c_int, [_c_vp, _c_i64, _c_f64, _c_vp, _c_f64, _c_vp]),

@@ -884,6 +884,112 @@ struct EpiKlRatio {
     }
 };
 
+// ---- beta-divergence (DCP_LIK_BETA) ------------------------------------------------------------------
+// Exponent forms of the two parts R1 = (Y o M) o V^(beta-2), R2 = M o V^(beta-1), V = acc + 1e-15: closed
+// forms for the common betas, one log2 + one exp2 per element otherwise.
+enum BetaMode { BETA_0 = 0, BETA_HALF = 1, BETA_1 = 2, BETA_3HALF = 3, BETA_2 = 4, BETA_3 = 5, BETA_GEN = 6 };
+inline int beta_mode(double b) {
+    return b == 0.0 ? BETA_0 : b == 0.5 ? BETA_HALF : b == 1.0 ? BETA_1 : b == 1.5 ? BETA_3HALF
+         : b == 2.0 ? BETA_2 : b == 3.0 ? BETA_3 : BETA_GEN;
+}
+__device__ __forceinline__ float beta_rsqrt(float v) { return rsqrtf(v); }
+__device__ __forceinline__ double beta_rsqrt(double v) { return rsqrt(v); }
+__device__ __forceinline__ float beta_pow(float v, float e) { return exp2f(e * log2f(v)); }
+__device__ __forceinline__ double beta_pow(double v, double e) { return exp(e * log(v)); }
+
+template <class T>
+__device__ __forceinline__ void beta_parts(int mode, T e, T acc, T ym, T m, T& r1, T& r2) {
+    const T v = acc + T(1.0e-15);
+    switch (mode) {
+    case BETA_0: { const T r = T(1) / v; r1 = ym * r * r; r2 = m * r; break; }
+    case BETA_HALF: { const T s = beta_rsqrt(v); r1 = ym * (s * s * s); r2 = m * s; break; }
+    case BETA_1: { r1 = ym / v; r2 = m; break; }
+    case BETA_3HALF: { const T s = beta_rsqrt(v); r1 = ym * s; r2 = m * (s * v); break; }
+    case BETA_2: { r1 = ym; r2 = m * v; break; }
+    case BETA_3: { r1 = ym * v; r2 = m * (v * v); break; }
+    default: { const T p = beta_pow(v, e); r1 = ym * p; r2 = m * (p * v); break; }
+    }
+}
+
+// Forward product of a beta step: both gradient operands in one pass over x.D.
+//   r1 = (Y o M) o V^(beta-2),  r2 = M o V^(beta-1)       (M = 1 without a mask)
+// ym is Y o M (the caller's pre-masked Y); mode = beta_mode(beta), e = beta - 2.
+template <class T>
+struct EpiBetaParts {
+    static constexpr bool kVec4 = std::is_same<T, float>::value;
+    const T* ym;
+    long ld_y;
+    const T* mask;  // nullable
+    long ld_mask;
+    int mode;
+    T e;
+    T* r1;
+    T* r2;
+    long ld_out;
+    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
+        const T m = mask != nullptr ? mask[(long)r * ld_mask + c] : T(1);
+        T a, b;
+        beta_parts<T>(mode, e, v, ym[(long)r * ld_y + c], m, a, b);
+        r1[(long)r * ld_out + c] = a;
+        r2[(long)r * ld_out + c] = b;
+    }
+    bool vec_ok() const {
+        return al16_ptr(ym) && al16_ptr(r1) && al16_ptr(r2) && (ld_y % 4) == 0 && (ld_out % 4) == 0 &&
+               (mask == nullptr || (al16_ptr(mask) && (ld_mask % 4) == 0));
+    }
+    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
+        if constexpr (std::is_same<T, float>::value) {
+            const f32x4 yy = *reinterpret_cast<const f32x4*>(ym + (long)r * ld_y + c0);
+            f32x4 m = {1.0f, 1.0f, 1.0f, 1.0f};
+            if (mask != nullptr) m = *reinterpret_cast<const f32x4*>(mask + (long)r * ld_mask + c0);
+            f32x4 a, b;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float ai, bi;
+                beta_parts<float>(mode, e, v[i], yy[i], m[i], ai, bi);
+                a[i] = ai;
+                b[i] = bi;
+            }
+            *reinterpret_cast<f32x4*>(r1 + (long)r * ld_out + c0) = a;
+            *reinterpret_cast<f32x4*>(r2 + (long)r * ld_out + c0) = b;
+        }
+    }
+};
+
+// d_beta(y | v) in double (Fevotte & Idier 2011):
+//   beta = 0: y/v - log(y/v) - 1     beta = 1: y log(y/v) - y + v  (0 log 0 = 0)
+//   otherwise (y^beta + (beta-1) v^beta - beta y v^(beta-1)) / (beta (beta-1))
+__device__ __forceinline__ double beta_divergence_elem(double beta, double y, double v) {
+    if (beta == 0.0) {
+        const double q = y / v;
+        return q - log(q) - 1.0;
+    }
+    if (beta == 1.0) return (y > 0.0 ? y * log(y / v) : 0.0) - y + v;
+    if (beta == 2.0) {
+        const double d = y - v;
+        return 0.5 * d * d;
+    }
+    return (pow(y, beta) + (beta - 1.0) * pow(v, beta) - beta * y * pow(v, beta - 1.0)) / (beta * (beta - 1.0));
+}
+
+// out = M o d_beta(Y | acc + 1e-15), an entry with M == 0 contributing exactly 0 (reduced by sum_partial_kernel)
+template <class T>
+struct EpiBetaDivergence {
+    const T* y;
+    long ld_y;
+    const T* mask;  // nullable
+    long ld_mask;
+    double beta;
+    T* out;
+    long ld_out;
+    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
+        const double m = mask != nullptr ? (double)mask[(long)r * ld_mask + c] : 1.0;
+        double d = 0.0;
+        if (m != 0.0) d = m * beta_divergence_elem(beta, (double)y[(long)r * ld_y + c], (double)v + 1.0e-15);
+        out[(long)r * ld_out + c] = (T)d;
+    }
+};
+
 // Residual: out = (y - acc) [* mask]   (parity metric; reduced by sumsq_partial_kernel)
 template <class T>
 struct EpiResidual {

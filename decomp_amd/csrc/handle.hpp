@@ -68,6 +68,8 @@ struct dcp_handle {
     // float32 products of the NMF Gram path (dcp_set_f32_product_mode): 0 = split-bf16 core (bf16x6,
     // gemm_mfma_bf16x6.hpp), 1 = the exact fp32 MFMA core
     int f32_product_mode = 0;
+    // beta of DCP_LIK_BETA (dcp_set_nmf_beta), read when an NMF call that passes DCP_LIK_BETA is enqueued
+    double nmf_beta = 0.0;
 };
 
 namespace dcp {

@@ -484,6 +484,18 @@ __global__ void __launch_bounds__(256) sumsq_partial_kernel(const T* __restrict_
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
+// per-workgroup sums of a[n] in double (second stage: the caller sums `partial` in order)
+template <class T>
+__global__ void __launch_bounds__(256) sum_partial_kernel(const T* __restrict__ a, long n,
+                                                          double* __restrict__ partial) {
+    __shared__ double sh[4];
+    double c = 0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L)
+        c += (double)a[i];
+    double t = block_sum_256(c, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
 inline int grid_for(long n, int cap = 2048) {
     long g = (n + 255) / 256;
     if (g < 1) g = 1;

@@ -1,5 +1,7 @@
 // C ABI: NMF multiplicative update (see include/decomp_hip.h for the contract and the
 // reference lines each entry point replaces).
+#include <cmath>
+
 #include "comm.hpp"
 #include "nmf_impl.hpp"
 
@@ -15,7 +17,7 @@ int check_nmf_args(dcp_handle* h, const T* Y, const T* X, const T* D, int64_t N,
     if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
     if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL || F + K > 0x3fffffffLL)
         return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
-    if (lik != DCP_LIK_L2 && lik != DCP_LIK_KL) return fail(h, DCP_ERR_INVALID, "bad likelihood");
+    if (lik != DCP_LIK_L2 && lik != DCP_LIK_KL && lik != DCP_LIK_BETA) return fail(h, DCP_ERR_INVALID, "bad likelihood");
     return DCP_OK;
 }
 
@@ -376,6 +378,33 @@ int nmf_gauss_logp_api(dcp_handle* h, const T* Y, const T* mask, const T* X, con
     return DCP_OK;
 }
 
+// sum M o d_beta(Y | X D + 1e-15) with the handle's beta, to the host (accumulated in double).
+template <class T>
+int nmf_beta_divergence_api(dcp_handle* h, const T* Y, const T* mask, const T* X, const T* D, int64_t N,
+                            int64_t F, int64_t K, double* out) {
+    DCP_TRY(check_nmf_args(h, Y, X, D, N, F, K, DCP_LIK_BETA));
+    if (!out) return fail(h, DCP_ERR_INVALID, "out is null");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    const int blocks = 1024;
+    WsPlan plan;
+    plan.add<T>((size_t)N * F);
+    plan.add<double>(blocks);
+    DCP_TRY(ws_reserve(h, plan.total));
+    ws_reset(h);
+    T* tmp = ws_alloc<T>(h, (size_t)N * F);
+    double* part = ws_alloc<double>(h, blocks);
+    if (!tmp || !part) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+    void* hostv = nullptr;
+    DCP_TRY(host_scratch(h, sizeof(double) * blocks, &hostv));
+    DCP_TRY(nmf_beta_divergence<T>(h, Y, mask, X, D, N, F, K, h->nmf_beta, tmp, part, blocks));
+    DCP_HIP_OK(h, hipMemcpyAsync(hostv, part, sizeof(double) * blocks, hipMemcpyDeviceToHost, h->stream));
+    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
+    double acc = 0.0;
+    for (int i = 0; i < blocks; ++i) acc += reinterpret_cast<double*>(hostv)[i];
+    *out = acc;
+    return DCP_OK;
+}
+
 // D_new = l2_strict(rule(D, P, Q)) and max|D - D_new| (host):
 //   alpha < 0 : D * max(P,0) / max(Q,eps)                         (grads.py:93)
 //   alpha >= 0: max(D * ((1-alpha) + alpha * P / max(Q,eps)), 0)  (kasai.py:77-78)
@@ -486,6 +515,20 @@ int dcp_nmf_gauss_logp_f32(dcp_handle* h, const float* Y, const float* mask, con
 int dcp_nmf_gauss_logp_f64(dcp_handle* h, const double* Y, const double* mask, const double* X, const double* D,
                            int64_t N, int64_t F, int64_t K, double scale, double* out) {
     return nmf_gauss_logp_api<double>(h, Y, mask, X, D, N, F, K, scale, out);
+}
+int dcp_set_nmf_beta(dcp_handle* h, double beta) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!std::isfinite(beta)) return fail(h, DCP_ERR_INVALID, "beta must be finite");
+    h->nmf_beta = beta;
+    return DCP_OK;
+}
+int dcp_nmf_beta_divergence_f32(dcp_handle* h, const float* Y, const float* mask, const float* X, const float* D,
+                                int64_t N, int64_t F, int64_t K, double* out) {
+    return nmf_beta_divergence_api<float>(h, Y, mask, X, D, N, F, K, out);
+}
+int dcp_nmf_beta_divergence_f64(dcp_handle* h, const double* Y, const double* mask, const double* X,
+                                const double* D, int64_t N, int64_t F, int64_t K, double* out) {
+    return nmf_beta_divergence_api<double>(h, Y, mask, X, D, N, F, K, out);
 }
 int dcp_nmf_apply_f32(dcp_handle* h, const float* D, const float* P, const float* Q, double alpha,
                       float* D_new, int64_t K, int64_t F, double* maxdiff) {

@@ -7,6 +7,11 @@
 //   decomp/nmf_methods/grads.py:143-160     Poisson gradient parts
 //   decomp/utils/normalize.py:13-21         l2_strict
 //
+// DCP_LIK_BETA (beta from the handle, dcp_set_nmf_beta) runs the same loop with the beta-divergence parts
+//   R1 = (Y o M) o V^(beta-2),  R2 = M o V^(beta-1),  V = x D + 1e-15
+//   x: pos = R1 D^T, neg = R2 D^T        D: pos = x^T R1, neg = x^T R2
+// both written by one forward product (EpiBetaParts) into two [N,F] intermediates.
+//
 // l2 without a mask uses the Gram formulation:
 //   (x D) D^T = x (D D^T)   and   x^T (x D) = (x^T x) D
 // which removes the [N,F] intermediate and 2/3 of the flops; masked and KL updates
@@ -43,7 +48,8 @@ template <class T>
 struct NmfStatsWs {
     T* Q = nullptr;       // [N,K]   negative part of the x gradient
     T* G = nullptr;       // [K,K]   D D^T (l2, no mask)
-    T* f = nullptr;       // [N,F]   (x D) o M  or  KL ratio
+    T* f = nullptr;       // [N,F]   (x D) o M  or  KL ratio  or  beta R1
+    T* f2 = nullptr;      // [N,F]   beta R2
     T* Ym = nullptr;      // [N,F]   Y o M when the caller did not pre-mask
     T* slabs = nullptr;   // split-K partials
     T* vecK = nullptr;    // [K]     KL: colsum(D) / colsum(x)
@@ -93,7 +99,7 @@ inline size_t nmf_slab_elems(const NmfShape<T>& s) {
     GemmArgs<T> pg;
     const int ps = nmf_xupdate_splits<T>(s.N, s.F, s.K, pg);
     size_t x_slabs = ps > 1 ? (size_t)ps * s.N * s.K : 0;
-    if (ps > 1 && s.masked && s.lik == DCP_LIK_L2) {      // the stacked [f ; Y o M] . D^T launch
+    if (ps > 1 && ((s.masked && s.lik == DCP_LIK_L2) || s.lik == DCP_LIK_BETA)) {   // stacked [A1 ; A2] . D^T
         GemmArgs<T> sg;
         const int ss = nmf_xupdate_splits<T>(2 * s.N, s.F, s.K, sg);
         const size_t st_slabs = (size_t)(ss > 1 ? ss : 1) * 2 * s.N * s.K;
@@ -109,6 +115,7 @@ inline void nmf_plan_stats(WsPlan& plan, const NmfShape<T>& s, bool need_ym) {
     plan.add<T>((size_t)s.N * s.K);                       // Q
     if (gram) plan.add<T>((size_t)s.K * s.K);             // G
     if (!gram) plan.add<T>((size_t)s.N * s.F);            // f
+    if (s.lik == DCP_LIK_BETA) plan.add<T>((size_t)s.N * s.F);   // f2
     if (need_ym) plan.add<T>((size_t)s.N * s.F);          // Ym
     plan.add<T>(nmf_slab_elems(s));                       // slabs
     plan.add<T>((size_t)s.K);                             // vecK
@@ -121,13 +128,14 @@ inline int nmf_carve_stats(dcp_handle* h, NmfStatsWs<T>& w, const NmfShape<T>& s
     w.Q = ws_alloc<T>(h, (size_t)s.N * s.K);
     if (gram) w.G = ws_alloc<T>(h, (size_t)s.K * s.K);
     if (!gram) w.f = ws_alloc<T>(h, (size_t)s.N * s.F);
+    if (s.lik == DCP_LIK_BETA) w.f2 = ws_alloc<T>(h, (size_t)s.N * s.F);
     if (need_ym) w.Ym = ws_alloc<T>(h, (size_t)s.N * s.F);
     w.slab_count = nmf_slab_elems(s);
     w.slabs = ws_alloc<T>(h, w.slab_count);
     w.vecK = ws_alloc<T>(h, (size_t)s.K);
     w.part = ws_alloc<T>(h, (size_t)64 * (s.K > s.F ? s.K : s.F));
     if (!w.Q || !w.slabs || !w.vecK || !w.part || (gram && !w.G) || (!gram && !w.f) ||
-        (need_ym && !w.Ym))
+        (need_ym && !w.Ym) || (s.lik == DCP_LIK_BETA && !w.f2))
         return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
     return DCP_OK;
 }
@@ -196,13 +204,17 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
     const int N = (int)s.N, F = (int)s.F, K = (int)s.K;
     const bool gram = (s.lik == DCP_LIK_L2 && !s.masked);
     const int W = (int)nmf_stats_width(s.F, s.K, s.lik, s.masked);
+    const double beta = h->nmf_beta;
 
-    // forward product x.D with an elementwise epilogue into the [N,F] intermediate w.f
+    // forward product x.D with an elementwise epilogue into the [N,F] intermediate w.f (beta: w.f and w.f2)
     auto forward = [&](const T* X) -> int {
         ProfScope ps(h, DCP_PROF_FWD);
         GemmArgs<T> fa;
         fa.A = X; fa.lda = K; fa.B = D; fa.ldb = F; fa.M = N; fa.N = F; fa.K = K;
-        if (s.lik == DCP_LIK_L2) {  // f = (x D) o M                 (grads.py:113,123)
+        if (s.lik == DCP_LIK_BETA) {   // R1 = (Y o M) V^(beta-2), R2 = M V^(beta-1)
+            DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, fa, EpiBetaParts<T>{Ypre, F, mask, F, beta_mode(beta), T(beta - 2.0),
+                                                                     w.f, w.f2, F})));
+        } else if (s.lik == DCP_LIK_L2) {  // f = (x D) o M                 (grads.py:113,123)
             if constexpr (std::is_same<T, float>::value) {
                 if (w.mbits != nullptr) {
                     DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, fa, EpiMulMaskBits{w.mbits, (long)F, w.f, (long)F})));
@@ -212,6 +224,33 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
             DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, fa, EpiMulMask<T>{mask, F, w.f, F})));
         } else                       // r = (Y o M) / (x D + eps)     (grads.py:145-149)
             DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, fa, EpiKlRatio<T>{Ypre, F, nullptr, 0, w.f, F})));
+        return DCP_OK;
+    };
+
+    // Few rows per GPU (float): both parts of the x gradient are products against the same D^T -- [A_neg ; A_pos] . D^T
+    // as ONE split-K launch over the stacked rows (2N x K output: twice the tiles, half the splits, one set of fixed
+    // costs), then one quotient kernel.  Masked l2: [f ; Y o M];  beta: [R2 ; R1].  Sets done when it ran.
+    auto stacked_xupdate = [&](const T* a_neg, const T* a_pos, bool& done) -> int {
+        done = false;
+        if constexpr (std::is_same<T, float>::value) {
+            GemmArgs<T> probe;
+            const bool split_single = nmf_xupdate_splits<T>(s.N, s.F, s.K, probe) > 1;
+            if (split_single && (N % 256) == 0 && (F % 16) == 0) {
+                ProfScope ps(h, DCP_PROF_XUPDATE);
+                GemmArgs<T> sg;
+                nmf_xupdate_splits<T>(2 * s.N, s.F, s.K, sg);      // plan for the stacked problem
+                sg.A = a_neg; sg.lda = F; sg.A2 = a_pos; sg.lda2 = F; sg.m_a1 = N;
+                sg.B = D; sg.ldb = F;
+                if (sg.ksplits < 1) sg.ksplits = 1;
+                if ((size_t)sg.ksplits * 2 * N * K > w.slab_count)
+                    return fail(h, DCP_ERR_INTERNAL, "nmf stacked x-update slab plan mismatch");
+                DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, sg, EpiSlab<T>{w.slabs, K, (long)2 * N * K})));
+                hipLaunchKernelGGL((mu_quotient_stacked_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0,
+                                   st, Xin, (const T*)w.slabs, (long)2 * N * K, sg.ksplits, (long)N * K, Xout);
+                DCP_LAUNCH_OK(h, hipGetLastError());
+                done = true;
+            }
+        }
         return DCP_OK;
     };
 
@@ -248,34 +287,21 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
         }
     } else if (s.lik == DCP_LIK_L2) {
         DCP_TRY(forward(Xin));
-        if constexpr (std::is_same<T, float>::value) {
-            // masked l2 with few rows per GPU: both parts of the x gradient are products against the
-            // same D^T -- [f ; Y o M] . D^T as ONE split-K launch over the stacked rows (2N x K output:
-            // twice the tiles, half the splits, one set of fixed costs), then one quotient kernel
-            GemmArgs<T> sg;
-            sg.A = w.f; sg.lda = F; sg.A2 = Ypre; sg.lda2 = F; sg.m_a1 = N;
-            sg.B = D; sg.ldb = F; sg.M = 2 * N; sg.N = K; sg.K = F;
-            GemmArgs<T> probe;
-            const bool split_single = nmf_xupdate_splits<T>(s.N, s.F, s.K, probe) > 1;
-            if (split_single && (N % 256) == 0 && (F % 16) == 0) {
-                ProfScope ps(h, DCP_PROF_XUPDATE);
-                nmf_xupdate_splits<T>(2 * s.N, s.F, s.K, sg);      // plan for the stacked problem
-                sg.A = w.f; sg.lda = F; sg.A2 = Ypre; sg.lda2 = F; sg.m_a1 = N;
-                sg.B = D; sg.ldb = F;
-                if (sg.ksplits < 1) sg.ksplits = 1;
-                if ((size_t)sg.ksplits * 2 * N * K > w.slab_count)
-                    return fail(h, DCP_ERR_INTERNAL, "nmf stacked x-update slab plan mismatch");
-                DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, sg, EpiSlab<T>{w.slabs, K, (long)2 * N * K})));
-                hipLaunchKernelGGL((mu_quotient_stacked_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0,
-                                   st, Xin, (const T*)w.slabs, (long)2 * N * K, sg.ksplits, (long)N * K, Xout);
-                DCP_LAUNCH_OK(h, hipGetLastError());
-                x_done = true;
-            }
-        }
+        DCP_TRY(stacked_xupdate(w.f, Ypre, x_done));
         if (!x_done) {
             ProfScope ps(h, DCP_PROF_XNEG);   // Q = f D^T
             GemmArgs<T> q;
             q.A = w.f; q.lda = F; q.B = D; q.ldb = F; q.M = N; q.N = K; q.K = F;
+            DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, q, EpiStore<T>{w.Q, K})));
+        }
+    } else if (s.lik == DCP_LIK_BETA) {
+        DCP_TRY(forward(Xin));
+        xnum_A = w.f;                         // pos = R1 D^T
+        DCP_TRY(stacked_xupdate(w.f2, w.f, x_done));
+        if (!x_done) {
+            ProfScope ps(h, DCP_PROF_XNEG);   // Q = R2 D^T
+            GemmArgs<T> q;
+            q.A = w.f2; q.lda = F; q.B = D; q.ldb = F; q.M = N; q.N = K; q.K = F;
             DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, q, EpiStore<T>{w.Q, K})));
         }
     } else {
@@ -334,6 +360,9 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
     } else if (s.lik == DCP_LIK_L2) {
         DCP_TRY(forward(X));
         sa.B = Ypre; sa.ldb = F; sa.B2 = w.f; sa.ldb2 = F; sa.n_b1 = F;    // [ x^T Ym | x^T f ]
+    } else if (s.lik == DCP_LIK_BETA) {
+        DCP_TRY(forward(X));
+        sa.B = w.f; sa.ldb = F; sa.B2 = w.f2; sa.ldb2 = F; sa.n_b1 = F;    // [ x^T R1 | x^T R2 ]
     } else {
         DCP_TRY(forward(X));
         if (s.masked) {
@@ -375,6 +404,7 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
 // Gaussian.grad_x / Poisson.grad_x (grads.py:108-115, 143-150): pos, neg [N, K].
 //   l2        : pos = (Y o M) D^T,  neg = ((x D) o M) D^T   (no mask: neg = x (D D^T), the Gram identity)
 //   kl        : pos = ((Y o M) / (x D + eps)) D^T,  neg = colsum(D) on every row (no mask) or M D^T
+//   beta      : pos = R1 D^T,  neg = R2 D^T  (full [N, K] parts, mask or not)
 // (for kl without a mask the reference returns the [1, K] row d.T.sum(axis=0, keepdims=True); the caller
 //  slices row 0 of neg).  Ypre = Y o M (or Y).
 template <class T>
@@ -398,7 +428,15 @@ inline int nmf_grad_x(dcp_handle* h, const T* Ypre, const T* mask, const T* X, c
     } else {
         GemmArgs<T> fa;
         fa.A = X; fa.lda = K; fa.B = D; fa.ldb = F; fa.M = N; fa.N = F; fa.K = K;
-        if (s.lik == DCP_LIK_L2) {
+        if (s.lik == DCP_LIK_BETA) {
+            const double beta = h->nmf_beta;
+            DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, fa, EpiBetaParts<T>{Ypre, F, mask, F, beta_mode(beta), T(beta - 2.0),
+                                                                     w.f, w.f2, F})));
+            GemmArgs<T> q;
+            q.A = w.f2; q.lda = F; q.B = D; q.ldb = F; q.M = N; q.N = K; q.K = F;
+            DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, q, EpiStore<T>{neg, K})));
+            pos_A = w.f;
+        } else if (s.lik == DCP_LIK_L2) {
             DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, fa, EpiMulMask<T>{mask, F, w.f, F})));
             GemmArgs<T> q;
             q.A = w.f; q.lda = F; q.B = D; q.ldb = F; q.M = N; q.N = K; q.K = F;
@@ -484,6 +522,21 @@ inline int nmf_residual(dcp_handle* h, const T* Y, const T* mask, const T* X, co
     a.A = X; a.lda = K; a.B = D; a.ldb = F; a.M = (int)N; a.N = (int)F; a.K = (int)K;
     DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiResidual<T>{Y, F, mask, F, tmpNF, F})));
     hipLaunchKernelGGL((sumsq_partial_kernel<T>), dim3(nblocks), dim3(256), 0, h->stream, tmpNF,
+                       (long)N * F, partial_dev);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
+// ---- beta divergence  sum M o d_beta(Y | X D + 1e-15) -----------------------------------------------
+// Per-element divergence in double (EpiBetaDivergence), stored in tmpNF, then per-workgroup double sums
+// into partial_dev[nblocks]; the caller sums the partials in order (deterministic).
+template <class T>
+inline int nmf_beta_divergence(dcp_handle* h, const T* Y, const T* mask, const T* X, const T* D, int64_t N,
+                               int64_t F, int64_t K, double beta, T* tmpNF, double* partial_dev, int nblocks) {
+    GemmArgs<T> a;
+    a.A = X; a.lda = K; a.B = D; a.ldb = F; a.M = (int)N; a.N = (int)F; a.K = (int)K;
+    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiBetaDivergence<T>{Y, F, mask, F, beta, tmpNF, F})));
+    hipLaunchKernelGGL((sum_partial_kernel<T>), dim3(nblocks), dim3(256), 0, h->stream, (const T*)tmpNF,
                        (long)N * F, partial_dev);
     DCP_LAUNCH_OK(h, hipGetLastError());
     return DCP_OK;

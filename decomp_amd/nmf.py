@@ -24,20 +24,55 @@ MINIBATCH_METHODS = [
 _JITTER = 1.0e-15
 
 
-def _likelihood_code(likelihood):
-    """grads.py:7-14: the kernel code (an int) of a built-in likelihood, or the user-supplied
-    ``Likelihood`` instance itself (grads.py:12-13), which then runs through the host loop
-    ``_run_mu_user`` / ``nmf_minibatch._UserKernels``."""
+def _likelihood_spec(likelihood):
+    """grads.py:7-14: (code, beta).  code is the kernel code (an int) of a built-in likelihood, or the
+    user-supplied ``Likelihood`` instance itself (grads.py:12-13), which then runs through the host loop
+    ``_run_mu_user`` / ``nmf_minibatch._UserKernels``.  beta is the exponent that goes with DCP_LIK_BETA
+    ('is' / 'itakura-saito' = 0, or a ``BetaDivergence``'s own), None for every other code."""
     from .nmf_methods import grads
     if isinstance(likelihood, str):
         if likelihood in ('l2', 'gaussian'):
-            return _hip.LIK_L2
+            return _hip.LIK_L2, None
         if likelihood in ('kl', 'poisson'):
-            return _hip.LIK_KL
+            return _hip.LIK_KL, None
+        if likelihood in ('is', 'itakura-saito'):
+            return _hip.LIK_BETA, 0.0
     elif isinstance(likelihood, grads.Likelihood):
-        code = grads.fused_code(likelihood)
-        return likelihood if code is None else code
+        spec = grads.fused_spec(likelihood)
+        return (likelihood, None) if spec is None else spec
     raise NotImplementedError('Likelihood {} is not implemented for nmf'.format(likelihood))
+
+
+def _likelihood_code(likelihood):
+    """The code of ``_likelihood_spec`` alone."""
+    return _likelihood_spec(likelihood)[0]
+
+
+def _fused_lik(lik, beta):
+    """What the minibatch loops take as ``lik``: the code, or (DCP_LIK_BETA, beta)."""
+    return (lik, beta) if isinstance(lik, int) and lik == _hip.LIK_BETA else lik
+
+
+def _beta_of(likelihood):
+    """beta of a beta-divergence likelihood ('is' / 'itakura-saito', any ``BetaDivergence``), else None."""
+    from .nmf_methods import grads
+    if isinstance(likelihood, str):
+        return 0.0 if likelihood in ('is', 'itakura-saito') else None
+    if isinstance(likelihood, grads.BetaDivergence):
+        return likelihood.beta
+    return None
+
+
+def _check_beta_data(likelihood, y, mask):
+    """Data a beta divergence is defined on: beta < 2 needs y >= 0 (as 'kl', nmf.py:67-68), beta <= 0 also
+    y > 0 wherever mask != 0 (a missing entry is zero by the reference's convention, nmf.py:48).  NumPy arrays
+    are checked on the host, torch tensors on their device.  Raises AssertionError."""
+    beta = _beta_of(likelihood)
+    if beta is None or beta >= 2.0:
+        return
+    assertion.assert_nonnegative_host_or_device(y)
+    if beta <= 0.0:
+        assertion.assert_positive_where(y, mask)
 
 
 class _OnesLike(object):
@@ -90,6 +125,7 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
     D_dev = _arrays.to_device(D, copy=True)           # normalised in place below
     dev = D_dev.device.index
     assertion.assert_nonnegative(D_dev)                               # nmf.py:64-65
+    _check_beta_data(likelihood, y, mask)
     if streamed:
         return _solve_streamed(y, D_dev, x_given, tol, minibatch, maxiter, method, likelihood,
                                mask, random_seed, kwargs)
@@ -113,7 +149,7 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
             if kwargs:  # batch_mu.solve accepts no extra keyword (nmf.py:77, batch_mu.py:8)
                 raise TypeError('solve() got an unexpected keyword argument %r'
                                 % sorted(kwargs)[0])
-            lik = _likelihood_code(likelihood)
+            lik, beta = _likelihood_spec(likelihood)
             get_array_module(y, mask)
             if not isinstance(lik, int):
                 it, D_dev, x_dev = _run_mu_user(y, mask, x_dev, D_dev, lik, tol, maxiter, kind)
@@ -121,7 +157,7 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
             if y_dev is None:
                 y_dev = _arrays.to_device(y, dev)
             m_dev = _arrays.to_device(mask, dev)
-            it = _run_mu(y_dev, m_dev, x_dev, D_dev, lik, tol, maxiter)
+            it = _run_mu(y_dev, m_dev, x_dev, D_dev, lik, tol, maxiter, beta=beta)
             return it, _arrays.to_caller(D_dev, kind), _arrays.to_caller(x_dev, kind)
         raise NotImplementedError('Batch-NMF with {} algorithm is not yet '
                                   'implemented.'.format(method))
@@ -132,7 +168,7 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
         raise NotImplementedError('NMF with {} algorithm is not yet '
                                   'implemented.'.format(method))
     get_array_module(y, D, x_given, mask)
-    lik = _likelihood_code(likelihood)
+    lik = _fused_lik(*_likelihood_spec(likelihood))
     if y_dev is None:
         y_dev = _arrays.to_device(y, dev)
     ybat = MinibatchData(y_dev, minibatch)
@@ -178,7 +214,7 @@ def _solve_streamed(y, D_dev, x_given, tol, minibatch, maxiter, method, likeliho
     if _arrays.is_torch(y) and isinstance(likelihood, str) and likelihood in ['kl']:
         assertion.assert_nonnegative(_arrays.to_device(y, dev))
     _arrays.l2_normalize_(D_dev, strict=True)                         # nmf.py:70
-    lik = _likelihood_code(likelihood)
+    lik = _fused_lik(*_likelihood_spec(likelihood))
     xbat = dataset(x_given, True)
     ybat = dataset(y, False)
     mbat = dataset(mask, False)
@@ -192,8 +228,10 @@ def _solve_streamed(y, D_dev, x_given, tol, minibatch, maxiter, method, likeliho
     return it, Dout, xout
 
 
-def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None):
-    """batch_mu.solve on device arrays; x and D are updated in place.  Returns it."""
+def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None, beta=None):
+    """batch_mu.solve on device arrays; x and D are updated in place.  Returns it.  ``beta`` goes with
+    lik == DCP_LIK_BETA."""
+    from .nmf_methods.grads import set_beta
     lib, h = _arrays.lib_handle(D)
     sfx = _arrays.suffix(D)
     N, F = y.shape
@@ -205,6 +243,7 @@ def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None):
     if resid_trace is not None:
         trace = (ctype * max(int(maxiter), 1))()
     fn = getattr(lib, 'dcp_nmf_mu_' + sfx)
+    set_beta(h, lik, beta)
     rc = fn(h, _arrays.ptr(y), _arrays.ptr(mask), _arrays.ptr(x), _arrays.ptr(D),
             N, F, K, lik, ctype(tol), int(maxiter), ctypes.byref(it), ctypes.byref(last),
             trace)

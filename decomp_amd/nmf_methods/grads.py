@@ -12,7 +12,12 @@ computes its gradient parts on arrays of the caller's kind (NumPy in -> NumPy ar
 CUDA in -> torch CUDA tensors) and the library applies the reference's update rule
 ``cur * max(pos, 0) / max(neg, 1e-15)`` (``dcp_mu_quotient_*``), ``l2_strict`` and the
 ``max|D - D_new|`` stop test (``dcp_nmf_apply_*``) on the GPU.
+
+``BetaDivergence(beta)`` adds the beta-divergence family (beta = 0: Itakura-Saito, 1: KL, 2: square loss) with
+the same MU rule (Fevotte & Idier 2011); ``nmf.solve`` runs it fused (``DCP_LIK_BETA``).
 """
+import math
+
 from .. import _arrays, _hip
 
 _JITTER = 1.0e-15
@@ -78,7 +83,13 @@ def _device_args(y, x, d, mask):
     return kind, yd, xd, dd, md
 
 
-def _grad_x(code, y, x, d, mask):
+def set_beta(h, code, beta):
+    """Hand beta to the handle right before a call that passes DCP_LIK_BETA (``dcp_set_nmf_beta``)."""
+    if code == _hip.LIK_BETA:
+        _hip.check(h, _hip.load().dcp_set_nmf_beta(h, float(beta)), 'dcp_set_nmf_beta')
+
+
+def _grad_x(code, y, x, d, mask, beta=None):
     """The two parts of the x gradient, [N, K] each (``dcp_nmf_grad_x_*``)."""
     import torch
     kind, yd, xd, dd, md = _device_args(y, x, d, mask)
@@ -87,13 +98,14 @@ def _grad_x(code, y, x, d, mask):
     pos = torch.empty((N, K), dtype=yd.dtype, device=yd.device)
     neg = torch.empty((N, K), dtype=yd.dtype, device=yd.device)
     lib, h = _arrays.lib_handle(yd)
+    set_beta(h, code, beta)
     fn = getattr(lib, 'dcp_nmf_grad_x_' + _arrays.suffix(yd))
     _hip.check(h, fn(h, _arrays.ptr(yd), _arrays.ptr(md), _arrays.ptr(xd), _arrays.ptr(dd), N, F, K, code,
                      _arrays.ptr(pos), _arrays.ptr(neg)), 'dcp_nmf_grad_x')
     return kind, pos, neg
 
 
-def _grad_d(code, y, x, d, mask):
+def _grad_d(code, y, x, d, mask, beta=None):
     """The two parts of the D gradient, [K, F] each (``dcp_nmf_grads_*`` without an x update)."""
     import torch
     kind, yd, xd, dd, md = _device_args(y, x, d, mask)
@@ -102,6 +114,7 @@ def _grad_d(code, y, x, d, mask):
     pos = torch.empty((K, F), dtype=yd.dtype, device=yd.device)
     neg = torch.empty((K, F), dtype=yd.dtype, device=yd.device)
     lib, h = _arrays.lib_handle(yd)
+    set_beta(h, code, beta)
     fn = getattr(lib, 'dcp_nmf_grads_' + _arrays.suffix(yd))
     _hip.check(h, fn(h, _arrays.ptr(yd), _arrays.ptr(md), _arrays.ptr(xd), _arrays.ptr(dd), N, F, K, code, 0,
                      _arrays.ptr(pos), _arrays.ptr(neg)), 'dcp_nmf_grads')
@@ -172,24 +185,97 @@ class Poisson(Likelihood):
         raise AttributeError("'Poisson' object has no attribute 'scale'")
 
 
-def fused_code(likelihood):
-    """The kernel code of a likelihood that ``nmf.solve`` may run as fused kernels: an instance of Gaussian /
-    Poisson -- or of a subclass that overrides none of the four methods the MU loop calls (a subclass that only
-    adds ``logp`` or bookkeeping keeps the fused path); None otherwise."""
-    for base in (Gaussian, Poisson):
+class BetaDivergence(Likelihood):
+    """Beta-divergence loss  sum M o d_beta(y | x d + 1e-15)  (Fevotte & Idier 2011), minimised by the
+    reference's MU rule ``cur * max(pos, 0) / max(neg, 1e-15)`` on the parts (V = x d + 1e-15, M = mask or 1)
+
+        R1 = (y o M) o V^(beta-2),  R2 = M o V^(beta-1)
+        grad_x = (R1 d^T, R2 d^T)  [N, K],   grad_d = (x^T R1, x^T R2)  [K, F]
+
+    beta = 0 is Itakura-Saito, beta = 1 KL (``Poisson``), beta = 2 the square loss (``Gaussian``).
+    ``nmf.solve`` runs it as fused kernels (DCP_LIK_BETA; beta 1 and 2 dispatch to the 'kl' / 'l2' kernels).
+    The parts are full arrays with and without a mask (no broadcast shapes).  Every method runs on the GPU and
+    returns the caller's array kind."""
+    _code = _hip.LIK_BETA
+
+    def __init__(self, beta):
+        beta = float(beta)
+        if not math.isfinite(beta):
+            raise ValueError('beta must be finite, got %r' % beta)
+        self.beta = beta
+
+    def grad_x(self, y, x, d, mask):
+        kind, pos, neg = _grad_x(self._code, y, x, d, mask, self.beta)
+        return _arrays.to_caller(pos, kind), _arrays.to_caller(neg, kind)
+
+    def grad_d(self, y, x, d, mask):
+        kind, pos, neg = _grad_d(self._code, y, x, d, mask, self.beta)
+        return _arrays.to_caller(pos, kind), _arrays.to_caller(neg, kind)
+
+    def divergence(self, y, x, d, mask):
+        """sum M o d_beta(y | x d + 1e-15) over the entries with M != 0, a scalar of y's dtype
+        (``dcp_nmf_beta_divergence_*``: per element and accumulated in double precision).
+            d_0 = y/v - log(y/v) - 1,   d_1 = y log(y/v) - y + v  (0 log 0 = 0),
+            d_beta = (y^beta + (beta-1) v^beta - beta y v^(beta-1)) / (beta (beta-1))  otherwise."""
+        import ctypes
+        kind, yd, xd, dd, md = _device_args(y, x, d, mask)
+        N, F = yd.shape
+        K = dd.shape[0]
+        out = ctypes.c_double(0.0)
+        lib, h = _arrays.lib_handle(yd)
+        set_beta(h, self._code, self.beta)
+        fn = getattr(lib, 'dcp_nmf_beta_divergence_' + _arrays.suffix(yd))
+        _hip.check(h, fn(h, _arrays.ptr(yd), _arrays.ptr(md), _arrays.ptr(xd), _arrays.ptr(dd), N, F, K,
+                         ctypes.byref(out)), 'dcp_nmf_beta_divergence')
+        if kind == 'torch':
+            import torch
+            return torch.tensor(out.value, dtype=yd.dtype, device=yd.device)
+        return _arrays.np_dtype(yd).type(out.value)
+
+    def logp(self, y, x, d, mask):
+        """-divergence: the log likelihood up to the Tweedie constant (which does not depend on x, d)."""
+        return -self.divergence(y, x, d, mask)
+
+
+_LOOP_METHODS = ('grad_x', 'grad_d', 'update_x', 'update_d')
+
+
+def fused_spec(likelihood):
+    """(kernel code, beta) of a likelihood that ``nmf.solve`` may run as fused kernels, None otherwise: an
+    instance of Gaussian / Poisson / BetaDivergence -- or of a subclass that overrides none of the four methods
+    the MU loop calls (a subclass that only adds ``logp`` or bookkeeping keeps the fused path).  A
+    BetaDivergence with beta 2 or 1 runs the 'l2' / 'kl' kernels (the same math).  beta is None unless the code
+    is DCP_LIK_BETA."""
+    for base in (Gaussian, Poisson, BetaDivergence):
         if isinstance(likelihood, base):
             cls = type(likelihood)
-            if all(getattr(cls, n) is getattr(base, n) for n in ('grad_x', 'grad_d', 'update_x', 'update_d')):
-                return base._code
+            if not all(getattr(cls, n) is getattr(base, n) for n in _LOOP_METHODS):
+                return None
+            if base is not BetaDivergence:
+                return base._code, None
+            beta = likelihood.beta
+            if beta == 2.0:
+                return _hip.LIK_L2, None
+            if beta == 1.0:
+                return _hip.LIK_KL, None
+            return _hip.LIK_BETA, beta
     return None
 
 
+def fused_code(likelihood):
+    """The kernel code of ``fused_spec``, or None."""
+    spec = fused_spec(likelihood)
+    return None if spec is None else spec[0]
+
+
 def get_likelihood(likelihood):
-    """grads.py:7-14."""
+    """grads.py:7-14, plus 'is' / 'itakura-saito' = BetaDivergence(0)."""
     if likelihood in ['l2', 'gaussian']:
         return Gaussian()
     if likelihood in ['kl', 'poisson']:
         return Poisson()
+    if likelihood in ['is', 'itakura-saito']:
+        return BetaDivergence(0.0)
     if isinstance(likelihood, Likelihood):
         return likelihood
     raise NotImplementedError('Likelihood {} is not implemented for nmf'.format(likelihood))

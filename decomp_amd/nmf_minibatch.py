@@ -12,12 +12,14 @@ import ctypes
 import numpy as np
 
 from . import _arrays, _hip
+from .nmf_methods.grads import set_beta
 
 
 class _Kernels(object):
-    def __init__(self, D, lik):
+    def __init__(self, D, lik, beta=None):
         self.sfx = _arrays.suffix(D)
         self.lik = lik
+        self.beta = beta          # goes with lik == DCP_LIK_BETA
         self.K, self.F = D.shape
         self.lib, _ = _arrays.lib_handle(D)
         self.md = ctypes.c_double(0.0)
@@ -25,6 +27,7 @@ class _Kernels(object):
     def grads(self, y_mb, m_mb, x_mb, D, n_x_updates, gpos, gneg):
         lib, h = _arrays.lib_handle(D)
         fn = getattr(lib, 'dcp_nmf_grads_' + self.sfx)
+        set_beta(h, self.lik, self.beta)
         _hip.check(h, fn(h, _arrays.ptr(y_mb), _arrays.ptr(m_mb), _arrays.ptr(x_mb), _arrays.ptr(D),
                          y_mb.shape[0], self.F, self.K, self.lik, int(n_x_updates),
                          _arrays.ptr(gpos), _arrays.ptr(gneg)), 'dcp_nmf_grads')
@@ -68,6 +71,9 @@ class _UserKernels(_Kernels):
 
 
 def _kernels_for(D, lik, kind):
+    """lik: a kernel code, (DCP_LIK_BETA, beta), or a user Likelihood."""
+    if isinstance(lik, tuple):
+        return _Kernels(D, *lik)
     return _Kernels(D, lik) if isinstance(lik, int) else _UserKernels(D, lik, kind)
 
 

@@ -138,11 +138,14 @@ def comm_allreduce_(t):
     return t
 
 
-def mu_solve_in_library(y, mask, x, D, lik, tol, maxiter):
-    """``dcp_nmf_mu_sharded_*`` on this rank's rows (x and D updated in place).  Returns it."""
+def mu_solve_in_library(y, mask, x, D, lik, tol, maxiter, beta=None):
+    """``dcp_nmf_mu_sharded_*`` on this rank's rows (x and D updated in place).  Returns it.  ``beta`` goes
+    with lik == DCP_LIK_BETA."""
+    from .nmf_methods.grads import set_beta
     lib, h = _arrays.lib_handle(D)
     sfx = _arrays.suffix(D)
     fn = getattr(lib, 'dcp_nmf_mu_sharded_' + sfx)
+    set_beta(h, lik, beta)
     it = ctypes.c_int(0)
     ctol = ctypes.c_float(tol) if sfx == 'f32' else ctypes.c_double(tol)
     _hip.check(h, fn(h, _arrays.ptr(y), _arrays.ptr(mask), _arrays.ptr(x), _arrays.ptr(D), y.shape[0],
@@ -156,12 +159,13 @@ class HipStepBackend(object):
 
     x is double buffered: ``local_stats`` reads the current x and writes the next one, so
     the iteration that was enqueued speculatively (see ``mu_loop``) can be discarded with
-    ``rollback``.  ``x`` is always the buffer holding the current iterate."""
+    ``rollback``.  ``x`` is always the buffer holding the current iterate.  ``beta`` goes with
+    lik == DCP_LIK_BETA."""
 
-    def __init__(self, y, mask, x, D, lik):
+    def __init__(self, y, mask, x, D, lik, beta=None):
         import torch
         self.torch = torch
-        self.y, self.mask, self.lik = y, mask, lik
+        self.y, self.mask, self.lik, self.beta = y, mask, lik, beta
         self.x = x
         self._x_other = torch.empty_like(x)
         self.N, self.F = y.shape
@@ -187,7 +191,9 @@ class HipStepBackend(object):
             self._bits = bits if binary.value else None
 
     def local_stats(self, D):
+        from .nmf_methods.grads import set_beta
         lib, h = _arrays.lib_handle(D)
+        set_beta(h, self.lik, self.beta)
         if self.mask is not None:
             fn = getattr(lib, 'dcp_nmf_mu_stats_prepared_' + self.sfx)
             _hip.check(h, fn(h, _arrays.ptr(self._ym), _arrays.ptr(self.mask), _arrays.ptr(self._bits),
@@ -269,7 +275,7 @@ def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likeli
     assertion.assert_dtypes(y=y_local, D=D, x=x_local, mask=mask_local, dtypes='f')
     assertion.assert_shapes('y', y_local, 'D', D, axes=[-1])
     assertion.assert_shapes('y', y_local, 'mask', mask_local)
-    lik = _nmf._likelihood_code(likelihood)
+    lik, beta = _nmf._likelihood_spec(likelihood)
     y = _arrays.to_device(y_local)
     m = _arrays.to_device(mask_local)
     Dd = _arrays.to_device(D, copy=True)
@@ -282,12 +288,13 @@ def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likeli
     assertion.assert_nonnegative(x)
     if likelihood in ['kl']:
         assertion.assert_nonnegative(y)
+    _nmf._check_beta_data(likelihood, y, m)
     _arrays.l2_normalize_(Dd, strict=True)
     if world > 1 and attach_communicator(Dd, group):
         # the shipped multi-GPU path: the whole loop, collective included, behind the C ABI
-        it = mu_solve_in_library(y, m, x, Dd, lik, tol, maxiter)
+        it = mu_solve_in_library(y, m, x, Dd, lik, tol, maxiter, beta=beta)
         return it, Dd, x
-    backend = HipStepBackend(y, m, x, Dd, lik)
+    backend = HipStepBackend(y, m, x, Dd, lik, beta=beta)
     it, Dout = mu_loop(backend, Dd, tol, maxiter, group=group, world_size=world,
                        new_like=torch.empty_like)
     return it, Dout, backend.x

@@ -85,3 +85,26 @@ def assert_nonnegative_host_or_device(x):
         return
     assert x.dtype.kind != 'c'
     assert bool((x >= 0.0).all())
+
+
+def assert_positive(x):
+    """assertion.py:87-92: every element satisfies x > 0 (NaN fails).  NumPy arrays are scanned on the host,
+    torch tensors where they live (argument validation, not part of the compute path)."""
+    if x is None:
+        return
+    assert _arrays.np_dtype(x).kind != 'c'
+    assert bool((x > 0.0).all())
+
+
+def assert_positive_where(x, mask):
+    """x > 0 wherever mask != 0 (everywhere without a mask): the data of a beta <= 0 divergence, whose
+    missing entries are zero by the reference's convention (nmf.py:48).  NaN in x fails where mask != 0."""
+    if mask is None:
+        return assert_positive(x)
+    if _arrays.is_torch(x):
+        m = _arrays.to_device(mask, x.device.index) if not _arrays.is_torch(mask) else mask
+        assert bool(((x > 0.0) | (m == 0.0)).all())
+        return
+    if _arrays.is_torch(mask):
+        mask = mask.detach().cpu().numpy()
+    assert bool(((x > 0.0) | (mask == 0.0)).all())

@@ -42,8 +42,9 @@ enum {
     DCP_ERR_COMM = -7       /* librccl missing, no communicator on the handle, or an RCCL call failed */
 };
 
-/* likelihood codes: decomp/nmf_methods/grads.py:7-14 */
-enum { DCP_LIK_L2 = 0, DCP_LIK_KL = 1 };
+/* likelihood codes: decomp/nmf_methods/grads.py:7-14, and the beta-divergence family (Fevotte & Idier 2011;
+ * beta = 0 is Itakura-Saito).  DCP_LIK_BETA takes its beta from the handle (dcp_set_nmf_beta). */
+enum { DCP_LIK_L2 = 0, DCP_LIK_KL = 1, DCP_LIK_BETA = 2 };
 
 /* LASSO solver codes: decomp/lasso.py:13 */
 enum { DCP_LASSO_ISTA = 0, DCP_LASSO_ACC_ISTA = 1, DCP_LASSO_FISTA = 2, DCP_LASSO_CD = 3,
@@ -307,6 +308,23 @@ int dcp_nmf_gauss_logp_f32(dcp_handle* h, const float* Y, const float* mask, con
                            int64_t N, int64_t F, int64_t K, double scale, double* out);
 int dcp_nmf_gauss_logp_f64(dcp_handle* h, const double* Y, const double* mask, const double* X, const double* D,
                            int64_t N, int64_t F, int64_t K, double scale, double* out);
+/* beta of DCP_LIK_BETA on this handle (default 0, Itakura-Saito).  Handle state like the stream and
+ * dcp_set_f32_product_mode: read when a call that passes DCP_LIK_BETA is enqueued, so set it before each such
+ * call when several betas share a handle.  DCP_ERR_INVALID for a NULL handle or a non-finite beta.
+ * With DCP_LIK_BETA every NMF entry that takes `likelihood` runs the beta-divergence MU rule (Fevotte & Idier
+ * 2011, the reference's update_x / update_d applied to these parts), V = X D + 1e-15, M = mask or 1:
+ *   R1 = (Y o M) o V^(beta-2),  R2 = M o V^(beta-1)
+ *   x: pos = R1 D^T, neg = R2 D^T  [N, K]      D: pos = X^T R1, neg = X^T R2  [K, F]
+ * statistics width 2F ([X^T R1 | X^T R2]), mask or not.  No Gram identity applies. */
+int dcp_set_nmf_beta(dcp_handle* h, double beta);
+/* sum over entries with mask != 0 of mask * d_beta(Y | X D + 1e-15) with the handle's beta, to the HOST double
+ * (per-element divergence and accumulation in double, ordered second-stage sum: deterministic).  d_0 = y/v -
+ * log(y/v) - 1, d_1 = y log(y/v) - y + v (0 log 0 = 0), else (y^b + (b-1) v^b - b y v^(b-1)) / (b (b-1)).
+ * Valid for every beta.  Synchronises. */
+int dcp_nmf_beta_divergence_f32(dcp_handle* h, const float* Y, const float* mask, const float* X, const float* D,
+                                int64_t N, int64_t F, int64_t K, double* out);
+int dcp_nmf_beta_divergence_f64(dcp_handle* h, const double* Y, const double* mask, const double* X,
+                                const double* D, int64_t N, int64_t F, int64_t K, double* out);
 int dcp_nmf_apply_f32(dcp_handle* h, const float* D, const float* P, const float* Q, double alpha,
                       float* D_new, int64_t K, int64_t F, double* maxdiff);
 int dcp_nmf_apply_f64(dcp_handle* h, const double* D, const double* P, const double* Q, double alpha,
