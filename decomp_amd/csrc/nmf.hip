@@ -432,7 +432,7 @@ __global__ void __launch_bounds__(256) axpby_kernel(long n, T a, const T* x, T b
     // x and y may alias (no __restrict__).
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
         T v;
-        if (b == T(0)) v = a * x[i];
+        if (b == T(0)) v = (a == T(0)) ? T(0) : a * x[i];
         else if (a == T(0)) v = b * y[i];
         else v = a * x[i] + b * y[i];
         y[i] = v;

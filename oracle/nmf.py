@@ -6,6 +6,10 @@ Restates, in NumPy, the full-batch 'mu' path of the reference:
   decomp/nmf_methods/grads.py:77-93       multiplicative quotient
   decomp/nmf_methods/grads.py:108-125     Gaussian (l2) gradient parts
   decomp/nmf_methods/grads.py:143-160     Poisson (kl) gradient parts
+and the beta-divergence parts (Fevotte & Idier 2011) that the product's fused beta likelihood and
+tools/make_beta_golden.py put on the reference's Likelihood extension point:
+  R1 = (y o M) V^(beta-2),  R2 = M V^(beta-1),  V = x d + 1e-15
+  x: (R1 d^T, R2 d^T)        d: (x^T R1, x^T R2)
 The GEMM structure (f = x.D materialised, six products per iteration) is kept
 as in the reference so that fp64 results agree to rounding.
 """
@@ -13,8 +17,32 @@ import numpy as np
 from .common import JITTER, l2_strict
 
 
+def beta_of(likelihood):
+    """beta of a beta-divergence spec, else None.  A spec is 'is' / 'itakura-saito' (beta = 0), a number,
+    ('beta', b), or an object with a ``beta`` attribute (a BetaDivergence)."""
+    if isinstance(likelihood, str):
+        return 0.0 if likelihood in ('is', 'itakura-saito') else None
+    if isinstance(likelihood, tuple) and len(likelihood) == 2 and likelihood[0] == 'beta':
+        return float(likelihood[1])
+    if isinstance(likelihood, (int, float, np.floating)) and not isinstance(likelihood, bool):
+        return float(likelihood)
+    b = getattr(likelihood, 'beta', None)
+    return None if b is None else float(b)
+
+
+def _beta_parts(y, x, d, mask, beta):
+    V = x.dot(d) + JITTER
+    if mask is None:
+        return y * V ** (beta - 2.0), V ** (beta - 1.0)
+    return y * mask * V ** (beta - 2.0), mask * V ** (beta - 1.0)
+
+
 def _parts_x(y, x, d, mask, likelihood):
     """(positive, negative) parts of the x-gradient."""
+    beta = beta_of(likelihood)
+    if beta is not None:
+        r1, r2 = _beta_parts(y, x, d, mask, beta)
+        return r1.dot(d.T), r2.dot(d.T)
     if likelihood == 'l2':            # grads.py:108-115
         f = x.dot(d)
         if mask is not None:
@@ -30,6 +58,10 @@ def _parts_x(y, x, d, mask, likelihood):
 
 def _parts_d(y, x, d, mask, likelihood):
     """(positive, negative) parts of the D-gradient."""
+    beta = beta_of(likelihood)
+    if beta is not None:
+        r1, r2 = _beta_parts(y, x, d, mask, beta)
+        return x.T.dot(r1), x.T.dot(r2)
     if likelihood == 'l2':            # grads.py:117-125
         f = x.dot(d)
         if mask is not None:
@@ -89,6 +121,7 @@ def solve(y, D, x=None, tol=1.0e-3, maxiter=1000, likelihood='l2', mask=None,
     """nmf.py:52-78 + batch_mu.py:8-26 (validation lives in the product's host
     layer, not here).  ``trace`` (a list) receives one dict per iteration with
     'maxdiff' and 'resid' (residual after the iteration's x and normalised D).
+    ``likelihood``: 'l2' / 'gaussian', 'kl' / 'poisson', or a beta spec (beta_of).
     Returns (it, D, x) with the reference's conventions: ``range(1, maxiter)``
     iterations, (it, D_new, x) on convergence, (maxiter, D, x) on exhaustion.
     """

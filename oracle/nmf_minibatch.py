@@ -4,6 +4,8 @@ Restates, in NumPy, the reference's
   decomp/nmf_methods/serizel.py:36-165  asg / gsg / asag / gsag-MU (Serizel et al.)
   decomp/nmf_methods/kasai.py:36-88     SVRMU / SVRMU-ACC (Kasai)
 on the minibatch containers of decomp/utils/data.py (oracle.common.RowBatches).
+``likelihood`` is anything oracle.nmf._parts_x takes ('l2', 'kl' or a beta spec).  ``trace`` (a list,
+optional) receives max|D - D_new| of every D update in order, the one that stops the run included.
 """
 import numpy as np
 
@@ -21,8 +23,15 @@ def _x_step(y_mb, x_mb, D, m_mb, lik):
     x_mb[:] = _quotient(x_mb, *_parts_x(y_mb, x_mb, D, m_mb, lik))
 
 
+def _diff(D, D_new, trace):
+    diff = np.max(np.abs(D - D_new))
+    if trace is not None:
+        trace.append(float(diff))
+    return diff
+
+
 def solve_serizel(y, D, x, tol, minibatch, maxiter, method, likelihood, mask, random_seed,
-                  forget_rate=0.5):
+                  forget_rate=0.5, trace=None):
     """serizel.py:9-165.  QUIRKS: 'gsg-mu' runs the asg algorithm (:23-25); on convergence
     the old D is returned (:58-59, :122-123, :160-161)."""
     rng = np.random.RandomState(random_seed)
@@ -46,19 +55,19 @@ def solve_serizel(y, D, x, tol, minibatch, maxiter, method, likelihood, mask, ra
                 P, Q = spos, sneg
             if per_mb:
                 D_new = l2_strict(_quotient(D, P, Q))
-                if np.max(np.abs(D - D_new)) < tol:
+                if _diff(D, D_new, trace) < tol:
                     return it, D, xb.array
                 D = D_new
         if not per_mb:
             D_new = l2_strict(_quotient(D, spos, sneg))
-            if np.max(np.abs(D - D_new)) < tol:
+            if _diff(D, D_new, trace) < tol:
                 return it, D, xb.array
             D = D_new
     return maxiter, D, xb.array
 
 
 def solve_kasai(y, D, x, tol, minibatch, maxiter, method, likelihood, mask, random_seed,
-                alpha=1.0, beta=0.5):
+                alpha=1.0, beta=0.5, trace=None):
     """kasai.py:10-88."""
     rng = np.random.RandomState(random_seed)
     D = l2_strict(D)
@@ -66,8 +75,7 @@ def solve_kasai(y, D, x, tol, minibatch, maxiter, method, likelihood, mask, rand
         iters = 1
     else:                                              # :24-28 (F, K = D.shape as written)
         F, K = D.shape
-        N = x.shape[0]
-        iters = int(np.maximum(beta * F * (3 * K + 2 * N) / (3 * F * N + 2 * K), 1.0))
+        iters = svrmu_acc_iters(F, K, x.shape[0], beta)
     yb, xb, mb = _containers(y, x, mask, minibatch)
     index = np.arange(len(y))
     rng.shuffle(index)                                 # shuffled once (:42-46)
@@ -91,12 +99,18 @@ def solve_kasai(y, D, x, tol, minibatch, maxiter, method, likelihood, mask, rand
             Q = gn + prev_pos[k] + full_neg
             D_new = D * ((1.0 - alpha) + alpha * P / np.maximum(Q, JITTER))
             D_new = l2_strict(np.maximum(D_new, 0.0))
-            if np.max(np.abs(D - D_new)) < tol:
+            if _diff(D, D_new, trace) < tol:
                 return it, D, xb.array
             D = D_new
             prev_pos[k] = gp
             prev_neg[k] = gn
     return maxiter, D, xb.array
+
+
+def svrmu_acc_iters(F, K, N, beta=0.5):
+    """kasai.py:24-28 as written: x updates per minibatch of 'svrmu-acc' (the caller passes D.shape as
+    (F, K), so F is the atom count and K the feature count)."""
+    return int(np.maximum(beta * F * (3 * K + 2 * N) / (3 * F * N + 2 * K), 1.0))
 
 
 def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='asg-mu',

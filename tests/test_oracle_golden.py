@@ -279,3 +279,73 @@ def test_dictionary_minibatch_step_equals_solve():
                 assert np.array_equal(A, t['A']) and np.array_equal(B, t['B']) and np.array_equal(D, t['D'])
                 assert diff == t['maxdiff']
                 count += 1
+
+
+# ------------------------------------------------- beta-divergence MU NMF -----
+def test_nmf_beta_batch_and_minibatch_cases(golden_dir):
+    """The oracle's beta parts reproduce the reference runs of nmf_beta_golden.npz: the batch MU cases
+    (every beta, with and without a mask, 24 iterations) and the minibatch asg-mu / svrmu cases (beta = 0,
+    16-row minibatches, 5 epochs).  The oracle runs in the fixture's dtype, as the reference did."""
+    from oracle import nmf_minibatch as omb
+
+    class Beta(object):      # an object spec, as decomp_amd's BetaDivergence
+        def __init__(self, beta):
+            self.beta = beta
+    g = _load(golden_dir, 'nmf_beta_golden.npz')
+    n = 0
+    for si in (0, 1):
+        for dt in ('float32', 'float64'):
+            y, ym, D0, mask = (g['in/%d/%s/%s' % (si, dt, k)] for k in ('y', 'ym', 'D0', 'mask'))
+            tol = _tol(dt)
+            for beta in (0.0, 0.5, 1.5, 3.0):
+                for masked in (0, 1):
+                    yy, mm = (ym, mask) if masked else (y, None)
+                    spec = 'is' if beta == 0.0 and masked else (Beta(beta) if si else beta)
+                    it, D, x = onmf.solve(yy.copy(), D0.copy(), tol=0.0, maxiter=25, likelihood=spec,
+                                          mask=None if mm is None else mm.copy())
+                    key = 'mu/%d/%s/%s/%d/' % (si, dt, beta, masked)
+                    assert it == 25 and D.dtype == np.dtype(dt), key
+                    assert _close(D, g[key + 'D'], tol), key
+                    assert _close(x, g[key + 'x'], tol), key
+                    n += 1
+    for dt in ('float32', 'float64'):
+        y, D0 = g['in/0/%s/y' % dt], g['in/0/%s/D0' % dt]
+        for method in ('asg-mu', 'svrmu'):
+            trace = []
+            it, D, x = omb.solve(y.copy(), D0.copy(), tol=0.0, minibatch=16, maxiter=6, method=method,
+                                 likelihood='itakura-saito', random_seed=3, trace=trace)
+            key = 'mb/%s/%s/' % (method, dt)
+            assert it == int(g[key + 'it']), key
+            assert _close(D, g[key + 'D'], _tol(dt)), key
+            assert _close(x, g[key + 'x'], _tol(dt)), key
+            assert len(trace) == 5 * (64 // 16) and all(t > 0 for t in trace), key
+            n += 1
+    assert n == 36
+
+
+def test_nmf_minibatch_trace_and_beta_spec():
+    """trace holds max|D - D_new| of every update, the stopping one included; beta 2 / 1 specs give the l2 /
+    kl parts (the latter up to the [1, K] broadcast of the unmasked x negative part)."""
+    from oracle import nmf_minibatch as omb
+    rng = np.random.RandomState(2)
+    y, D0 = rng.uniform(0.1, 1.0, (90, 12)), rng.uniform(0.1, 1.0, (3, 12))
+    for method in ('asg-mu', 'gsag-mu', 'svrmu'):
+        full = []
+        omb.solve(y.copy(), D0.copy(), tol=0.0, minibatch=30, maxiter=4, method=method, random_seed=1,
+                  trace=full)
+        assert len(full) == (3 if method == 'gsag-mu' else 9)
+        tol = 0.5 * (full[4] + full[5]) if method != 'gsag-mu' else 0.5 * (full[1] + full[2])
+        stop = [i for i, t in enumerate(full) if t < tol][0]
+        cut = []
+        it, _, _ = omb.solve(y.copy(), D0.copy(), tol=tol, minibatch=30, maxiter=4, method=method,
+                             random_seed=1, trace=cut)
+        assert cut == full[:stop + 1]
+        assert it == (stop // 3 + 1 if method != 'gsag-mu' else stop + 1)
+    x, D = rng.uniform(0.1, 1.0, (90, 3)), D0
+    for spec, name in ((2.0, 'l2'), (1.0, 'kl')):
+        for mask in (None, (rng.uniform(size=y.shape) > 0.3).astype(float)):
+            for parts in (onmf._parts_x, onmf._parts_d):
+                a, b = parts(y, x, D, mask, spec)
+                c, d = parts(y, x, D, mask, name)
+                assert np.allclose(a, c, rtol=1e-12, atol=0)
+                assert np.allclose(b, np.broadcast_to(d, b.shape), rtol=1e-12, atol=0)
