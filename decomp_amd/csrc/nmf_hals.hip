@@ -1,0 +1,231 @@
+// C ABI: NMF by HALS (exact block coordinate descent, squared loss, no mask) and the non-negative
+// coordinate sweep on its own.  Contract in include/decomp_hip.h; the kernels in nmf_hals.hpp.
+#include <cmath>
+
+#include "nmf_hals.hpp"
+#include "nmf_impl.hpp"
+
+using namespace dcp;
+
+namespace {
+
+template <class T>
+int check_hals_args(dcp_handle* h, const T* Y, const T* X, const T* D, int64_t N, int64_t F, int64_t K) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!Y || !X || !D) return fail(h, DCP_ERR_INVALID, "null array pointer");
+    if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
+    if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL || F + K > 0x3fffffffLL)
+        return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
+    return DCP_OK;
+}
+
+int sweep_rc(dcp_handle* h, hipError_t e) {
+    if (e != hipSuccess) return fail(h, DCP_ERR_HIP, std::string("launch failed: ") + hipGetErrorString(e));
+    return DCP_OK;
+}
+
+// One HALS iteration's products and sweeps from (Xc, Dc) into (Xn, U):
+//   G = Dc Dc^T, C = Y Dc^T           (w.G, w.Q)
+//   Xn = sweep(Xc, C, G)              vector-major, N vectors
+//   stats = [Xn^T Y | Xn^T Xn]        the statistics product of the MU loop (nmf_stats, D-side phase)
+//   U = sweep(Dc, (Xn^T Y)^T, Xn^T Xn)   coordinate-major, F vectors (the columns of D)
+template <class T>
+int hals_products_and_sweeps(dcp_handle* h, const T* Y, const T* Xc, T* Xn, const T* Dc, T* U,
+                             const NmfShape<T>& s, T* stats, NmfStatsWs<T>& w) {
+    hipStream_t st = h->stream;
+    const int N = (int)s.N, F = (int)s.F, K = (int)s.K;
+    const long W = F + K;
+    {   // G = D D^T (split over F, partial slabs summed in order), as the MU loop's Gram product
+        ProfScope ps(h, DCP_PROF_GRAM);
+        GemmArgs<T> g;
+        g.A = Dc; g.lda = F; g.B = Dc; g.ldb = F; g.M = K; g.N = K; g.K = F;
+        if (!std::is_same<T, float>::value) g.tile = TILE_SMALL_DEEP;
+        plan_splits<FORM_NT>(g, 512, kMaxSplits, 16);
+        DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, g, EpiSlab<T>{w.slabs, K, (long)K * K})));
+        hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, st, w.slabs,
+                           (long)K * K, g.ksplits, (long)K * K, w.G);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+    }
+    {   // C = Y D^T, then the x sweep
+        ProfScope ps(h, DCP_PROF_XUPDATE);
+        GemmArgs<T> pg;
+        pg.A = Y; pg.lda = F; pg.B = Dc; pg.ldb = F; pg.M = N; pg.N = K; pg.K = F;
+        const int psplits = nmf_xupdate_splits<T>(s.N, s.F, s.K, pg);
+        if (psplits <= 1) {
+            pg.ksplits = 1;
+            DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiStore<T>{w.Q, K}, true)));
+        } else {   // few rows: split the F reduction so that all CUs work, slabs summed in order
+            if ((size_t)pg.ksplits * N * K > w.slab_count)
+                return fail(h, DCP_ERR_INTERNAL, "hals Y.D^T slab plan mismatch");
+            DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiSlab<T>{w.slabs, K, (long)N * K}, true)));
+            launch_reduce_slabs<T>(st, w.slabs, (long)N * K, pg.ksplits, (long)N * K, w.Q);
+            DCP_LAUNCH_OK(h, hipGetLastError());
+        }
+        DCP_TRY(sweep_rc(h, launch_nn_cd_sweep<T, false>(st, Xc, Xn, K, w.Q, K, w.G, K, N, K)));
+    }
+    DCP_TRY(nmf_stats<T>(h, Y, nullptr, Xn, Xn, Dc, s, stats, w, 2));
+    {
+        ProfScope ps(h, DCP_PROF_DUPDATE);
+        DCP_TRY(sweep_rc(h, launch_nn_cd_sweep<T, true>(st, Dc, U, F, stats, W, stats + F, W, F, K)));
+    }
+    return DCP_OK;
+}
+
+template <class T>
+int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, int64_t K, T tol, int maxiter,
+                   int* it_out, T* last_maxdiff, T* resid_trace) {
+    DCP_TRY(check_hals_args(h, Y, X, D, N, F, K));
+    if (!it_out) return fail(h, DCP_ERR_INVALID, "it_out is null");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    NmfShape<T> s{N, F, K, DCP_LIK_L2, false};
+    const int64_t W = F + K;
+    const bool want_resid = resid_trace != nullptr;
+    const int resid_blocks = 1024;
+
+    WsPlan plan;
+    nmf_plan_stats(plan, s, false);
+    plan.add<T>((size_t)K * W);   // stats
+    plan.add<T>((size_t)K * F);   // U: the swept, not yet normalised D
+    plan.add<T>((size_t)K * F);   // second D buffer
+    plan.add<T>((size_t)N * K);   // second x buffer
+    plan.add<T>((size_t)K);       // atom norms
+    plan.add<T>(2);               // max|dD| of the two iterations in flight
+    plan.add<unsigned int>(4);    // arrival ticket of the normalisation's workgroups
+    if (want_resid) {
+        plan.add<T>((size_t)N * F);
+        plan.add<double>(resid_blocks);
+    }
+    DCP_TRY(ws_reserve(h, plan.total));
+    ws_reset(h);
+    NmfStatsWs<T> ws;
+    DCP_TRY(nmf_carve_stats(h, ws, s, false));
+    T* stats = ws_alloc<T>(h, (size_t)K * W);
+    T* U = ws_alloc<T>(h, (size_t)K * F);
+    T* D2 = ws_alloc<T>(h, (size_t)K * F);
+    T* X2 = ws_alloc<T>(h, (size_t)N * K);
+    T* nrm = ws_alloc<T>(h, (size_t)K);
+    T* maxdiff_dev = ws_alloc<T>(h, 2);
+    unsigned int* ticket = ws_alloc<unsigned int>(h, 4);
+    T* resid_tmp = nullptr;
+    double* resid_part = nullptr;
+    if (want_resid) {
+        resid_tmp = ws_alloc<T>(h, (size_t)N * F);
+        resid_part = ws_alloc<double>(h, resid_blocks);
+    }
+    if (!stats || !U || !D2 || !X2 || !nrm || !maxdiff_dev || !ticket || (want_resid && (!resid_tmp || !resid_part)))
+        return fail(h, DCP_ERR_INTERNAL, "hals workspace plan mismatch");
+    void* hostv = nullptr;
+    DCP_TRY(host_scratch(h, sizeof(double) * (resid_blocks + 4), &hostv));
+    T* host_md = reinterpret_cast<T*>(hostv);             // [2]
+    double* host_part = reinterpret_cast<double*>(hostv) + 2;
+    // the stop test polls the pinned word the normalisation's last workgroup stores max|dD| into (the MU loop's
+    // protocol: a sentinel of -1 is put there before the iteration is enqueued; max|dD| >= 0 or NaN)
+    auto wait_md = [&](int slot, T* out) -> int {
+        volatile T* v = host_md + slot;
+        bool seen = false;
+        for (long spin = 0; spin < 400000000L; ++spin) {
+            if (!(*v == T(-1))) { seen = true; break; }
+            __builtin_ia32_pause();
+        }
+        if (!seen) DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
+        *out = *v;
+        return DCP_OK;
+    };
+    DCP_HIP_OK(h, hipMemsetAsync(maxdiff_dev, 0, 2 * sizeof(T), h->stream));
+    DCP_HIP_OK(h, hipMemsetAsync(ticket, 0, 4 * sizeof(unsigned int), h->stream));
+
+    // Iteration `it` reads (x_{it-1}, D_{it-1}) from (Xc, Dc) and writes (x_it, D_it) to (Xn, Dn); the stop test
+    // of iteration it-1 is evaluated after iteration it has been enqueued, and iteration it is discarded when
+    // it-1 has converged -- exactly the MU loop (nmf.hip, nmf_mu_solve).
+    T* Xc = X;  T* Xn = X2;
+    T* Dc = D;  T* Dn = D2;
+    int result_it = maxiter;
+    T md_last = T(0);
+    bool converged = false;
+    for (int it = 1; it < maxiter; ++it) {
+        const int slot = it & 1;
+        DCP_TRY(hals_products_and_sweeps<T>(h, Y, Xc, Xn, Dc, U, s, stats, ws));
+        *reinterpret_cast<volatile T*>(host_md + slot) = T(-1);
+        {
+            ProfScope ps(h, DCP_PROF_DNORM);
+            hipLaunchKernelGGL((hals_normalize_kernel<T>), dim3((unsigned)K), dim3(256), 0, h->stream, (const T*)U,
+                               (long)F, (const T*)Dc, Dn, nrm, maxdiff_dev + slot, maxdiff_dev + (slot ^ 1), ticket,
+                               host_md + slot);
+            DCP_LAUNCH_OK(h, hipGetLastError());
+            hipLaunchKernelGGL((hals_rescale_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, h->stream, Xn,
+                               (long)N * K, (int)K, (const T*)nrm);
+            DCP_LAUNCH_OK(h, hipGetLastError());
+        }
+        if (want_resid) {   // parity/debug mode: synchronous
+            DCP_TRY(nmf_residual<T>(h, Y, nullptr, Xn, Dn, N, F, K, resid_tmp, resid_part, resid_blocks));
+            DCP_HIP_OK(h, hipMemcpyAsync(host_part, resid_part, sizeof(double) * resid_blocks,
+                                         hipMemcpyDeviceToHost, h->stream));
+            DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
+            double acc = 0.0;
+            for (int i = 0; i < resid_blocks; ++i) acc += host_part[i];
+            resid_trace[it - 1] = (T)sqrt(acc);
+        }
+        if (it > 1) {   // stop test of the PREVIOUS iteration
+            DCP_TRY(wait_md(slot ^ 1, &md_last));
+            if (md_last < tol) {   // a NaN compares false
+                result_it = it - 1;
+                converged = true;
+                break;
+            }
+        }
+        T* t = Xc; Xc = Xn; Xn = t;
+        t = Dc; Dc = Dn; Dn = t;
+    }
+    if (!converged && maxiter > 1) {
+        const int slot = (maxiter - 1) & 1;
+        DCP_TRY(wait_md(slot, &md_last));
+        if (md_last < tol) result_it = maxiter - 1;
+    }
+    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));   // drain (incl. a discarded iteration)
+    if (Xc != X)
+        DCP_HIP_OK(h, hipMemcpyAsync(X, Xc, sizeof(T) * (size_t)N * K, hipMemcpyDeviceToDevice, h->stream));
+    if (Dc != D)
+        DCP_HIP_OK(h, hipMemcpyAsync(D, Dc, sizeof(T) * (size_t)K * F, hipMemcpyDeviceToDevice, h->stream));
+    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
+    *it_out = result_it;
+    if (last_maxdiff) *last_maxdiff = md_last;
+    return DCP_OK;
+}
+
+template <class T>
+int nn_cd_sweep_api(dcp_handle* h, const T* V_in, T* V_out, const T* C, const T* G, int64_t R, int64_t K,
+                    int coord_major) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!V_in || !V_out || !C || !G) return fail(h, DCP_ERR_INVALID, "null array pointer");
+    if (R <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
+    if (R > 0x7fffffffLL || K > 0x7fffffffLL) return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    if (coord_major)
+        return sweep_rc(h, launch_nn_cd_sweep<T, true>(h->stream, V_in, V_out, (long)R, C, (long)R, G, (long)K,
+                                                          (int)R, (int)K));
+    return sweep_rc(h, launch_nn_cd_sweep<T, false>(h->stream, V_in, V_out, (long)K, C, (long)K, G, (long)K,
+                                                       (int)R, (int)K));
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcp_nmf_hals_f32(dcp_handle* h, const float* Y, float* X, float* D, int64_t N, int64_t F, int64_t K, float tol,
+                     int maxiter, int* it_out, float* last_maxdiff, float* resid_trace) {
+    return nmf_hals_solve<float>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, resid_trace);
+}
+int dcp_nmf_hals_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
+                     double tol, int maxiter, int* it_out, double* last_maxdiff, double* resid_trace) {
+    return nmf_hals_solve<double>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, resid_trace);
+}
+int dcp_nn_cd_sweep_f32(dcp_handle* h, const float* V_in, float* V_out, const float* C, const float* G, int64_t R,
+                        int64_t K, int coord_major) {
+    return nn_cd_sweep_api<float>(h, V_in, V_out, C, G, R, K, coord_major);
+}
+int dcp_nn_cd_sweep_f64(dcp_handle* h, const double* V_in, double* V_out, const double* C, const double* G,
+                        int64_t R, int64_t K, int coord_major) {
+    return nn_cd_sweep_api<double>(h, V_in, V_out, C, G, R, K, coord_major);
+}
+
+}  // extern "C"

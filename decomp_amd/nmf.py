@@ -3,7 +3,9 @@
 Same entry point, argument meaning, return convention and error behaviour as the
 reference's decomp/nmf.py:16-113: the full-batch multiplicative update
 (``minibatch=None, method='mu'``) and the stochastic minibatch variants
-(decomp_amd/nmf_minibatch.py).  The full-batch iteration itself
+(decomp_amd/nmf_minibatch.py).  Beyond the reference: ``method='hals'`` (l2, no mask,
+full batch), exact block coordinate descent in libdecomp_hip.so (``dcp_nmf_hals_*``,
+decomp_amd/csrc/nmf_hals.hpp).  The full-batch MU iteration itself
 (decomp/nmf_methods/batch_mu.py:8-26 with the update rules of
 decomp/nmf_methods/grads.py:77-160) runs in libdecomp_hip.so: see
 include/decomp_hip.h ``dcp_nmf_mu_*`` and decomp_amd/csrc/nmf_impl.hpp.
@@ -86,7 +88,9 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
           likelihood='l2', mask=None, random_seed=None, **kwargs):
     """
     Non-negative matrix factorisation  argmin_{x, D} |y - xD|^2,  x >= 0, D >= 0,
-    |D_j| = 1, by multiplicative updates.
+    |D_j| = 1, by multiplicative updates (method='mu'), or, for the l2 likelihood without a
+    mask, by HALS (method='hals': exact block coordinate descent on the columns of x and the
+    atoms of D, then the atoms rescaled to unit norm with x rescaled so that xD is unchanged).
 
     y: [n_samples, n_channels], x: [n_samples, n_features], D: [n_features, n_channels],
     mask (optional): [n_samples, n_channels], 0 marks a missing entry; float32 or
@@ -158,6 +162,15 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
                 y_dev = _arrays.to_device(y, dev)
             m_dev = _arrays.to_device(mask, dev)
             it = _run_mu(y_dev, m_dev, x_dev, D_dev, lik, tol, maxiter, beta=beta)
+            return it, _arrays.to_caller(D_dev, kind), _arrays.to_caller(x_dev, kind)
+        if method == 'hals':
+            if kwargs:
+                raise TypeError('solve() got an unexpected keyword argument %r'
+                                % sorted(kwargs)[0])
+            _check_hals_scope(likelihood, mask)
+            if y_dev is None:
+                y_dev = _arrays.to_device(y, dev)
+            it = _run_hals(y_dev, x_dev, D_dev, tol, maxiter)
             return it, _arrays.to_caller(D_dev, kind), _arrays.to_caller(x_dev, kind)
         raise NotImplementedError('Batch-NMF with {} algorithm is not yet '
                                   'implemented.'.format(method))
@@ -248,6 +261,39 @@ def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None, beta=None):
             N, F, K, lik, ctype(tol), int(maxiter), ctypes.byref(it), ctypes.byref(last),
             trace)
     _hip.check(h, rc, 'dcp_nmf_mu_' + sfx)
+    if resid_trace is not None:
+        n_done = it.value if it.value < maxiter else maxiter - 1
+        resid_trace.extend(float(trace[i]) for i in range(max(n_done, 0)))
+    return it.value
+
+
+def _check_hals_scope(likelihood, mask):
+    """What method='hals' covers: the squared loss without a mask.  Raises NotImplementedError otherwise."""
+    if mask is not None:
+        raise NotImplementedError('NMF with the hals algorithm does not support a mask '
+                                  '(use method=\'mu\')')
+    if not (isinstance(likelihood, str) and likelihood in ('l2', 'gaussian')):
+        raise NotImplementedError('NMF with the hals algorithm supports only the l2 likelihood, '
+                                  'not {} (use method=\'mu\')'.format(likelihood))
+
+
+def _run_hals(y, x, D, tol, maxiter, resid_trace=None):
+    """HALS (exact block coordinate descent) on device arrays, D l2_strict normalised; x and D are updated
+    in place.  Same stop rule and return convention as ``_run_mu``.  Returns it."""
+    lib, h = _arrays.lib_handle(D)
+    sfx = _arrays.suffix(D)
+    N, F = y.shape
+    K = D.shape[0]
+    ctype = ctypes.c_float if sfx == 'f32' else ctypes.c_double
+    it = ctypes.c_int(0)
+    last = ctype(0)
+    trace = None
+    if resid_trace is not None:
+        trace = (ctype * max(int(maxiter), 1))()
+    fn = getattr(lib, 'dcp_nmf_hals_' + sfx)
+    rc = fn(h, _arrays.ptr(y), _arrays.ptr(x), _arrays.ptr(D), N, F, K, ctype(tol), int(maxiter),
+            ctypes.byref(it), ctypes.byref(last), trace)
+    _hip.check(h, rc, 'dcp_nmf_hals_' + sfx)
     if resid_trace is not None:
         n_done = it.value if it.value < maxiter else maxiter - 1
         resid_trace.extend(float(trace[i]) for i in range(max(n_done, 0)))

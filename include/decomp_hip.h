@@ -213,6 +213,29 @@ int dcp_nmf_mu_f64(dcp_handle* h, const double* Y, const double* mask, double* X
                    int64_t N, int64_t F, int64_t K, int likelihood, double tol, int maxiter,
                    int* it_out, double* last_maxdiff, double* resid_trace);
 
+/* ---- NMF, HALS (exact block coordinate descent, squared loss, no mask) ------------- */
+/* One iteration from (X, D), D with unit-norm rows:
+ *   X <- sweep(X, Y D^T, D D^T)                      (N vectors, the rows of X)
+ *   D^T <- sweep(D^T, (X^T Y)^T, X^T X)              (F vectors, the columns of D; with the new X)
+ *   n_k = ||D_k||_2; where n_k > 0: D_k /= n_k, X[:,k] *= n_k (X D unchanged); where n_k = 0 both stay
+ * with sweep() as dcp_nn_cd_sweep_*.  The stop rule, the return convention, last_maxdiff and resid_trace are
+ * those of dcp_nmf_mu_*: (it, D_new, X) at the first iteration with max|D - D_new| < tol, else (maxiter, D, X)
+ * after maxiter-1 iterations; the test of iteration it-1 is made while iteration it runs, with no host round
+ * trip per iteration.  float: Y D^T and X^T [Y | X] follow dcp_set_f32_product_mode. */
+int dcp_nmf_hals_f32(dcp_handle* h, const float* Y, float* X, float* D, int64_t N, int64_t F, int64_t K,
+                     float tol, int maxiter, int* it_out, float* last_maxdiff, float* resid_trace);
+int dcp_nmf_hals_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
+                     double tol, int maxiter, int* it_out, double* last_maxdiff, double* resid_trace);
+/* The non-negative coordinate sweep of HALS on R independent vectors: for k = 0 .. K-1 in order, with the
+ * current V (coordinates < k already updated),
+ *   if G[k,k] > 0:  V[:,k] = max(0, V[:,k] - (V G[:,k] - C[:,k]) / G[k,k])      (else V[:,k] unchanged)
+ * G [K, K] symmetric, row-major.  coord_major == 0: V and C are [R, K] (vector r is row r); != 0: they are
+ * [K, R] (vector r is column r).  Reads V_in, writes V_out (they may be the same array).  Deterministic. */
+int dcp_nn_cd_sweep_f32(dcp_handle* h, const float* V_in, float* V_out, const float* C, const float* G,
+                        int64_t R, int64_t K, int coord_major);
+int dcp_nn_cd_sweep_f64(dcp_handle* h, const double* V_in, double* V_out, const double* C, const double* G,
+                        int64_t R, int64_t K, int coord_major);
+
 /* The same loop for a problem whose ROWS are sharded over the ranks of the handle's communicator
  * (dcp_comm_init): Y, mask, X are this rank's rows, D is replicated.  Every iteration runs
  *   local x update + [x^T Y | x^T x] (or [num | den]) on this rank's rows
