@@ -62,8 +62,11 @@ def _mean_over_batch(m):
 
 
 # ---------------------------------------------- proximal-gradient family ----
-def _prox_grad(y, A, alpha, x0, tol, maxiter, positive, mask, momentum):
+def _prox_grad(y, A, alpha, x0, tol, maxiter, positive, mask, momentum,
+               trace=None):
     """ista / acc_ista / fista with or without a full (batch-shaped) mask.
+    ``trace`` (a list) receives, at every check iteration, the array
+    |x_new - x_prev| - tol whose max the stop test compares with zero.
 
     lasso.py:274-297, 306-328 (ista) ; 331-357, 360-385 (acc_ista) ;
     388-415, 418-445 (fista).
@@ -98,6 +101,8 @@ def _prox_grad(y, A, alpha, x0, tol, maxiter, positive, mask, momentum):
         if momentum == 'acc_ista':
             c = rdt.type(i / (i + 3))
             v = x_new + c * (x_new - x_prev)                   # :353
+        if i % 10 == 0 and trace is not None:
+            trace.append(np.abs(x_new - x_prev) - tol)
         if i % 10 == 0 and np.max(np.abs(x_new - x_prev) - tol) < 0.0:
             return i, x_new                                    # :293-294
         if momentum == 'ista':
@@ -229,8 +234,10 @@ def _admm(y, A, alpha, x, tol, maxiter, positive, mask, rho=1.0):
 
 
 # --------------------------------------------------------- fast path -------
-def solve_fastpath(y, A, alpha, x, tol, maxiter, method, mask=None):
-    """lasso.py:97-189."""
+def solve_fastpath(y, A, alpha, x, tol, maxiter, method, mask=None,
+                   trace=None):
+    """lasso.py:97-189.  ``trace``: see _prox_grad (proximal-gradient
+    methods only; the stop test is in the scaled variables x' = x |A_k|)."""
     positive = method.endswith('_pos')
     if positive:
         method = method[:-4]
@@ -265,7 +272,7 @@ def solve_fastpath(y, A, alpha, x, tol, maxiter, method, mask=None):
         it, x = _admm(y, A, alpha, x, tol, maxiter, positive, full_mask)
     else:
         it, x = _prox_grad(y, A, alpha, x, tol, maxiter, positive, full_mask,
-                           method)
+                           method, trace=trace)
     return it, x / s                                           # :189
 
 

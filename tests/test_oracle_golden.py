@@ -349,3 +349,65 @@ def test_nmf_minibatch_trace_and_beta_spec():
                 c, d = parts(y, x, D, mask, name)
                 assert np.allclose(a, c, rtol=1e-12, atol=0)
                 assert np.allclose(b, np.broadcast_to(d, b.shape), rtol=1e-12, atol=0)
+
+
+# --------------------------------------------------------- template matching ----
+def test_template_matching_solve_fixtures(golden_dir):
+    """oracle.template_matching.solve reproduces every solve case recorded from the reference: the batch
+    and minibatch loops, every LASSO method the fixtures hold (the dense ones and '_pos' included)."""
+    from oracle import template_matching as otm
+    g = _load(golden_dir, 'template_golden.npz')
+    n = 0
+    for name in g['solve_keys']:
+        name = str(name)
+        padding, stride, _, mb, method, maxiter, liter, tol, seed = [str(a) for a in g[name + '_args']]
+        mb = None if mb == 'None' else int(mb)
+        tol = float(tol)
+        y, D0 = g[name + '_y'], g[name + '_D0']
+        it, D, x = otm.solve(y.copy(), D0.copy(), 0.1, stride=int(stride), padding=padding, tol=tol,
+                             minibatch=mb, size_of_minibatch=30 if mb else None, maxiter=int(maxiter),
+                             lasso_method=method, lasso_iter=int(liter), random_seed=int(seed))
+        it_ref, D_ref, x_ref = int(g[name + '_it']), g[name + '_D'], g[name + '_x']
+        assert x.shape == x_ref.shape and D.shape == D_ref.shape, name
+        n += 1
+        if y.dtype in (np.float32, np.complex64):
+            # the bound and the knife-edge rule of tests/test_gpu_template.py::test_solve_fixtures
+            trace = g[name + '_trace']
+            if it != it_ref:
+                assert tol > 0 and bool(np.any(np.abs(trace - tol) < 1e-2 * tol)), (name, it, it_ref)
+                continue
+            lim = 2e-4
+        else:
+            assert it == it_ref, (name, it, it_ref)
+            lim = 1e-8
+        for a, b in ((D, D_ref), (x, x_ref)):
+            err = float(np.max(np.abs(a - b))) / max(1e-30, float(np.max(np.abs(b))))
+            assert err < lim, (name, err)
+    assert n == 42
+
+
+def test_template_matching_operators():
+    """The closed-form operators: predict = x.A = sum over the taps of X; XXt, yX are the products of X;
+    the running sums follow yX_sum += yX / it."""
+    from oracle import template_matching as otm
+    rng = np.random.RandomState(0)
+    for S, N, s, padding in ((5, 40, 1, 'SAME'), (5, 40, 3, 'VALID'), (7, 40, 9, 'SAME'), (40, 40, 1, 'VALID')):
+        C, Q = otm.geometry(S, N, s, padding)
+        D = rng.randn(2, S) + 1j * rng.randn(2, S)
+        x = rng.randn(3, 2, C) + 1j * rng.randn(3, 2, C)
+        y = rng.randn(3, N) + 1j * rng.randn(3, N)
+        A = otm.temp2mat(D, N, s, padding)
+        X = otm.coef2mat(x, N, S, s, padding)
+        for t in range(2):
+            for c in range(C):
+                for n in range(N):
+                    k = n - s * c + Q
+                    assert A[t, c, n] == (D[t, k] if 0 <= k < S else 0)
+        p = otm.predict(x, D, N, s, padding)
+        assert np.allclose(p, np.einsum('btkn,tk->bn', X, D), rtol=1e-13, atol=1e-13)
+        XXt, yX = otm.statistics(y, x, S, s, padding)
+        X2 = X.reshape(3, -1, N)
+        assert np.allclose(XXt, np.einsum('bin,bjn->ij', X2, np.conj(X2)), rtol=1e-13, atol=1e-13)
+        assert np.allclose(yX, np.einsum('bn,bin->i', y, X2), rtol=1e-13, atol=1e-13)
+        X1, Y1 = otm.accumulate(XXt, yX, XXt, yX, 2)
+        assert np.allclose(X1, 1.5 * XXt) and np.allclose(Y1, 1.5 * yX)
