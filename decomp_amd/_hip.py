@@ -147,6 +147,14 @@ SIGNATURES = {
                                   _P(_c_int), _P(_c_f32), _P(_c_f32)]),
     'dcp_nmf_hals_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int,
                                   _P(_c_int), _P(_c_f64), _P(_c_f64)]),
+    'dcp_nmf_hals_sharded_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f32, _c_int,
+                                          _P(_c_int), _P(_c_f32)]),
+    'dcp_nmf_hals_sharded_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int,
+                                          _P(_c_int), _P(_c_f64)]),
+    'dcp_nmf_hals_stats_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
+    'dcp_nmf_hals_stats_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
+    'dcp_nmf_hals_update_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
+    'dcp_nmf_hals_update_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
     'dcp_nn_cd_sweep_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
     'dcp_nn_cd_sweep_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
     'dcp_nmf_mu_stats_width': (_c_i64, [_c_i64, _c_i64, _c_int, _c_int]),

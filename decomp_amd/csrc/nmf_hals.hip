@@ -1,7 +1,9 @@
-// C ABI: NMF by HALS (exact block coordinate descent, squared loss, no mask) and the non-negative
-// coordinate sweep on its own.  Contract in include/decomp_hip.h; the kernels in nmf_hals.hpp.
+// C ABI: NMF by HALS (exact block coordinate descent, squared loss, no mask), its row-sharded loop and split
+// step, and the non-negative coordinate sweep on its own.  Contract in include/decomp_hip.h; the kernels in
+// nmf_hals.hpp.
 #include <cmath>
 
+#include "comm.hpp"
 #include "nmf_hals.hpp"
 #include "nmf_impl.hpp"
 
@@ -24,17 +26,18 @@ int sweep_rc(dcp_handle* h, hipError_t e) {
     return DCP_OK;
 }
 
-// One HALS iteration's products and sweeps from (Xc, Dc) into (Xn, U):
+// The two halves of one HALS iteration from (Xc, Dc) into (Xn, U), split where the sharded loop all-reduces:
+// hals_x_side (every term local to this rank's rows, or replicated)
 //   G = Dc Dc^T, C = Y Dc^T           (w.G, w.Q)
 //   Xn = sweep(Xc, C, G)              vector-major, N vectors
 //   stats = [Xn^T Y | Xn^T Xn]        the statistics product of the MU loop (nmf_stats, D-side phase)
+// hals_d_sweep (from the statistics summed over the ranks)
 //   U = sweep(Dc, (Xn^T Y)^T, Xn^T Xn)   coordinate-major, F vectors (the columns of D)
 template <class T>
-int hals_products_and_sweeps(dcp_handle* h, const T* Y, const T* Xc, T* Xn, const T* Dc, T* U,
-                             const NmfShape<T>& s, T* stats, NmfStatsWs<T>& w) {
+int hals_x_side(dcp_handle* h, const T* Y, const T* Xc, T* Xn, const T* Dc, const NmfShape<T>& s, T* stats,
+                NmfStatsWs<T>& w) {
     hipStream_t st = h->stream;
     const int N = (int)s.N, F = (int)s.F, K = (int)s.K;
-    const long W = F + K;
     {   // G = D D^T (split over F, partial slabs summed in order), as the MU loop's Gram product
         ProfScope ps(h, DCP_PROF_GRAM);
         GemmArgs<T> g;
@@ -63,19 +66,38 @@ int hals_products_and_sweeps(dcp_handle* h, const T* Y, const T* Xc, T* Xn, cons
         }
         DCP_TRY(sweep_rc(h, launch_nn_cd_sweep<T, false>(st, Xc, Xn, K, w.Q, K, w.G, K, N, K)));
     }
-    DCP_TRY(nmf_stats<T>(h, Y, nullptr, Xn, Xn, Dc, s, stats, w, 2));
-    {
-        ProfScope ps(h, DCP_PROF_DUPDATE);
-        DCP_TRY(sweep_rc(h, launch_nn_cd_sweep<T, true>(st, Dc, U, F, stats, W, stats + F, W, F, K)));
-    }
+    return nmf_stats<T>(h, Y, nullptr, Xn, Xn, Dc, s, stats, w, 2);
+}
+
+template <class T>
+int hals_d_sweep(dcp_handle* h, const T* Dc, T* U, int64_t F, int64_t K, const T* stats) {
+    ProfScope ps(h, DCP_PROF_DUPDATE);
+    const long W = (long)(F + K);
+    return sweep_rc(h, launch_nn_cd_sweep<T, true>(h->stream, Dc, U, (long)F, stats, W, stats + F, W, (int)F,
+                                                   (int)K));
+}
+
+// D_new = U with unit-norm rows, max|Dc - D_new| into *maxdiff_dev (see hals_normalize_kernel), X[:, k] *= ||U_k||
+template <class T>
+int hals_normalize_rescale(dcp_handle* h, const T* U, const T* Dc, T* Dn, T* X, int64_t N, int64_t F, int64_t K,
+                           T* nrm, T* maxdiff_dev, T* maxdiff_next, unsigned int* ticket, T* host_out) {
+    ProfScope ps(h, DCP_PROF_DNORM);
+    hipLaunchKernelGGL((hals_normalize_kernel<T>), dim3((unsigned)K), dim3(256), 0, h->stream, U, (long)F, Dc, Dn,
+                       nrm, maxdiff_dev, maxdiff_next, ticket, host_out);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    hipLaunchKernelGGL((hals_rescale_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, h->stream, X,
+                       (long)N * K, (int)K, (const T*)nrm);
+    DCP_LAUNCH_OK(h, hipGetLastError());
     return DCP_OK;
 }
 
 template <class T>
 int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, int64_t K, T tol, int maxiter,
-                   int* it_out, T* last_maxdiff, T* resid_trace) {
+                   int* it_out, T* last_maxdiff, T* resid_trace, bool sharded = false) {
     DCP_TRY(check_hals_args(h, Y, X, D, N, F, K));
     if (!it_out) return fail(h, DCP_ERR_INVALID, "it_out is null");
+    if (sharded && !comm_active(h))
+        return fail(h, DCP_ERR_COMM, "dcp_nmf_hals_sharded_* needs a communicator (dcp_comm_init)");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     NmfShape<T> s{N, F, K, DCP_LIK_L2, false};
     const int64_t W = F + K;
@@ -144,18 +166,16 @@ int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, 
     bool converged = false;
     for (int it = 1; it < maxiter; ++it) {
         const int slot = it & 1;
-        DCP_TRY(hals_products_and_sweeps<T>(h, Y, Xc, Xn, Dc, U, s, stats, ws));
-        *reinterpret_cast<volatile T*>(host_md + slot) = T(-1);
-        {
-            ProfScope ps(h, DCP_PROF_DNORM);
-            hipLaunchKernelGGL((hals_normalize_kernel<T>), dim3((unsigned)K), dim3(256), 0, h->stream, (const T*)U,
-                               (long)F, (const T*)Dc, Dn, nrm, maxdiff_dev + slot, maxdiff_dev + (slot ^ 1), ticket,
-                               host_md + slot);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            hipLaunchKernelGGL((hals_rescale_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, h->stream, Xn,
-                               (long)N * K, (int)K, (const T*)nrm);
-            DCP_LAUNCH_OK(h, hipGetLastError());
+        DCP_TRY(hals_x_side<T>(h, Y, Xc, Xn, Dc, s, stats, ws));
+        if (sharded) {   // the one exchange of the step: the D sweep reads sums over all ranks' rows
+            ProfScope ps(h, DCP_PROF_EXCHANGE);
+            DCP_TRY(comm_allreduce_sum(h, stats, (size_t)K * W,
+                                       std::is_same<T, float>::value ? COMM_F32 : COMM_F64));
         }
+        DCP_TRY(hals_d_sweep<T>(h, Dc, U, F, K, stats));
+        *reinterpret_cast<volatile T*>(host_md + slot) = T(-1);
+        DCP_TRY(hals_normalize_rescale<T>(h, U, Dc, Dn, Xn, N, F, K, nrm, maxdiff_dev + slot,
+                                          maxdiff_dev + (slot ^ 1), ticket, host_md + slot));
         if (want_resid) {   // parity/debug mode: synchronous
             DCP_TRY(nmf_residual<T>(h, Y, nullptr, Xn, Dn, N, F, K, resid_tmp, resid_part, resid_blocks));
             DCP_HIP_OK(h, hipMemcpyAsync(host_part, resid_part, sizeof(double) * resid_blocks,
@@ -192,6 +212,49 @@ int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, 
     return DCP_OK;
 }
 
+// dcp_nmf_hals_stats_*: the x side of one iteration, up to the exchange point.  Same kernels in the same order
+// as the loop above, so that the Python loop (decomp_amd.sharded.mu_loop) reproduces it bit for bit.
+template <class T>
+int nmf_hals_stats_api(dcp_handle* h, const T* Y, const T* X, T* X_out, const T* D, int64_t N, int64_t F, int64_t K,
+                       T* stats) {
+    DCP_TRY(check_hals_args(h, Y, X, D, N, F, K));
+    if (!stats || !X_out) return fail(h, DCP_ERR_INVALID, "stats / X_out is null");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    NmfShape<T> s{N, F, K, DCP_LIK_L2, false};
+    WsPlan plan;
+    nmf_plan_stats(plan, s, false);
+    DCP_TRY(ws_reserve(h, plan.total));
+    ws_reset(h);
+    NmfStatsWs<T> ws;
+    DCP_TRY(nmf_carve_stats(h, ws, s, false));
+    return hals_x_side<T>(h, Y, X, X_out, D, s, stats, ws);
+}
+
+// dcp_nmf_hals_update_*: the D sweep from the (all-reduced) statistics, the normalisation and the x rescale.
+template <class T>
+int nmf_hals_update_api(dcp_handle* h, const T* stats, const T* D, T* D_new, T* X, int64_t N, int64_t F,
+                        int64_t K, T* maxdiff_dev, T* maxdiff_next) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!stats || !D || !D_new || !X || !maxdiff_dev) return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
+    if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL || F + K > 0x3fffffffLL)
+        return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    // shares the arena with dcp_nmf_hals_stats_*: its temporaries are dead by now (same stream)
+    WsPlan plan;
+    plan.add<T>((size_t)K * F);   // U
+    plan.add<T>((size_t)K);       // atom norms
+    DCP_TRY(ws_reserve(h, plan.total));
+    ws_reset(h);
+    T* U = ws_alloc<T>(h, (size_t)K * F);
+    T* nrm = ws_alloc<T>(h, (size_t)K);
+    if (!U || !nrm) return fail(h, DCP_ERR_INTERNAL, "hals workspace plan mismatch");
+    DCP_TRY(hals_d_sweep<T>(h, D, U, F, K, stats));
+    // without a ping-pong partner the max is formed from zero here (the kernel's atomic max needs it)
+    if (!maxdiff_next) DCP_HIP_OK(h, hipMemsetAsync(maxdiff_dev, 0, sizeof(T), h->stream));
+    return hals_normalize_rescale<T>(h, U, D, D_new, X, N, F, K, nrm, maxdiff_dev, maxdiff_next, nullptr, nullptr);
+}
+
 template <class T>
 int nn_cd_sweep_api(dcp_handle* h, const T* V_in, T* V_out, const T* C, const T* G, int64_t R, int64_t K,
                     int coord_major) {
@@ -218,6 +281,30 @@ int dcp_nmf_hals_f32(dcp_handle* h, const float* Y, float* X, float* D, int64_t 
 int dcp_nmf_hals_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
                      double tol, int maxiter, int* it_out, double* last_maxdiff, double* resid_trace) {
     return nmf_hals_solve<double>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, resid_trace);
+}
+int dcp_nmf_hals_sharded_f32(dcp_handle* h, const float* Y, float* X, float* D, int64_t N, int64_t F, int64_t K,
+                             float tol, int maxiter, int* it_out, float* last_maxdiff) {
+    return nmf_hals_solve<float>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, nullptr, true);
+}
+int dcp_nmf_hals_sharded_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
+                             double tol, int maxiter, int* it_out, double* last_maxdiff) {
+    return nmf_hals_solve<double>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, nullptr, true);
+}
+int dcp_nmf_hals_stats_f32(dcp_handle* h, const float* Y, const float* X, float* X_out, const float* D, int64_t N,
+                           int64_t F, int64_t K, float* stats) {
+    return nmf_hals_stats_api<float>(h, Y, X, X_out, D, N, F, K, stats);
+}
+int dcp_nmf_hals_stats_f64(dcp_handle* h, const double* Y, const double* X, double* X_out, const double* D,
+                           int64_t N, int64_t F, int64_t K, double* stats) {
+    return nmf_hals_stats_api<double>(h, Y, X, X_out, D, N, F, K, stats);
+}
+int dcp_nmf_hals_update_f32(dcp_handle* h, const float* stats, const float* D, float* D_new, float* X, int64_t N,
+                            int64_t F, int64_t K, float* maxdiff_dev, float* maxdiff_next) {
+    return nmf_hals_update_api<float>(h, stats, D, D_new, X, N, F, K, maxdiff_dev, maxdiff_next);
+}
+int dcp_nmf_hals_update_f64(dcp_handle* h, const double* stats, const double* D, double* D_new, double* X,
+                            int64_t N, int64_t F, int64_t K, double* maxdiff_dev, double* maxdiff_next) {
+    return nmf_hals_update_api<double>(h, stats, D, D_new, X, N, F, K, maxdiff_dev, maxdiff_next);
 }
 int dcp_nn_cd_sweep_f32(dcp_handle* h, const float* V_in, float* V_out, const float* C, const float* G, int64_t R,
                         int64_t K, int coord_major) {

@@ -17,6 +17,11 @@ only reads the lagged stop test -- no Python, no second stream, no event pair pe
 loop ``mu_loop`` stays as the executable statement of the host logic (it is what the gloo tests
 drive, with an oracle-backed or HIP-backed step) and as the path for process groups RCCL cannot
 serve (several ranks on one GPU).
+
+HALS (``nmf_solve_sharded(..., method='hals')``) shards the same way: its D sweep reads exactly the
+[x^T Y | x^T x] statistics MU all-reduces, so ``dcp_nmf_hals_sharded_*`` all-reduces them between the x side
+and the D sweep, and ``HipHalsStepBackend`` drives the split step (``dcp_nmf_hals_stats_*`` /
+``dcp_nmf_hals_update_*``) through the same ``mu_loop``.
 """
 import ctypes
 import os
@@ -154,6 +159,18 @@ def mu_solve_in_library(y, mask, x, D, lik, tol, maxiter, beta=None):
     return it.value
 
 
+def hals_solve_in_library(y, x, D, tol, maxiter):
+    """``dcp_nmf_hals_sharded_*`` on this rank's rows (x and D updated in place).  Returns it."""
+    lib, h = _arrays.lib_handle(D)
+    sfx = _arrays.suffix(D)
+    fn = getattr(lib, 'dcp_nmf_hals_sharded_' + sfx)
+    it = ctypes.c_int(0)
+    ctol = ctypes.c_float(tol) if sfx == 'f32' else ctypes.c_double(tol)
+    _hip.check(h, fn(h, _arrays.ptr(y), _arrays.ptr(x), _arrays.ptr(D), y.shape[0], y.shape[1], D.shape[0], ctol,
+                     int(maxiter), ctypes.byref(it), None), 'dcp_nmf_hals_sharded_' + sfx)
+    return it.value
+
+
 class HipStepBackend(object):
     """The two halves of one MU iteration on this rank's GPU, through the C ABI.
 
@@ -230,6 +247,56 @@ class HipStepBackend(object):
         return float(self._host[slot])
 
 
+class HipHalsStepBackend(object):
+    """The two halves of one HALS iteration on this rank's GPU (``dcp_nmf_hals_stats_*`` /
+    ``dcp_nmf_hals_update_*``), with the protocol of ``HipStepBackend``: x is double buffered,
+    ``local_stats`` writes the next x into the other buffer, ``update`` rescales that new x in place, and
+    ``rollback`` returns to the untouched previous one."""
+
+    def __init__(self, y, x, D):
+        import torch
+        self.torch = torch
+        self.y = y
+        self.x = x
+        self._x_other = torch.empty_like(x)
+        self.N, self.F = y.shape
+        self.K = D.shape[0]
+        self.sfx = _arrays.suffix(D)
+        self.stats = torch.empty((self.K, self.F + self.K), dtype=D.dtype, device=D.device)
+        self.maxdiff = torch.zeros((2,), dtype=D.dtype, device=D.device)
+        self._host = torch.zeros((2,), dtype=D.dtype).pin_memory()
+        self._events = [None, None]
+
+    def local_stats(self, D):
+        lib, h = _arrays.lib_handle(D)
+        fn = getattr(lib, 'dcp_nmf_hals_stats_' + self.sfx)
+        _hip.check(h, fn(h, _arrays.ptr(self.y), _arrays.ptr(self.x), _arrays.ptr(self._x_other), _arrays.ptr(D),
+                         self.N, self.F, self.K, _arrays.ptr(self.stats)), 'dcp_nmf_hals_stats')
+        self.x, self._x_other = self._x_other, self.x
+        return self.stats
+
+    def rollback(self):
+        """Forget the last local_stats (and the rescale of its x by update)."""
+        self.x, self._x_other = self._x_other, self.x
+
+    def update(self, stats, D, D_new, slot):
+        """Enqueue the D sweep, normalisation and x rescale; max|dD| lands asynchronously in host slot ``slot``."""
+        lib, h = _arrays.lib_handle(D)
+        fn = getattr(lib, 'dcp_nmf_hals_update_' + self.sfx)
+        md = self.maxdiff[slot:slot + 1]            # zero on entry (ping-pong, see the C ABI)
+        nxt = self.maxdiff[(slot ^ 1):(slot ^ 1) + 1]
+        _hip.check(h, fn(h, _arrays.ptr(stats), _arrays.ptr(D), _arrays.ptr(D_new), _arrays.ptr(self.x), self.N,
+                         self.F, self.K, _arrays.ptr(md), _arrays.ptr(nxt)), 'dcp_nmf_hals_update')
+        self._host[slot:slot + 1].copy_(md, non_blocking=True)
+        ev = self.torch.cuda.Event()
+        ev.record()
+        self._events[slot] = ev
+
+    def read_maxdiff(self, slot):
+        self._events[slot].synchronize()
+        return float(self._host[slot])
+
+
 def mu_loop(backend, D, tol, maxiter, group=None, world_size=1, new_like=None):
     """batch_mu.py:16-26 with the statistics all-reduced over ``group``.
 
@@ -260,17 +327,23 @@ def mu_loop(backend, D, tol, maxiter, group=None, world_size=1, new_like=None):
 
 
 def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likelihood='l2',
-                      mask_local=None, group=None):
-    """``decomp.nmf.solve(method='mu')`` for a row-sharded problem.
+                      mask_local=None, group=None, method='mu'):
+    """``decomp.nmf.solve(method='mu')`` -- or, with ``method='hals'``, ``nmf.solve(method='hals')``
+    (l2, no mask) -- for a row-sharded problem.
 
     Every rank passes its own rows (torch CUDA tensors) and the same D.  Returns
     (it, D, x_local); D and it are identical on all ranks.  torch.distributed must be
-    initialised (backend "nccl" = RCCL on ROCm) unless the world size is 1.
+    initialised (backend "nccl" = RCCL on ROCm) unless the world size is 1.  Both methods
+    exchange the same [K, F+K] statistics once per iteration.
     """
     import torch
     import torch.distributed as dist
     from . import nmf as _nmf
     from .utils import assertion
+    if method == 'hals':
+        _nmf._check_hals_scope(likelihood, mask_local)
+    elif method != 'mu':
+        raise NotImplementedError('Sharded NMF with {} algorithm is not yet implemented.'.format(method))
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     assertion.assert_dtypes(y=y_local, D=D, x=x_local, mask=mask_local, dtypes='f')
     assertion.assert_shapes('y', y_local, 'D', D, axes=[-1])
@@ -292,9 +365,15 @@ def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likeli
     _arrays.l2_normalize_(Dd, strict=True)
     if world > 1 and attach_communicator(Dd, group):
         # the shipped multi-GPU path: the whole loop, collective included, behind the C ABI
-        it = mu_solve_in_library(y, m, x, Dd, lik, tol, maxiter, beta=beta)
+        if method == 'hals':
+            it = hals_solve_in_library(y, x, Dd, tol, maxiter)
+        else:
+            it = mu_solve_in_library(y, m, x, Dd, lik, tol, maxiter, beta=beta)
         return it, Dd, x
-    backend = HipStepBackend(y, m, x, Dd, lik, beta=beta)
+    if method == 'hals':
+        backend = HipHalsStepBackend(y, x, Dd)
+    else:
+        backend = HipStepBackend(y, m, x, Dd, lik, beta=beta)
     it, Dout = mu_loop(backend, Dd, tol, maxiter, group=group, world_size=world,
                        new_like=torch.empty_like)
     return it, Dout, backend.x

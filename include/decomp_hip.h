@@ -226,6 +226,34 @@ int dcp_nmf_hals_f32(dcp_handle* h, const float* Y, float* X, float* D, int64_t 
                      float tol, int maxiter, int* it_out, float* last_maxdiff, float* resid_trace);
 int dcp_nmf_hals_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
                      double tol, int maxiter, int* it_out, double* last_maxdiff, double* resid_trace);
+/* HALS for a problem whose ROWS are sharded over the ranks of the handle's communicator (dcp_comm_init or
+ * dcp_comm_set_external): Y and X are this rank's rows, D is replicated.  Every iteration runs
+ *   D D^T, Y D^T, the x sweep and [x^T Y | x^T x] with the new x on this rank's rows
+ *   -> all-reduce(sum) of the [K, F+K] statistics on the handle's stream          (the ONLY exchange)
+ *   -> the replicated D sweep and normalisation (identical on every rank), X[:,k] *= n_k on this rank's rows
+ * with the stop rule of dcp_nmf_hals_*: no host synchronisation and no second stream inside a step.  Every rank
+ * must call it with the same F, K, tol and maxiter; N >= 1 may differ per rank.  it_out, last_maxdiff and D are
+ * identical on all ranks.  DCP_ERR_COMM without a communicator. */
+int dcp_nmf_hals_sharded_f32(dcp_handle* h, const float* Y, float* X, float* D, int64_t N, int64_t F, int64_t K,
+                             float tol, int maxiter, int* it_out, float* last_maxdiff);
+int dcp_nmf_hals_sharded_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
+                             double tol, int maxiter, int* it_out, double* last_maxdiff);
+/* One HALS iteration split at the exchange point, asynchronous on the handle's stream (the HALS counterpart of
+ * dcp_nmf_mu_stats_* / dcp_nmf_mu_update_*; run in this order they reproduce dcp_nmf_hals_* bit for bit):
+ *   dcp_nmf_hals_stats_*  : G = D D^T, C = Y D^T, X_out = sweep(X, C, G) (X_out may alias X), then this rank's
+ *                           stats[K, F+K] = [ X_out^T Y | X_out^T X_out ]  (the caller sums stats over ranks)
+ *   dcp_nmf_hals_update_* : U = sweep(D^T, (stats[:, :F])^T, stats[:, F:]) (coordinate-major), D_new = U with
+ *                           each row of positive norm n_k scaled to unit norm, X[:,k] *= n_k (X [N, K] in place,
+ *                           columns with n_k = 0 unchanged), max|D - D_new| to the DEVICE scalar maxdiff_dev,
+ *                           with the maxdiff_next protocol of dcp_nmf_mu_update_* (NULL: maxdiff_dev is set). */
+int dcp_nmf_hals_stats_f32(dcp_handle* h, const float* Y, const float* X, float* X_out, const float* D, int64_t N,
+                           int64_t F, int64_t K, float* stats);
+int dcp_nmf_hals_stats_f64(dcp_handle* h, const double* Y, const double* X, double* X_out, const double* D,
+                           int64_t N, int64_t F, int64_t K, double* stats);
+int dcp_nmf_hals_update_f32(dcp_handle* h, const float* stats, const float* D, float* D_new, float* X, int64_t N,
+                            int64_t F, int64_t K, float* maxdiff_dev, float* maxdiff_next);
+int dcp_nmf_hals_update_f64(dcp_handle* h, const double* stats, const double* D, double* D_new, double* X,
+                            int64_t N, int64_t F, int64_t K, double* maxdiff_dev, double* maxdiff_next);
 /* The non-negative coordinate sweep of HALS on R independent vectors: for k = 0 .. K-1 in order, with the
  * current V (coordinates < k already updated),
  *   if G[k,k] > 0:  V[:,k] = max(0, V[:,k] - (V G[:,k] - C[:,k]) / G[k,k])      (else V[:,k] unchanged)
