@@ -113,6 +113,7 @@ SIGNATURES = {
     'dcp_nmf_gauss_logp_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_f64)]),
     'dcp_nmf_gauss_logp_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_f64)]),
     'dcp_set_nmf_beta': (_c_int, [_c_vp, _c_f64]),
+    'dcp_set_nmf_penalty': (_c_int, [_c_vp, _c_f64, _c_f64]),
     'dcp_nmf_beta_divergence_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _P(_c_f64)]),
     'dcp_nmf_beta_divergence_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _P(_c_f64)]),
     'dcp_nmf_apply_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_f64, _c_vp, _c_i64, _c_i64, _P(_c_f64)]),

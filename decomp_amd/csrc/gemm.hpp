@@ -693,6 +693,17 @@ struct EpiStore {  // C[row, col] = acc
 };
 
 template <class T>
+struct EpiStoreSub {  // C[row, col] = acc - sub  (the HALS x sweep's C = Y D^T - l1 under an L1 penalty)
+    static constexpr bool kVec4 = false;
+    T* C;
+    long ldc;
+    T sub;
+    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
+        C[(long)r * ldc + c] = v - sub;
+    }
+};
+
+template <class T>
 struct EpiSlab {  // split-K partial: slab[split][row, col] = acc
     static constexpr bool kVec4 = false;   // neutral in the A/B (1.134 vs 1.130 ms on x^T.Y): off
     T* slab;
@@ -746,6 +757,30 @@ struct EpiMuNum {
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = x[e] * max_np(v[e], 0.0f) / max_np(d[e], 1.0e-15f);
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + (long)r * ld_out + c0) = o;
+    }
+};
+
+// EpiMuNum with the L1/L2 penalty on the codes: out = cur * max(acc, 0) / max(den + l1 + l2 cur, 1e-15).
+// A type of its own, so that the unpenalised instantiations stay exactly as they are; l1 / l2 are uniform
+// kernel arguments (SGPRs).
+template <class T>
+struct EpiMuNumPen : EpiMuNum<T> {
+    T l1, l2;
+    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
+        const T d = this->den[(long)r * this->ld_den + c];
+        const T x = this->cur[(long)r * this->ld_cur + c];
+        this->out[(long)r * this->ld_out + c] = x * max_np(v, T(0)) / max_np(d + l1 + l2 * x, T(1.0e-15));
+    }
+    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
+        const f32x4 d =
+            *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(this->den) + (long)r * this->ld_den + c0);
+        const f32x4 x =
+            *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(this->cur) + (long)r * this->ld_cur + c0);
+        const float a1 = (float)l1, a2 = (float)l2;
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = x[e] * max_np(v[e], 0.0f) / max_np(d[e] + a1 + a2 * x[e], 1.0e-15f);
+        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(this->out) + (long)r * this->ld_out + c0) = o;
     }
 };
 
@@ -804,6 +839,35 @@ struct EpiMuDenSlabs {
 #pragma unroll
             for (int e = 0; e < 4; ++e) q[e] = x[e] * max_np(nu[e], 0.0f) / max_np(v[e], 1.0e-15f);
             *reinterpret_cast<f32x4*>(out + (long)r * ld_out + c0) = q;
+        }
+    }
+};
+
+// EpiMuDenSlabs with the L1/L2 penalty on the codes: out = cur * max(sum slabs, 0) / max(acc + l1 + l2 cur, 1e-15).
+template <class T>
+struct EpiMuDenSlabsPen : EpiMuDenSlabs<T> {
+    T l1, l2;
+    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
+        const long o = (long)r * this->ld_slab + c;
+        T nu = this->slabs[o];
+        for (int s = 1; s < this->S; ++s) nu = nu + this->slabs[(long)s * this->slab_stride + o];
+        const T x = this->cur[(long)r * this->ld_cur + c];
+        this->out[(long)r * this->ld_out + c] = x * max_np(nu, T(0)) / max_np(v + l1 + l2 * x, T(1.0e-15));
+    }
+    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
+        if constexpr (std::is_same<T, float>::value) {
+            const long o = (long)r * this->ld_slab + c0;
+            f32x4 nu = *reinterpret_cast<const f32x4*>(this->slabs + o);
+            for (int s = 1; s < this->S; ++s) {
+                const f32x4 p = *reinterpret_cast<const f32x4*>(this->slabs + (long)s * this->slab_stride + o);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) nu[e] = nu[e] + p[e];
+            }
+            const f32x4 x = *reinterpret_cast<const f32x4*>(this->cur + (long)r * this->ld_cur + c0);
+            f32x4 q;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) q[e] = x[e] * max_np(nu[e], 0.0f) / max_np(v[e] + l1 + l2 * x[e], 1.0e-15f);
+            *reinterpret_cast<f32x4*>(this->out + (long)r * this->ld_out + c0) = q;
         }
     }
 };

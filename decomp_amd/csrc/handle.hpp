@@ -70,6 +70,9 @@ struct dcp_handle {
     int f32_product_mode = 0;
     // beta of DCP_LIK_BETA (dcp_set_nmf_beta), read when an NMF call that passes DCP_LIK_BETA is enqueued
     double nmf_beta = 0.0;
+    // L1 / L2 penalty on the NMF codes (dcp_set_nmf_penalty), read when an MU or HALS loop or split step is
+    // enqueued; every other entry ignores it
+    double nmf_l1 = 0.0, nmf_l2 = 0.0;
 };
 
 namespace dcp {

@@ -153,6 +153,31 @@ inline void launch_reduce_slabs(hipStream_t st, const T* slabs, long stride, int
     hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3((unsigned)g), dim3(256), 0, st, slabs, stride, S, count, out);
 }
 
+// reduce_slabs_kernel's sum (the same left-to-right order) with an affine term: out[i] = sum_s slabs[s][i] - sub,
+// plus add_diag on the diagonal of a [diag_n, diag_n] matrix when diag_n > 0.  The HALS x sweep folds the L1/L2
+// penalty on the codes into its operands with it: C = Y D^T - l1 (sub) and G = D D^T + l2 I (add_diag).
+template <class T>
+__global__ void __launch_bounds__(256) reduce_slabs_affine_kernel(const T* __restrict__ slabs, long stride, int S,
+                                                                  long count, T sub, long diag_n, T add_diag,
+                                                                  T* __restrict__ out) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < count; i += (long)gridDim.x * 256L) {
+        T acc = slabs[i];
+        for (int s = 1; s < S; ++s) acc = add(acc, slabs[(long)s * stride + i]);
+        if (diag_n > 0 && i % (diag_n + 1) == 0) acc = acc + add_diag;
+        out[i] = acc - sub;
+    }
+}
+
+template <class T>
+inline void launch_reduce_slabs_affine(hipStream_t st, const T* slabs, long stride, int S, long count, T sub,
+                                       long diag_n, T add_diag, T* out) {
+    long g = (count + 255) / 256;
+    if (g < 1) g = 1;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL((reduce_slabs_affine_kernel<T>), dim3((unsigned)g), dim3(256), 0, st, slabs, stride, S, count,
+                       sub, diag_n, add_diag, out);
+}
+
 // Same, for a [rows, cols] matrix written into a wider destination (leading dim ld_out).
 template <class T>
 __global__ void __launch_bounds__(256) reduce_slabs_rows_kernel(const T* __restrict__ slabs,
@@ -306,6 +331,42 @@ __global__ void __launch_bounds__(256) mu_quotient_stacked_kernel(const T* __res
             nu = nu + slabs[(long)s * stride + count + i];
         }
         out[i] = cur[i] * max_np(nu, T(0)) / max_np(de, T(1.0e-15));
+    }
+}
+
+// The two kernels above with the L1/L2 penalty on the codes: the denominator is den + l1 + l2 cur (kernels of
+// their own, so that the unpenalised ones stay exactly as they are).
+template <class T>
+__global__ void __launch_bounds__(256) mu_quotient_slabs_pen_kernel(const T* __restrict__ cur,
+                                                                    const T* __restrict__ slabs,
+                                                                    long stride, int S,
+                                                                    const T* __restrict__ den, long ld_den,
+                                                                    long rows, long cols, T l1, T l2,
+                                                                    T* __restrict__ out) {
+    const long n = rows * cols;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
+        T nu = slabs[i];
+        for (int s = 1; s < S; ++s) nu = nu + slabs[(long)s * stride + i];
+        const long r = i / cols, c = i - r * cols;
+        const T d = den[r * ld_den + c];
+        const T x = cur[i];
+        out[i] = x * max_np(nu, T(0)) / max_np(d + l1 + l2 * x, T(1.0e-15));
+    }
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) mu_quotient_stacked_pen_kernel(const T* __restrict__ cur,
+                                                                      const T* __restrict__ slabs, long stride,
+                                                                      int S, long count, T l1, T l2,
+                                                                      T* __restrict__ out) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < count; i += (long)gridDim.x * 256L) {
+        T de = slabs[i], nu = slabs[count + i];
+        for (int s = 1; s < S; ++s) {
+            de = de + slabs[(long)s * stride + i];
+            nu = nu + slabs[(long)s * stride + count + i];
+        }
+        const T x = cur[i];
+        out[i] = x * max_np(nu, T(0)) / max_np(de + l1 + l2 * x, T(1.0e-15));
     }
 }
 

@@ -121,7 +121,7 @@ int nmf_mu_solve(dcp_handle* h, const T* Y, const T* mask, T* X, T* D, int64_t N
     bool converged = false;
     for (int it = 1; it < maxiter; ++it) {  // batch_mu.py:16
         const int slot = it & 1;
-        DCP_TRY(nmf_stats<T>(h, Ypre, mask, Xc, Xn, Dc, s, stats, ws));
+        DCP_TRY(nmf_stats<T>(h, Ypre, mask, Xc, Xn, Dc, s, stats, ws, 3, nmf_penalty(h)));
         if (sharded) {   // the one exchange of the step: sums over rows become sums over ranks
             ProfScope ps(h, DCP_PROF_EXCHANGE);
             DCP_TRY(comm_allreduce_sum(h, stats, (size_t)K * W,
@@ -192,7 +192,7 @@ int nmf_mu_stats_api(dcp_handle* h, const T* Y, const T* mask, const T* X, T* X_
         DCP_HIP_OK(h, hipGetLastError());
         Ypre = ws.Ym;
     }
-    return nmf_stats<T>(h, Ypre, mask, X, X_out, D, s, stats, ws);
+    return nmf_stats<T>(h, Ypre, mask, X, X_out, D, s, stats, ws, 3, nmf_penalty(h));
 }
 
 // dcp_nmf_mu_stats_* with the loop-invariant mask work done once by dcp_nmf_mask_prepare_*.
@@ -210,7 +210,7 @@ int nmf_mu_stats_prepared_api(dcp_handle* h, const T* Ym, const T* mask, const u
     NmfStatsWs<T> ws;
     DCP_TRY(nmf_carve_stats(h, ws, s, false));
     ws.mbits = bits;
-    return nmf_stats<T>(h, Ym, mask, X, X_out, D, s, stats, ws);
+    return nmf_stats<T>(h, Ym, mask, X, X_out, D, s, stats, ws, 3, nmf_penalty(h));
 }
 
 template <class T>
@@ -520,6 +520,14 @@ int dcp_set_nmf_beta(dcp_handle* h, double beta) {
     if (!h) return DCP_ERR_INVALID;
     if (!std::isfinite(beta)) return fail(h, DCP_ERR_INVALID, "beta must be finite");
     h->nmf_beta = beta;
+    return DCP_OK;
+}
+int dcp_set_nmf_penalty(dcp_handle* h, double l1, double l2) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!std::isfinite(l1) || !std::isfinite(l2) || l1 < 0.0 || l2 < 0.0)
+        return fail(h, DCP_ERR_INVALID, "penalties must be finite and >= 0");
+    h->nmf_l1 = l1;
+    h->nmf_l2 = l2;
     return DCP_OK;
 }
 int dcp_nmf_beta_divergence_f32(dcp_handle* h, const float* Y, const float* mask, const float* X, const float* D,

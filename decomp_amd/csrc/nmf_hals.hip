@@ -30,12 +30,15 @@ int sweep_rc(dcp_handle* h, hipError_t e) {
 // hals_x_side (every term local to this rank's rows, or replicated)
 //   G = Dc Dc^T, C = Y Dc^T           (w.G, w.Q)
 //   Xn = sweep(Xc, C, G)              vector-major, N vectors
+// With the L1/L2 penalty on the codes (dcp_set_nmf_penalty) the x sweep is the exact coordinate minimiser of the
+// penalised objective, which is the same sweep on C = Y Dc^T - l1 and G = Dc Dc^T + l2 I: the kernels that write
+// w.Q and w.G fold the penalty in (EpiStoreSub / reduce_slabs_affine_kernel), the sweep kernel is unchanged.
 //   stats = [Xn^T Y | Xn^T Xn]        the statistics product of the MU loop (nmf_stats, D-side phase)
 // hals_d_sweep (from the statistics summed over the ranks)
 //   U = sweep(Dc, (Xn^T Y)^T, Xn^T Xn)   coordinate-major, F vectors (the columns of D)
 template <class T>
 int hals_x_side(dcp_handle* h, const T* Y, const T* Xc, T* Xn, const T* Dc, const NmfShape<T>& s, T* stats,
-                NmfStatsWs<T>& w) {
+                NmfStatsWs<T>& w, NmfPenalty pen) {
     hipStream_t st = h->stream;
     const int N = (int)s.N, F = (int)s.F, K = (int)s.K;
     {   // G = D D^T (split over F, partial slabs summed in order), as the MU loop's Gram product
@@ -45,8 +48,12 @@ int hals_x_side(dcp_handle* h, const T* Y, const T* Xc, T* Xn, const T* Dc, cons
         if (!std::is_same<T, float>::value) g.tile = TILE_SMALL_DEEP;
         plan_splits<FORM_NT>(g, 512, kMaxSplits, 16);
         DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, g, EpiSlab<T>{w.slabs, K, (long)K * K})));
-        hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, st, w.slabs,
-                           (long)K * K, g.ksplits, (long)K * K, w.G);
+        if (pen.on())   // G + l2 I
+            launch_reduce_slabs_affine<T>(st, w.slabs, (long)K * K, g.ksplits, (long)K * K, T(0), (long)K, T(pen.l2),
+                                          w.G);
+        else
+            hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, st, w.slabs,
+                               (long)K * K, g.ksplits, (long)K * K, w.G);
         DCP_LAUNCH_OK(h, hipGetLastError());
     }
     {   // C = Y D^T, then the x sweep
@@ -56,12 +63,19 @@ int hals_x_side(dcp_handle* h, const T* Y, const T* Xc, T* Xn, const T* Dc, cons
         const int psplits = nmf_xupdate_splits<T>(s.N, s.F, s.K, pg);
         if (psplits <= 1) {
             pg.ksplits = 1;
-            DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiStore<T>{w.Q, K}, true)));
+            if (pen.on())   // Y D^T - l1
+                DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiStoreSub<T>{w.Q, K, T(pen.l1)}, true)));
+            else
+                DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiStore<T>{w.Q, K}, true)));
         } else {   // few rows: split the F reduction so that all CUs work, slabs summed in order
             if ((size_t)pg.ksplits * N * K > w.slab_count)
                 return fail(h, DCP_ERR_INTERNAL, "hals Y.D^T slab plan mismatch");
             DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiSlab<T>{w.slabs, K, (long)N * K}, true)));
-            launch_reduce_slabs<T>(st, w.slabs, (long)N * K, pg.ksplits, (long)N * K, w.Q);
+            if (pen.on())   // Y D^T - l1
+                launch_reduce_slabs_affine<T>(st, w.slabs, (long)N * K, pg.ksplits, (long)N * K, T(pen.l1), 0L, T(0),
+                                              w.Q);
+            else
+                launch_reduce_slabs<T>(st, w.slabs, (long)N * K, pg.ksplits, (long)N * K, w.Q);
             DCP_LAUNCH_OK(h, hipGetLastError());
         }
         DCP_TRY(sweep_rc(h, launch_nn_cd_sweep<T, false>(st, Xc, Xn, K, w.Q, K, w.G, K, N, K)));
@@ -100,6 +114,7 @@ int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, 
         return fail(h, DCP_ERR_COMM, "dcp_nmf_hals_sharded_* needs a communicator (dcp_comm_init)");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     NmfShape<T> s{N, F, K, DCP_LIK_L2, false};
+    const NmfPenalty pen = nmf_penalty(h);
     const int64_t W = F + K;
     const bool want_resid = resid_trace != nullptr;
     const int resid_blocks = 1024;
@@ -166,7 +181,7 @@ int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, 
     bool converged = false;
     for (int it = 1; it < maxiter; ++it) {
         const int slot = it & 1;
-        DCP_TRY(hals_x_side<T>(h, Y, Xc, Xn, Dc, s, stats, ws));
+        DCP_TRY(hals_x_side<T>(h, Y, Xc, Xn, Dc, s, stats, ws, pen));
         if (sharded) {   // the one exchange of the step: the D sweep reads sums over all ranks' rows
             ProfScope ps(h, DCP_PROF_EXCHANGE);
             DCP_TRY(comm_allreduce_sum(h, stats, (size_t)K * W,
@@ -227,7 +242,7 @@ int nmf_hals_stats_api(dcp_handle* h, const T* Y, const T* X, T* X_out, const T*
     ws_reset(h);
     NmfStatsWs<T> ws;
     DCP_TRY(nmf_carve_stats(h, ws, s, false));
-    return hals_x_side<T>(h, Y, X, X_out, D, s, stats, ws);
+    return hals_x_side<T>(h, Y, X, X_out, D, s, stats, ws, nmf_penalty(h));
 }
 
 // dcp_nmf_hals_update_*: the D sweep from the (all-reduced) statistics, the normalisation and the x rescale.

@@ -36,6 +36,14 @@ inline int64_t nmf_stats_width(int64_t F, int64_t K, int likelihood, bool masked
 constexpr int kSplitTarget = 1024;
 constexpr int kMaxSplits = 64;
 
+// L1/L2 penalty on the codes (dcp_set_nmf_penalty): the x update divides by  neg + l1 + l2 x  instead of neg.
+// Read from the handle by the MU / HALS loops and their split steps only; {0, 0} selects the unpenalised kernels.
+struct NmfPenalty {
+    double l1 = 0.0, l2 = 0.0;
+    bool on() const { return l1 != 0.0 || l2 != 0.0; }
+};
+inline NmfPenalty nmf_penalty(const dcp_handle* h) { return NmfPenalty{h->nmf_l1, h->nmf_l2}; }
+
 template <class T>
 struct NmfShape {
     int64_t N, F, K;
@@ -197,14 +205,16 @@ inline hipError_t nmf_product(dcp_handle* h, hipStream_t st, const GemmArgs<T>& 
 // Ypre: Y already multiplied by the mask (or Y itself when there is no mask).
 template <class T>
 inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, T* Xout, const T* D,
-                     const NmfShape<T>& s, T* stats, NmfStatsWs<T>& w, int phases = 3) {
+                     const NmfShape<T>& s, T* stats, NmfStatsWs<T>& w, int phases = 3,
+                     NmfPenalty pen = NmfPenalty()) {
     // phases: bit 0 = the x update (Xin -> Xout), bit 1 = the D-side sums (with Xout, or with
-    // Xin when the x update is skipped)
+    // Xin when the x update is skipped).  pen: the penalty on the codes, in the x update only
     hipStream_t st = h->stream;
     const int N = (int)s.N, F = (int)s.F, K = (int)s.K;
     const bool gram = (s.lik == DCP_LIK_L2 && !s.masked);
     const int W = (int)nmf_stats_width(s.F, s.K, s.lik, s.masked);
     const double beta = h->nmf_beta;
+    const T l1 = T(pen.l1), l2 = T(pen.l2);
 
     // forward product x.D with an elementwise epilogue into the [N,F] intermediate w.f (beta: w.f and w.f2)
     auto forward = [&](const T* X) -> int {
@@ -245,8 +255,13 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
                 if ((size_t)sg.ksplits * 2 * N * K > w.slab_count)
                     return fail(h, DCP_ERR_INTERNAL, "nmf stacked x-update slab plan mismatch");
                 DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, sg, EpiSlab<T>{w.slabs, K, (long)2 * N * K})));
-                hipLaunchKernelGGL((mu_quotient_stacked_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0,
-                                   st, Xin, (const T*)w.slabs, (long)2 * N * K, sg.ksplits, (long)N * K, Xout);
+                if (pen.on())
+                    hipLaunchKernelGGL((mu_quotient_stacked_pen_kernel<T>), dim3(grid_for((long)N * K)), dim3(256),
+                                       0, st, Xin, (const T*)w.slabs, (long)2 * N * K, sg.ksplits, (long)N * K, l1,
+                                       l2, Xout);
+                else
+                    hipLaunchKernelGGL((mu_quotient_stacked_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0,
+                                       st, Xin, (const T*)w.slabs, (long)2 * N * K, sg.ksplits, (long)N * K, Xout);
                 DCP_LAUNCH_OK(h, hipGetLastError());
                 done = true;
             }
@@ -320,7 +335,7 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
             DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, q, EpiStore<T>{w.Q, K})));
         }
     }
-    if (!x_done) {   // x <- x * max(pos, 0) / max(neg, eps)
+    if (!x_done) {   // x <- x * max(pos, 0) / max(neg, eps)   (penalised: max(neg + l1 + l2 x, eps))
         ProfScope ps(h, DCP_PROF_XUPDATE);
         GemmArgs<T> pg;
         pg.A = xnum_A; pg.lda = F; pg.B = D; pg.ldb = F; pg.M = N; pg.N = K; pg.K = F;
@@ -328,7 +343,11 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
         if (psplits <= 1) {
             // enough row tiles to fill the chip: quotient fused into the GEMM epilogue
             pg.ksplits = 1;
-            DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiMuNum<T>{Xin, K, xden, ld_xden, Xout, K}, gram)));
+            const EpiMuNum<T> num{Xin, K, xden, ld_xden, Xout, K};
+            if (pen.on())
+                DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, EpiMuNumPen<T>{num, l1, l2}, gram)));
+            else
+                DCP_LAUNCH_OK(h, (nmf_product<FORM_NT>(h, st, pg, num, gram)));
         } else {
             // few rows per GPU (a shard of a multi-GPU run): split the F reduction so that all
             // CUs work, then sum the slabs in order inside the quotient kernel
@@ -338,12 +357,20 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
             if (split_gram) {
                 GemmArgs<T> q;   // x_new = x * max(sum slabs, 0) / max(x G, eps)
                 q.A = Xin; q.lda = K; q.B = w.G; q.ldb = K; q.M = N; q.N = K; q.K = K;
-                DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, q, EpiMuDenSlabs<T>{Xin, K, w.slabs, K, (long)N * K,
-                                                                        pg.ksplits, Xout, K})));
+                const EpiMuDenSlabs<T> den{Xin, K, w.slabs, K, (long)N * K, pg.ksplits, Xout, K};
+                if (pen.on())
+                    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, q, EpiMuDenSlabsPen<T>{den, l1, l2})));
+                else
+                    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, q, den)));
             } else {
-                hipLaunchKernelGGL((mu_quotient_slabs_kernel<T>), dim3(grid_for((long)N * K)), dim3(256),
-                                   0, st, Xin, (const T*)w.slabs, (long)N * K, pg.ksplits, xden,
-                                   (long)ld_xden, (long)N, (long)K, Xout);
+                if (pen.on())
+                    hipLaunchKernelGGL((mu_quotient_slabs_pen_kernel<T>), dim3(grid_for((long)N * K)), dim3(256),
+                                       0, st, Xin, (const T*)w.slabs, (long)N * K, pg.ksplits, xden,
+                                       (long)ld_xden, (long)N, (long)K, l1, l2, Xout);
+                else
+                    hipLaunchKernelGGL((mu_quotient_slabs_kernel<T>), dim3(grid_for((long)N * K)), dim3(256),
+                                       0, st, Xin, (const T*)w.slabs, (long)N * K, pg.ksplits, xden,
+                                       (long)ld_xden, (long)N, (long)K, Xout);
                 DCP_LAUNCH_OK(h, hipGetLastError());
             }
         }

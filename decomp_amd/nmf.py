@@ -8,9 +8,12 @@ full batch), exact block coordinate descent in libdecomp_hip.so (``dcp_nmf_hals_
 decomp_amd/csrc/nmf_hals.hpp).  The full-batch MU iteration itself
 (decomp/nmf_methods/batch_mu.py:8-26 with the update rules of
 decomp/nmf_methods/grads.py:77-160) runs in libdecomp_hip.so: see
-include/decomp_hip.h ``dcp_nmf_mu_*`` and decomp_amd/csrc/nmf_impl.hpp.
+include/decomp_hip.h ``dcp_nmf_mu_*`` and decomp_amd/csrc/nmf_impl.hpp.  Also beyond the reference: an L1/L2
+penalty on the codes (``l1_penalty`` / ``l2_penalty``, ``dcp_set_nmf_penalty``) for both full-batch methods.
 """
 import ctypes
+import math
+import numbers
 
 import numpy as np
 
@@ -77,6 +80,39 @@ def _check_beta_data(likelihood, y, mask):
         assertion.assert_positive_where(y, mask)
 
 
+def _check_penalty(l1_penalty, l2_penalty):
+    """(l1, l2) as floats.  ValueError for a penalty that is not a finite real number >= 0."""
+    out = []
+    for name, v in (('l1_penalty', l1_penalty), ('l2_penalty', l2_penalty)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real):
+            raise ValueError('%s must be a real number, not %r' % (name, v))
+        v = float(v)
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError('%s must be finite and >= 0, not %r' % (name, v))
+        out.append(v)
+    return tuple(out)
+
+
+def _check_penalty_scope(penalty, minibatch, method, likelihood):
+    """What the penalty on the codes covers: the full-batch MU loop with a fused likelihood and HALS.  Raises
+    NotImplementedError for a non-zero penalty with a minibatch method or with a user ``Likelihood`` whose update
+    rule runs on the host (``_run_mu_user``).  Zero penalties pass everywhere."""
+    if penalty == (0.0, 0.0):
+        return
+    if minibatch is not None:
+        raise NotImplementedError('l1_penalty / l2_penalty are not implemented for the minibatch NMF methods')
+    if method == 'mu' and not isinstance(_likelihood_spec(likelihood)[0], int):
+        raise NotImplementedError('l1_penalty / l2_penalty are not implemented for a likelihood with its own '
+                                  'update rule')
+
+
+def _set_penalty(h, penalty):
+    """Hand (l1, l2) to the handle right before a call of the MU / HALS loops or split steps
+    (``dcp_set_nmf_penalty``); (0, 0) included, so that no earlier call's penalty is read."""
+    l1, l2 = penalty
+    _hip.check(h, _hip.load().dcp_set_nmf_penalty(h, float(l1), float(l2)), 'dcp_set_nmf_penalty')
+
+
 class _OnesLike(object):
     """Stand-in for the default x = ones((N, K)) during validation, so that the default
     is materialised directly in device memory."""
@@ -85,12 +121,22 @@ class _OnesLike(object):
 
 
 def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
-          likelihood='l2', mask=None, random_seed=None, **kwargs):
+          likelihood='l2', mask=None, random_seed=None, l1_penalty=0.0, l2_penalty=0.0, **kwargs):
     """
     Non-negative matrix factorisation  argmin_{x, D} |y - xD|^2,  x >= 0, D >= 0,
     |D_j| = 1, by multiplicative updates (method='mu'), or, for the l2 likelihood without a
     mask, by HALS (method='hals': exact block coordinate descent on the columns of x and the
     atoms of D, then the atoms rescaled to unit norm with x rescaled so that xD is unchanged).
+
+    l1_penalty, l2_penalty (lambda1, lambda2 >= 0, default 0): a penalty on the codes.  The objective
+    becomes  loss(y, xD) + lambda1 sum(x) + lambda2/2 |x|^2,  loss = 1/2 |M o (y - xD)|^2 for 'l2' (M the
+    mask, or 1), sum M o d(y | xD) for 'kl' and the beta divergences; no 1/n_samples scaling and no penalty
+    on D, whose rows stay unit norm.  So for a fixed D and lambda2 = 0 the x problem is exactly
+    ``lasso.solve(y, D, alpha=lambda1 / n_channels, method='cd_pos')`` (the lasso scales alpha by
+    n_channels).  MU divides by  grad_neg + lambda1 + lambda2 x  in its x update; HALS takes the exact
+    coordinate minimiser of the penalised objective in its x sweep.  Both 0 runs exactly the unpenalised
+    solver.  Non-zero penalties are not implemented for the minibatch methods or a likelihood with its own
+    update rule (NotImplementedError).
 
     y: [n_samples, n_channels], x: [n_samples, n_features], D: [n_features, n_channels],
     mask (optional): [n_samples, n_channels], 0 marks a missing entry; float32 or
@@ -104,6 +150,8 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
     Returns (it, D, x) exactly as the reference: ``it`` is the iteration at which
     max|D - D_new| < tol was met, or ``maxiter`` when it never was.
     """
+    penalty = _check_penalty(l1_penalty, l2_penalty)
+    _check_penalty_scope(penalty, minibatch, method, likelihood)
     kind = get_array_module(D)
     x_given = x
     if x is None:                                                     # nmf.py:53-54
@@ -161,7 +209,7 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
             if y_dev is None:
                 y_dev = _arrays.to_device(y, dev)
             m_dev = _arrays.to_device(mask, dev)
-            it = _run_mu(y_dev, m_dev, x_dev, D_dev, lik, tol, maxiter, beta=beta)
+            it = _run_mu(y_dev, m_dev, x_dev, D_dev, lik, tol, maxiter, beta=beta, penalty=penalty)
             return it, _arrays.to_caller(D_dev, kind), _arrays.to_caller(x_dev, kind)
         if method == 'hals':
             if kwargs:
@@ -170,7 +218,7 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
             _check_hals_scope(likelihood, mask)
             if y_dev is None:
                 y_dev = _arrays.to_device(y, dev)
-            it = _run_hals(y_dev, x_dev, D_dev, tol, maxiter)
+            it = _run_hals(y_dev, x_dev, D_dev, tol, maxiter, penalty=penalty)
             return it, _arrays.to_caller(D_dev, kind), _arrays.to_caller(x_dev, kind)
         raise NotImplementedError('Batch-NMF with {} algorithm is not yet '
                                   'implemented.'.format(method))
@@ -241,9 +289,9 @@ def _solve_streamed(y, D_dev, x_given, tol, minibatch, maxiter, method, likeliho
     return it, Dout, xout
 
 
-def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None, beta=None):
+def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None, beta=None, penalty=(0.0, 0.0)):
     """batch_mu.solve on device arrays; x and D are updated in place.  Returns it.  ``beta`` goes with
-    lik == DCP_LIK_BETA."""
+    lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes."""
     from .nmf_methods.grads import set_beta
     lib, h = _arrays.lib_handle(D)
     sfx = _arrays.suffix(D)
@@ -257,9 +305,14 @@ def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None, beta=None):
         trace = (ctype * max(int(maxiter), 1))()
     fn = getattr(lib, 'dcp_nmf_mu_' + sfx)
     set_beta(h, lik, beta)
-    rc = fn(h, _arrays.ptr(y), _arrays.ptr(mask), _arrays.ptr(x), _arrays.ptr(D),
-            N, F, K, lik, ctype(tol), int(maxiter), ctypes.byref(it), ctypes.byref(last),
-            trace)
+    _set_penalty(h, penalty)
+    try:
+        rc = fn(h, _arrays.ptr(y), _arrays.ptr(mask), _arrays.ptr(x), _arrays.ptr(D),
+                N, F, K, lik, ctype(tol), int(maxiter), ctypes.byref(it), ctypes.byref(last),
+                trace)
+    finally:
+        if penalty != (0.0, 0.0):
+            _set_penalty(h, (0.0, 0.0))
     _hip.check(h, rc, 'dcp_nmf_mu_' + sfx)
     if resid_trace is not None:
         n_done = it.value if it.value < maxiter else maxiter - 1
@@ -277,9 +330,10 @@ def _check_hals_scope(likelihood, mask):
                                   'not {} (use method=\'mu\')'.format(likelihood))
 
 
-def _run_hals(y, x, D, tol, maxiter, resid_trace=None):
+def _run_hals(y, x, D, tol, maxiter, resid_trace=None, penalty=(0.0, 0.0)):
     """HALS (exact block coordinate descent) on device arrays, D l2_strict normalised; x and D are updated
-    in place.  Same stop rule and return convention as ``_run_mu``.  Returns it."""
+    in place.  Same stop rule and return convention as ``_run_mu``; ``penalty`` is (l1, l2) on the codes.
+    Returns it."""
     lib, h = _arrays.lib_handle(D)
     sfx = _arrays.suffix(D)
     N, F = y.shape
@@ -291,8 +345,13 @@ def _run_hals(y, x, D, tol, maxiter, resid_trace=None):
     if resid_trace is not None:
         trace = (ctype * max(int(maxiter), 1))()
     fn = getattr(lib, 'dcp_nmf_hals_' + sfx)
-    rc = fn(h, _arrays.ptr(y), _arrays.ptr(x), _arrays.ptr(D), N, F, K, ctype(tol), int(maxiter),
-            ctypes.byref(it), ctypes.byref(last), trace)
+    _set_penalty(h, penalty)
+    try:
+        rc = fn(h, _arrays.ptr(y), _arrays.ptr(x), _arrays.ptr(D), N, F, K, ctype(tol), int(maxiter),
+                ctypes.byref(it), ctypes.byref(last), trace)
+    finally:
+        if penalty != (0.0, 0.0):
+            _set_penalty(h, (0.0, 0.0))
     _hip.check(h, rc, 'dcp_nmf_hals_' + sfx)
     if resid_trace is not None:
         n_done = it.value if it.value < maxiter else maxiter - 1

@@ -143,31 +143,44 @@ def comm_allreduce_(t):
     return t
 
 
-def mu_solve_in_library(y, mask, x, D, lik, tol, maxiter, beta=None):
+def mu_solve_in_library(y, mask, x, D, lik, tol, maxiter, beta=None, penalty=(0.0, 0.0)):
     """``dcp_nmf_mu_sharded_*`` on this rank's rows (x and D updated in place).  Returns it.  ``beta`` goes
-    with lik == DCP_LIK_BETA."""
+    with lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes (``nmf.solve``'s l1_penalty / l2_penalty)."""
     from .nmf_methods.grads import set_beta
+    from .nmf import _set_penalty
     lib, h = _arrays.lib_handle(D)
     sfx = _arrays.suffix(D)
     fn = getattr(lib, 'dcp_nmf_mu_sharded_' + sfx)
     set_beta(h, lik, beta)
     it = ctypes.c_int(0)
     ctol = ctypes.c_float(tol) if sfx == 'f32' else ctypes.c_double(tol)
-    _hip.check(h, fn(h, _arrays.ptr(y), _arrays.ptr(mask), _arrays.ptr(x), _arrays.ptr(D), y.shape[0],
-                     y.shape[1], D.shape[0], lik, ctol, int(maxiter), ctypes.byref(it), None),
-               'dcp_nmf_mu_sharded_' + sfx)
+    _set_penalty(h, penalty)
+    try:
+        _hip.check(h, fn(h, _arrays.ptr(y), _arrays.ptr(mask), _arrays.ptr(x), _arrays.ptr(D), y.shape[0],
+                         y.shape[1], D.shape[0], lik, ctol, int(maxiter), ctypes.byref(it), None),
+                   'dcp_nmf_mu_sharded_' + sfx)
+    finally:
+        if penalty != (0.0, 0.0):
+            _set_penalty(h, (0.0, 0.0))
     return it.value
 
 
-def hals_solve_in_library(y, x, D, tol, maxiter):
-    """``dcp_nmf_hals_sharded_*`` on this rank's rows (x and D updated in place).  Returns it."""
+def hals_solve_in_library(y, x, D, tol, maxiter, penalty=(0.0, 0.0)):
+    """``dcp_nmf_hals_sharded_*`` on this rank's rows (x and D updated in place).  Returns it.  ``penalty`` as
+    in ``mu_solve_in_library``."""
+    from .nmf import _set_penalty
     lib, h = _arrays.lib_handle(D)
     sfx = _arrays.suffix(D)
     fn = getattr(lib, 'dcp_nmf_hals_sharded_' + sfx)
     it = ctypes.c_int(0)
     ctol = ctypes.c_float(tol) if sfx == 'f32' else ctypes.c_double(tol)
-    _hip.check(h, fn(h, _arrays.ptr(y), _arrays.ptr(x), _arrays.ptr(D), y.shape[0], y.shape[1], D.shape[0], ctol,
-                     int(maxiter), ctypes.byref(it), None), 'dcp_nmf_hals_sharded_' + sfx)
+    _set_penalty(h, penalty)
+    try:
+        _hip.check(h, fn(h, _arrays.ptr(y), _arrays.ptr(x), _arrays.ptr(D), y.shape[0], y.shape[1], D.shape[0],
+                         ctol, int(maxiter), ctypes.byref(it), None), 'dcp_nmf_hals_sharded_' + sfx)
+    finally:
+        if penalty != (0.0, 0.0):
+            _set_penalty(h, (0.0, 0.0))
     return it.value
 
 
@@ -177,12 +190,13 @@ class HipStepBackend(object):
     x is double buffered: ``local_stats`` reads the current x and writes the next one, so
     the iteration that was enqueued speculatively (see ``mu_loop``) can be discarded with
     ``rollback``.  ``x`` is always the buffer holding the current iterate.  ``beta`` goes with
-    lik == DCP_LIK_BETA."""
+    lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes, set on the handle before every x step."""
 
-    def __init__(self, y, mask, x, D, lik, beta=None):
+    def __init__(self, y, mask, x, D, lik, beta=None, penalty=(0.0, 0.0)):
         import torch
         self.torch = torch
         self.y, self.mask, self.lik, self.beta = y, mask, lik, beta
+        self.penalty = penalty
         self.x = x
         self._x_other = torch.empty_like(x)
         self.N, self.F = y.shape
@@ -209,8 +223,10 @@ class HipStepBackend(object):
 
     def local_stats(self, D):
         from .nmf_methods.grads import set_beta
+        from .nmf import _set_penalty
         lib, h = _arrays.lib_handle(D)
         set_beta(h, self.lik, self.beta)
+        _set_penalty(h, self.penalty)
         if self.mask is not None:
             fn = getattr(lib, 'dcp_nmf_mu_stats_prepared_' + self.sfx)
             _hip.check(h, fn(h, _arrays.ptr(self._ym), _arrays.ptr(self.mask), _arrays.ptr(self._bits),
@@ -251,12 +267,13 @@ class HipHalsStepBackend(object):
     """The two halves of one HALS iteration on this rank's GPU (``dcp_nmf_hals_stats_*`` /
     ``dcp_nmf_hals_update_*``), with the protocol of ``HipStepBackend``: x is double buffered,
     ``local_stats`` writes the next x into the other buffer, ``update`` rescales that new x in place, and
-    ``rollback`` returns to the untouched previous one."""
+    ``rollback`` returns to the untouched previous one.  ``penalty`` as in ``HipStepBackend``."""
 
-    def __init__(self, y, x, D):
+    def __init__(self, y, x, D, penalty=(0.0, 0.0)):
         import torch
         self.torch = torch
         self.y = y
+        self.penalty = penalty
         self.x = x
         self._x_other = torch.empty_like(x)
         self.N, self.F = y.shape
@@ -268,7 +285,9 @@ class HipHalsStepBackend(object):
         self._events = [None, None]
 
     def local_stats(self, D):
+        from .nmf import _set_penalty
         lib, h = _arrays.lib_handle(D)
+        _set_penalty(h, self.penalty)
         fn = getattr(lib, 'dcp_nmf_hals_stats_' + self.sfx)
         _hip.check(h, fn(h, _arrays.ptr(self.y), _arrays.ptr(self.x), _arrays.ptr(self._x_other), _arrays.ptr(D),
                          self.N, self.F, self.K, _arrays.ptr(self.stats)), 'dcp_nmf_hals_stats')
@@ -327,19 +346,23 @@ def mu_loop(backend, D, tol, maxiter, group=None, world_size=1, new_like=None):
 
 
 def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likelihood='l2',
-                      mask_local=None, group=None, method='mu'):
+                      mask_local=None, group=None, method='mu', l1_penalty=0.0, l2_penalty=0.0):
     """``decomp.nmf.solve(method='mu')`` -- or, with ``method='hals'``, ``nmf.solve(method='hals')``
     (l2, no mask) -- for a row-sharded problem.
 
     Every rank passes its own rows (torch CUDA tensors) and the same D.  Returns
     (it, D, x_local); D and it are identical on all ranks.  torch.distributed must be
     initialised (backend "nccl" = RCCL on ROCm) unless the world size is 1.  Both methods
-    exchange the same [K, F+K] statistics once per iteration.
+    exchange the same [K, F+K] statistics once per iteration.  l1_penalty / l2_penalty: the
+    penalty on the codes of ``nmf.solve``; it acts on each rank's own rows of x only, so the
+    exchanged statistics are unchanged.
     """
     import torch
     import torch.distributed as dist
     from . import nmf as _nmf
     from .utils import assertion
+    penalty = _nmf._check_penalty(l1_penalty, l2_penalty)
+    _nmf._check_penalty_scope(penalty, None, method, likelihood)
     if method == 'hals':
         _nmf._check_hals_scope(likelihood, mask_local)
     elif method != 'mu':
@@ -366,16 +389,20 @@ def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likeli
     if world > 1 and attach_communicator(Dd, group):
         # the shipped multi-GPU path: the whole loop, collective included, behind the C ABI
         if method == 'hals':
-            it = hals_solve_in_library(y, x, Dd, tol, maxiter)
+            it = hals_solve_in_library(y, x, Dd, tol, maxiter, penalty=penalty)
         else:
-            it = mu_solve_in_library(y, m, x, Dd, lik, tol, maxiter, beta=beta)
+            it = mu_solve_in_library(y, m, x, Dd, lik, tol, maxiter, beta=beta, penalty=penalty)
         return it, Dd, x
     if method == 'hals':
-        backend = HipHalsStepBackend(y, x, Dd)
+        backend = HipHalsStepBackend(y, x, Dd, penalty=penalty)
     else:
-        backend = HipStepBackend(y, m, x, Dd, lik, beta=beta)
-    it, Dout = mu_loop(backend, Dd, tol, maxiter, group=group, world_size=world,
-                       new_like=torch.empty_like)
+        backend = HipStepBackend(y, m, x, Dd, lik, beta=beta, penalty=penalty)
+    try:
+        it, Dout = mu_loop(backend, Dd, tol, maxiter, group=group, world_size=world,
+                           new_like=torch.empty_like)
+    finally:
+        if penalty != (0.0, 0.0):
+            _nmf._set_penalty(_arrays.lib_handle(Dd)[1], (0.0, 0.0))
     return it, Dout, backend.x
 
 

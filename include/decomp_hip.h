@@ -368,6 +368,18 @@ int dcp_nmf_gauss_logp_f64(dcp_handle* h, const double* Y, const double* mask, c
  *   x: pos = R1 D^T, neg = R2 D^T  [N, K]      D: pos = X^T R1, neg = X^T R2  [K, F]
  * statistics width 2F ([X^T R1 | X^T R2]), mask or not.  No Gram identity applies. */
 int dcp_set_nmf_beta(dcp_handle* h, double beta);
+/* L1 / L2 penalty on the NMF codes on this handle (default 0, 0): the objective gains  l1 sum X + l2/2 |X|^2
+ * (no 1/N scaling; D stays unpenalised, its rows unit norm).  Handle state like dcp_set_nmf_beta, read when a
+ * call is enqueued by exactly these entries:
+ *   dcp_nmf_mu_*, dcp_nmf_mu_sharded_*, dcp_nmf_mu_stats_*, dcp_nmf_mu_stats_prepared_*   the MU x update
+ *       x <- x * max(pos, 0) / max(neg + l1 + l2 x, 1e-15)    (x before the update; pos / neg as without it)
+ *   dcp_nmf_hals_*, dcp_nmf_hals_sharded_*, dcp_nmf_hals_stats_*                           the HALS x sweep
+ *       the exact coordinate minimiser: the sweep on C = Y D^T - l1 and G = D D^T + l2 I, i.e. where
+ *       G[k,k] + l2 > 0:  X[:,k] = max(0, X[:,k] - (X G[:,k] + l2 X[:,k] - C[:,k] + l1) / (G[k,k] + l2))
+ * Every other entry ignores it (dcp_nmf_grads_*, dcp_nmf_grad_x_*, dcp_nn_cd_sweep_*, the D updates, the
+ * dictionary and lasso entries).  The D side, the statistics and the stop rule are unchanged; with both
+ * penalties 0 the unpenalised kernels run.  DCP_ERR_INVALID for a NULL handle or a negative or non-finite value. */
+int dcp_set_nmf_penalty(dcp_handle* h, double l1, double l2);
 /* sum over entries with mask != 0 of mask * d_beta(Y | X D + 1e-15) with the handle's beta, to the HOST double
  * (per-element divergence and accumulation in double, ordered second-stage sum: deterministic).  d_0 = y/v -
  * log(y/v) - 1, d_1 = y log(y/v) - y + v (0 log 0 = 0), else (y^b + (b-1) v^b - b y v^(b-1)) / (b (b-1)).
