@@ -254,4 +254,32 @@ inline int host_scratch(dcp_handle* h, size_t bytes, void** out) {
     return DCP_OK;
 }
 
+// Waits until a kernel on h->stream has stored over the `sentinel` the host put into a pinned (device-mapped) word
+// before that kernel was enqueued; *out (if given) is the word then.  Polling instead of sleeping in a blocking wait,
+// which wakes up late; a stream synchronisation is the fallback after ~2 s.  A NaN counts as stored.
+template <class W>
+inline int wait_pinned_word(dcp_handle* h, const W* word, W sentinel, W* out = nullptr) {
+    const volatile W* v = word;
+    for (long spin = 0; *v == sentinel; ++spin) {
+        if (spin == 400000000L) {
+            DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
+            break;
+        }
+        __builtin_ia32_pause();
+    }
+    if (out) *out = *v;
+    return DCP_OK;
+}
+
+// Sum of n doubles in device memory (per-workgroup partials, added in order): copied to `pinned`, one stream
+// synchronisation.
+inline int read_partial_sum(dcp_handle* h, const double* part_dev, int n, double* pinned, double* sum) {
+    DCP_HIP_OK(h, hipMemcpyAsync(pinned, part_dev, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
+    double acc = 0.0;
+    for (int i = 0; i < n; ++i) acc += pinned[i];
+    *sum = acc;
+    return DCP_OK;
+}
+
 }  // namespace dcp

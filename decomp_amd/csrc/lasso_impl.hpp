@@ -849,18 +849,9 @@ __global__ void flag_publish_kernel(int* __restrict__ flag, int* __restrict__ ho
     }
 }
 
-// Wait for flag_publish_kernel's store: the word was set to the sentinel -1 before that kernel was enqueued.  Polling
-// instead of sleeping in a blocking wait, which wakes up late (measured: the GPU sat idle ~2 ms per dictionary step
-// once the host ran a step ahead); a stream synchronisation is the fallback after ~2 s.
-inline int poll_host_flag(dcp_handle* h, int* host_flag) {
-    volatile int* vf = host_flag;
-    for (long spin = 0; spin < 400000000L; ++spin) {
-        if (*vf != -1) return DCP_OK;
-        __builtin_ia32_pause();
-    }
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    return DCP_OK;
-}
+// Wait for flag_publish_kernel's store: the word was set to the sentinel -1 before that kernel was enqueued (polling:
+// the GPU sat idle ~2 ms per dictionary step behind a blocking wait once the host ran a step ahead).
+inline int poll_host_flag(dcp_handle* h, int* host_flag) { return wait_pinned_word(h, host_flag, -1); }
 
 // The dictionary step's deferred *it_out of a coordinate-descent solve (see the Gram-form loop in lasso_solve): called
 // once the rest of the step has been enqueued, when the flag has long landed.

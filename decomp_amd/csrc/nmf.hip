@@ -3,7 +3,7 @@
 #include <cmath>
 
 #include "comm.hpp"
-#include "nmf_impl.hpp"
+#include "nmf_loop.hpp"
 
 using namespace dcp;
 
@@ -12,14 +12,71 @@ namespace {
 template <class T>
 int check_nmf_args(dcp_handle* h, const T* Y, const T* X, const T* D, int64_t N, int64_t F,
                    int64_t K, int lik) {
-    if (!h) return DCP_ERR_INVALID;
-    if (!Y || !X || !D) return fail(h, DCP_ERR_INVALID, "null array pointer");
-    if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
-    if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL || F + K > 0x3fffffffLL)
-        return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
+    DCP_TRY(check_nmf_dims(h, Y, X, D, N, F, K));
     if (lik != DCP_LIK_L2 && lik != DCP_LIK_KL && lik != DCP_LIK_BETA) return fail(h, DCP_ERR_INVALID, "bad likelihood");
     return DCP_OK;
 }
+
+// One MU iteration for nmf_lagged_loop:  stats(...)  [all-reduce of `stats` across ranks]  update(...)
+template <class T>
+struct MuStep {
+    const T* Y;
+    const T* mask;
+    NmfShape<T> s;
+    bool sharded;
+    NmfStatsWs<T> ws;
+    NmfUpdateWs<T> wu;
+    T* stats = nullptr;
+    uint32_t* mbits = nullptr;
+    int* mflag = nullptr;
+    const T* Ypre = nullptr;
+
+    int64_t W() const { return nmf_stats_width(s.F, s.K, s.lik, s.masked); }
+    bool want_bits() const { return s.masked && std::is_same<T, float>::value && s.lik == DCP_LIK_L2; }
+    void plan(WsPlan& plan) const {
+        nmf_plan_stats(plan, s, s.masked);
+        nmf_plan_update<T>(plan, s.F, s.K);
+        plan.add<T>((size_t)s.K * W());   // stats
+        if (want_bits()) {
+            plan.add<uint32_t>(mask_bits_words(s.N, s.F));
+            plan.add<int>(4);
+        }
+    }
+    int carve(dcp_handle* h) {
+        DCP_TRY(nmf_carve_stats(h, ws, s, s.masked));
+        DCP_TRY(nmf_carve_update(h, wu, s.F, s.K));
+        stats = ws_alloc<T>(h, (size_t)s.K * W());
+        if (want_bits()) {
+            mbits = ws_alloc<uint32_t>(h, mask_bits_words(s.N, s.F));
+            mflag = ws_alloc<int>(h, 4);
+        }
+        if (!stats || (want_bits() && (!mbits || !mflag)))
+            return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
+        return DCP_OK;
+    }
+    int prepare(dcp_handle* h) {
+        Ypre = Y;
+        if (!s.masked) return DCP_OK;
+        // y * mask is loop invariant (grads.py:114,124 recompute it every call)
+        int binary = 0;
+        DCP_TRY(nmf_mask_prepare<T>(h, Y, mask, s.N, s.F, ws.Ym, mbits, mflag, &binary));
+        Ypre = ws.Ym;
+        if (binary) ws.mbits = mbits;
+        return DCP_OK;
+    }
+    int iterate(dcp_handle* h, const T* Xc, T* Xn, const T* Dc, T* Dn, const NmfStopSlots<T>& slots) {
+        DCP_TRY(nmf_stats<T>(h, Ypre, mask, Xc, Xn, Dc, s, stats, ws, 3, nmf_penalty(h)));
+        if (sharded) {   // the one exchange of the step: sums over rows become sums over ranks
+            ProfScope ps(h, DCP_PROF_EXCHANGE);
+            DCP_TRY(comm_allreduce_sum(h, stats, (size_t)s.K * W(),
+                                       std::is_same<T, float>::value ? COMM_F32 : COMM_F64));
+        }
+        // max|D - D_new| reaches the host without a copy kernel: the normalisation's last-arriving workgroup stores
+        // it into the pinned (device-mapped) slot, which the stop test polls
+        return nmf_update<T>(h, stats, Dc, Dn, s.F, s.K, s.lik, s.masked, slots.md, wu, slots.md_next, slots.ticket,
+                             slots.host);
+    }
+};
 
 template <class T>
 int nmf_mu_solve(dcp_handle* h, const T* Y, const T* mask, T* X, T* D, int64_t N, int64_t F,
@@ -30,146 +87,34 @@ int nmf_mu_solve(dcp_handle* h, const T* Y, const T* mask, T* X, T* D, int64_t N
     if (sharded && !comm_active(h))
         return fail(h, DCP_ERR_COMM, "dcp_nmf_mu_sharded_* needs a communicator (dcp_comm_init)");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    const bool masked = mask != nullptr;
-    NmfShape<T> s{N, F, K, lik, masked};
-    const int64_t W = nmf_stats_width(F, K, lik, masked);
-    const bool want_resid = resid_trace != nullptr;
-    const bool gram = (lik == DCP_LIK_L2 && !masked);
-    const int resid_blocks = 1024;
-
-    WsPlan plan;
-    nmf_plan_stats(plan, s, masked);
-    nmf_plan_update<T>(plan, F, K);
-    plan.add<T>((size_t)K * W);   // stats
-    plan.add<T>((size_t)K * F);   // second D buffer
-    plan.add<T>((size_t)N * K);   // second x buffer
-    plan.add<T>(2);               // max|dD| of the two iterations in flight
-    plan.add<unsigned int>(4);    // arrival ticket of the normalisation's workgroups
-    const bool want_bits = masked && std::is_same<T, float>::value && lik == DCP_LIK_L2;
-    if (want_bits) {
-        plan.add<uint32_t>(mask_bits_words(N, F));
-        plan.add<int>(4);
-    }
-    if (want_resid) {
-        if (gram) plan.add<T>((size_t)N * F);
-        plan.add<double>(resid_blocks);
-    }
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    NmfStatsWs<T> ws;
-    NmfUpdateWs<T> wu;
-    DCP_TRY(nmf_carve_stats(h, ws, s, masked));
-    DCP_TRY(nmf_carve_update(h, wu, F, K));
-    T* stats = ws_alloc<T>(h, (size_t)K * W);
-    T* D2 = ws_alloc<T>(h, (size_t)K * F);
-    T* X2 = ws_alloc<T>(h, (size_t)N * K);
-    T* maxdiff_dev = ws_alloc<T>(h, 2);
-    unsigned int* ticket = ws_alloc<unsigned int>(h, 4);
-    uint32_t* mbits = nullptr;
-    int* mflag = nullptr;
-    if (want_bits) {
-        mbits = ws_alloc<uint32_t>(h, mask_bits_words(N, F));
-        mflag = ws_alloc<int>(h, 4);
-        if (!mbits || !mflag) return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
-    }
-    T* resid_tmp = nullptr;
-    double* resid_part = nullptr;
-    if (want_resid) {
-        resid_tmp = gram ? ws_alloc<T>(h, (size_t)N * F) : ws.f;
-        resid_part = ws_alloc<double>(h, resid_blocks);
-    }
-    if (!stats || !D2 || !X2 || !maxdiff_dev || !ticket || (want_resid && (!resid_tmp || !resid_part)))
-        return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, sizeof(double) * (resid_blocks + 4), &hostv));
-    T* host_md = reinterpret_cast<T*>(hostv);             // [2]
-    double* host_part = reinterpret_cast<double*>(hostv) + 2;
-    // The stop test polls the pinned word the normalisation's last workgroup stores max|dD| into (a sentinel of -1
-    // is put there before the iteration is enqueued; max|dD| >= 0 or NaN).  No event in the loop: the barrier packet of
-    // a hipEventRecord (system-scope release) cost ~6 us of idle GPU per iteration behind the normalisation.
-    auto wait_md = [&](int slot, T* out) -> int {
-        volatile T* v = host_md + slot;
-        bool seen = false;
-        for (long spin = 0; spin < 400000000L; ++spin) {
-            if (!(*v == T(-1))) { seen = true; break; }
-            __builtin_ia32_pause();
-        }
-        if (!seen) DCP_HIP_OK(h, hipStreamSynchronize(h->stream));   // ~2 s of polling: fall back to a blocking wait
-        *out = *v;
-        return DCP_OK;
-    };
-
-    const T* Ypre = Y;
-    if (masked) {  // y * mask is loop invariant (grads.py:114,124 recompute it every call)
-        int binary = 0;
-        DCP_TRY(nmf_mask_prepare<T>(h, Y, mask, N, F, ws.Ym, mbits, mflag, &binary));
-        Ypre = ws.Ym;
-        if (binary) ws.mbits = mbits;
-    }
-    DCP_HIP_OK(h, hipMemsetAsync(maxdiff_dev, 0, 2 * sizeof(T), h->stream));
-    DCP_HIP_OK(h, hipMemsetAsync(ticket, 0, 4 * sizeof(unsigned int), h->stream));
-
-    // Iteration `it` reads (x_{it-1}, D_{it-1}) from (Xc, Dc) and writes (x_it, D_it) to (Xn, Dn);
-    // its max|dD| lands in host slot it&1.  The stop test of iteration it-1
-    // (batch_mu.py:22) is evaluated AFTER iteration it has been enqueued, so the GPU never
-    // idles on the host; when it-1 turns out to have converged, iteration it is discarded:
-    // its inputs (Xc, Dc) are exactly the state the reference returns.
-    T* Xc = X;  T* Xn = X2;
-    T* Dc = D;  T* Dn = D2;
-    int result_it = maxiter;   // batch_mu.py:26
-    T md_last = T(0);
-    bool converged = false;
-    for (int it = 1; it < maxiter; ++it) {  // batch_mu.py:16
-        const int slot = it & 1;
-        DCP_TRY(nmf_stats<T>(h, Ypre, mask, Xc, Xn, Dc, s, stats, ws, 3, nmf_penalty(h)));
-        if (sharded) {   // the one exchange of the step: sums over rows become sums over ranks
-            ProfScope ps(h, DCP_PROF_EXCHANGE);
-            DCP_TRY(comm_allreduce_sum(h, stats, (size_t)K * W,
-                                       std::is_same<T, float>::value ? COMM_F32 : COMM_F64));
-        }
-        // max|D - D_new| reaches the host without a copy kernel: the normalisation's last-arriving workgroup stores
-        // it into the pinned (device-mapped) slot, which the stop test polls
-        *reinterpret_cast<volatile T*>(host_md + slot) = T(-1);
-        DCP_TRY(nmf_update<T>(h, stats, Dc, Dn, F, K, lik, masked, maxdiff_dev + slot, wu,
-                              maxdiff_dev + (slot ^ 1), ticket, host_md + slot));
-        if (want_resid) {   // parity/debug mode: synchronous
-            DCP_TRY(nmf_residual<T>(h, Y, mask, Xn, Dn, N, F, K, resid_tmp, resid_part,
-                                    resid_blocks));
-            DCP_HIP_OK(h, hipMemcpyAsync(host_part, resid_part, sizeof(double) * resid_blocks,
-                                         hipMemcpyDeviceToHost, h->stream));
-            DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-            double acc = 0.0;
-            for (int i = 0; i < resid_blocks; ++i) acc += host_part[i];
-            resid_trace[it - 1] = (T)sqrt(acc);
-        }
-        if (it > 1) {   // stop test of the PREVIOUS iteration
-            DCP_TRY(wait_md(slot ^ 1, &md_last));
-            if (md_last < tol) {   // a NaN compares false, as in NumPy
-                result_it = it - 1;
-                converged = true;
-                break;             // (Xc, Dc) hold x_{it-1} and D_new of iteration it-1
-            }
-        }
-        T* t = Xc; Xc = Xn; Xn = t;
-        t = Dc; Dc = Dn; Dn = t;
-    }
-    if (!converged && maxiter > 1) {   // stop test of the last iteration
-        const int slot = (maxiter - 1) & 1;
-        DCP_TRY(wait_md(slot, &md_last));
-        if (md_last < tol) result_it = maxiter - 1;
-    }
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));   // drain (incl. a discarded iteration)
-    if (Xc != X)
-        DCP_HIP_OK(h, hipMemcpyAsync(X, Xc, sizeof(T) * (size_t)N * K, hipMemcpyDeviceToDevice,
-                                     h->stream));
-    if (Dc != D)
-        DCP_HIP_OK(h, hipMemcpyAsync(D, Dc, sizeof(T) * (size_t)K * F, hipMemcpyDeviceToDevice,
-                                     h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    *it_out = result_it;
-    if (last_maxdiff) *last_maxdiff = md_last;
-    return DCP_OK;
+    MuStep<T> step{Y, mask, NmfShape<T>{N, F, K, lik, mask != nullptr}, sharded};
+    return nmf_lagged_loop<T>(h, step, Y, mask, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, resid_trace);
 }
+
+// [N,F] scratch and per-workgroup double partials of the scalar read-backs (residual, log-likelihood, divergence),
+// with the pinned words the partials are summed from.
+template <class T>
+struct NmfScalarWs {
+    static constexpr int blocks = 1024;
+    T* tmp = nullptr;
+    double* part = nullptr;
+    double* host = nullptr;
+    int reserve(dcp_handle* h, int64_t N, int64_t F) {
+        WsPlan plan;
+        plan.add<T>((size_t)N * F);
+        plan.add<double>(blocks);
+        DCP_TRY(ws_reserve(h, plan.total));
+        ws_reset(h);
+        tmp = ws_alloc<T>(h, (size_t)N * F);
+        part = ws_alloc<double>(h, blocks);
+        if (!tmp || !part) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+        void* hostv = nullptr;
+        DCP_TRY(host_scratch(h, sizeof(double) * blocks, &hostv));
+        host = reinterpret_cast<double*>(hostv);
+        return DCP_OK;
+    }
+    int sum(dcp_handle* h, double* out) const { return read_partial_sum(h, part, blocks, host, out); }
+};
 
 template <class T>
 int nmf_mu_stats_api(dcp_handle* h, const T* Y, const T* mask, const T* X, T* X_out, const T* D,
@@ -185,13 +130,8 @@ int nmf_mu_stats_api(dcp_handle* h, const T* Y, const T* mask, const T* X, T* X_
     ws_reset(h);
     NmfStatsWs<T> ws;
     DCP_TRY(nmf_carve_stats(h, ws, s, masked));
-    const T* Ypre = Y;
-    if (masked) {
-        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for(N * F)), dim3(256), 0, h->stream, Y,
-                           mask, (long)N, (long)F, (long)F, ws.Ym);
-        DCP_HIP_OK(h, hipGetLastError());
-        Ypre = ws.Ym;
-    }
+    const T* Ypre = nullptr;
+    DCP_TRY(nmf_premask<T>(h, Y, mask, N, F, ws.Ym, &Ypre));
     return nmf_stats<T>(h, Ypre, mask, X, X_out, D, s, stats, ws, 3, nmf_penalty(h));
 }
 
@@ -253,24 +193,11 @@ int nmf_residual_api(dcp_handle* h, const T* Y, const T* mask, const T* X, const
     DCP_TRY(check_nmf_args(h, Y, X, D, N, F, K, DCP_LIK_L2));
     if (!out) return fail(h, DCP_ERR_INVALID, "out is null");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    const int blocks = 1024;
-    WsPlan plan;
-    plan.add<T>((size_t)N * F);
-    plan.add<double>(blocks);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    T* tmp = ws_alloc<T>(h, (size_t)N * F);
-    double* part = ws_alloc<double>(h, blocks);
-    if (!tmp || !part) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, sizeof(double) * blocks, &hostv));
-    DCP_TRY(nmf_residual<T>(h, Y, mask, X, D, N, F, K, tmp, part, blocks));
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, part, sizeof(double) * blocks, hipMemcpyDeviceToHost,
-                                 h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    double acc = 0.0;
-    for (int i = 0; i < blocks; ++i) acc += reinterpret_cast<double*>(hostv)[i];
-    *out = sqrt(acc);
+    NmfScalarWs<T> w;
+    DCP_TRY(w.reserve(h, N, F));
+    DCP_TRY(nmf_residual<T>(h, Y, mask, X, D, N, F, K, w.tmp, w.part, w.blocks));
+    DCP_TRY(w.sum(h, out));
+    *out = sqrt(*out);
     return DCP_OK;
 }
 
@@ -296,13 +223,8 @@ int nmf_grads_api(dcp_handle* h, const T* Y, const T* mask, T* X, const T* D, in
     DCP_TRY(nmf_carve_stats(h, ws, s, masked));
     T* stats = ws_alloc<T>(h, (size_t)K * W);
     if (!stats) return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
-    const T* Ypre = Y;
-    if (masked) {
-        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for(N * F)), dim3(256), 0, h->stream, Y,
-                           mask, (long)N, (long)F, (long)F, ws.Ym);
-        DCP_HIP_OK(h, hipGetLastError());
-        Ypre = ws.Ym;
-    }
+    const T* Ypre = nullptr;
+    DCP_TRY(nmf_premask<T>(h, Y, mask, N, F, ws.Ym, &Ypre));
     for (int i = 0; i < n_x_updates; ++i)
         DCP_TRY(nmf_stats<T>(h, Ypre, mask, X, X, D, s, stats, ws, 1));
     DCP_TRY(nmf_stats<T>(h, Ypre, mask, X, X, D, s, stats, ws, 2));
@@ -336,13 +258,8 @@ int nmf_grad_x_api(dcp_handle* h, const T* Y, const T* mask, const T* X, const T
     ws_reset(h);
     NmfStatsWs<T> ws;
     DCP_TRY(nmf_carve_stats(h, ws, s, masked));
-    const T* Ypre = Y;
-    if (masked) {
-        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for(N * F)), dim3(256), 0, h->stream, Y, mask,
-                           (long)N, (long)F, (long)F, ws.Ym);
-        DCP_HIP_OK(h, hipGetLastError());
-        Ypre = ws.Ym;
-    }
+    const T* Ypre = nullptr;
+    DCP_TRY(nmf_premask<T>(h, Y, mask, N, F, ws.Ym, &Ypre));
     return nmf_grad_x<T>(h, Ypre, mask, X, D, s, grad_pos, grad_neg, ws);
 }
 
@@ -353,29 +270,15 @@ int nmf_gauss_logp_api(dcp_handle* h, const T* Y, const T* mask, const T* X, con
     DCP_TRY(check_nmf_args(h, Y, X, D, N, F, K, DCP_LIK_L2));
     if (!out) return fail(h, DCP_ERR_INVALID, "out is null");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    const int blocks = 1024;
-    WsPlan plan;
-    plan.add<T>((size_t)N * F);
-    plan.add<double>(blocks);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    T* tmp = ws_alloc<T>(h, (size_t)N * F);
-    double* part = ws_alloc<double>(h, blocks);
-    if (!tmp || !part) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, sizeof(double) * blocks, &hostv));
+    NmfScalarWs<T> w;
+    DCP_TRY(w.reserve(h, N, F));
     GemmArgs<T> a;
     a.A = X; a.lda = K; a.B = D; a.ldb = F; a.M = (int)N; a.N = (int)F; a.K = (int)K;
-    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiResidual<T>{Y, F, nullptr, 0, tmp, F})));   // d = y - x D
-    hipLaunchKernelGGL((gauss_logp_partial_kernel<T>), dim3(blocks), dim3(256), 0, h->stream, (const T*)tmp,
-                       mask, (long)N * F, 1.0 / scale, log(scale) + 3.14159265358979323846 * 0.5, part);
+    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiResidual<T>{Y, F, nullptr, 0, w.tmp, F})));   // d = y - x D
+    hipLaunchKernelGGL((gauss_logp_partial_kernel<T>), dim3(w.blocks), dim3(256), 0, h->stream, (const T*)w.tmp,
+                       mask, (long)N * F, 1.0 / scale, log(scale) + 3.14159265358979323846 * 0.5, w.part);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, part, sizeof(double) * blocks, hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    double acc = 0.0;
-    for (int i = 0; i < blocks; ++i) acc += reinterpret_cast<double*>(hostv)[i];
-    *out = acc;
-    return DCP_OK;
+    return w.sum(h, out);
 }
 
 // sum M o d_beta(Y | X D + 1e-15) with the handle's beta, to the host (accumulated in double).
@@ -385,24 +288,10 @@ int nmf_beta_divergence_api(dcp_handle* h, const T* Y, const T* mask, const T* X
     DCP_TRY(check_nmf_args(h, Y, X, D, N, F, K, DCP_LIK_BETA));
     if (!out) return fail(h, DCP_ERR_INVALID, "out is null");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    const int blocks = 1024;
-    WsPlan plan;
-    plan.add<T>((size_t)N * F);
-    plan.add<double>(blocks);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    T* tmp = ws_alloc<T>(h, (size_t)N * F);
-    double* part = ws_alloc<double>(h, blocks);
-    if (!tmp || !part) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, sizeof(double) * blocks, &hostv));
-    DCP_TRY(nmf_beta_divergence<T>(h, Y, mask, X, D, N, F, K, h->nmf_beta, tmp, part, blocks));
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, part, sizeof(double) * blocks, hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    double acc = 0.0;
-    for (int i = 0; i < blocks; ++i) acc += reinterpret_cast<double*>(hostv)[i];
-    *out = acc;
-    return DCP_OK;
+    NmfScalarWs<T> w;
+    DCP_TRY(w.reserve(h, N, F));
+    DCP_TRY(nmf_beta_divergence<T>(h, Y, mask, X, D, N, F, K, h->nmf_beta, w.tmp, w.part, w.blocks));
+    return w.sum(h, out);
 }
 
 // D_new = l2_strict(rule(D, P, Q)) and max|D - D_new| (host):

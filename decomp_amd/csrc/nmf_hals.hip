@@ -5,21 +5,11 @@
 
 #include "comm.hpp"
 #include "nmf_hals.hpp"
-#include "nmf_impl.hpp"
+#include "nmf_loop.hpp"
 
 using namespace dcp;
 
 namespace {
-
-template <class T>
-int check_hals_args(dcp_handle* h, const T* Y, const T* X, const T* D, int64_t N, int64_t F, int64_t K) {
-    if (!h) return DCP_ERR_INVALID;
-    if (!Y || !X || !D) return fail(h, DCP_ERR_INVALID, "null array pointer");
-    if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
-    if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL || F + K > 0x3fffffffLL)
-        return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
-    return DCP_OK;
-}
 
 int sweep_rc(dcp_handle* h, hipError_t e) {
     if (e != hipSuccess) return fail(h, DCP_ERR_HIP, std::string("launch failed: ") + hipGetErrorString(e));
@@ -105,126 +95,57 @@ int hals_normalize_rescale(dcp_handle* h, const T* U, const T* Dc, T* Dn, T* X, 
     return DCP_OK;
 }
 
+// One HALS iteration for nmf_lagged_loop:  hals_x_side  [all-reduce of `stats`]  hals_d_sweep  normalise + rescale
+template <class T>
+struct HalsStep {
+    const T* Y;
+    NmfShape<T> s;
+    NmfPenalty pen;
+    bool sharded;
+    NmfStatsWs<T> ws;
+    T* stats = nullptr;
+    T* U = nullptr;     // the swept, not yet normalised D
+    T* nrm = nullptr;   // atom norms
+
+    void plan(WsPlan& plan) const {
+        nmf_plan_stats(plan, s, false);
+        plan.add<T>((size_t)s.K * (s.F + s.K));
+        plan.add<T>((size_t)s.K * s.F);
+        plan.add<T>((size_t)s.K);
+    }
+    int carve(dcp_handle* h) {
+        DCP_TRY(nmf_carve_stats(h, ws, s, false));
+        stats = ws_alloc<T>(h, (size_t)s.K * (s.F + s.K));
+        U = ws_alloc<T>(h, (size_t)s.K * s.F);
+        nrm = ws_alloc<T>(h, (size_t)s.K);
+        if (!stats || !U || !nrm) return fail(h, DCP_ERR_INTERNAL, "hals workspace plan mismatch");
+        return DCP_OK;
+    }
+    int prepare(dcp_handle*) { return DCP_OK; }
+    int iterate(dcp_handle* h, const T* Xc, T* Xn, const T* Dc, T* Dn, const NmfStopSlots<T>& slots) {
+        DCP_TRY(hals_x_side<T>(h, Y, Xc, Xn, Dc, s, stats, ws, pen));
+        if (sharded) {   // the one exchange of the step: the D sweep reads sums over all ranks' rows
+            ProfScope ps(h, DCP_PROF_EXCHANGE);
+            DCP_TRY(comm_allreduce_sum(h, stats, (size_t)s.K * (s.F + s.K),
+                                       std::is_same<T, float>::value ? COMM_F32 : COMM_F64));
+        }
+        DCP_TRY(hals_d_sweep<T>(h, Dc, U, s.F, s.K, stats));
+        return hals_normalize_rescale<T>(h, U, Dc, Dn, Xn, s.N, s.F, s.K, nrm, slots.md, slots.md_next, slots.ticket,
+                                         slots.host);
+    }
+};
+
 template <class T>
 int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, int64_t K, T tol, int maxiter,
                    int* it_out, T* last_maxdiff, T* resid_trace, bool sharded = false) {
-    DCP_TRY(check_hals_args(h, Y, X, D, N, F, K));
+    DCP_TRY(check_nmf_dims(h, Y, X, D, N, F, K));
     if (!it_out) return fail(h, DCP_ERR_INVALID, "it_out is null");
     if (sharded && !comm_active(h))
         return fail(h, DCP_ERR_COMM, "dcp_nmf_hals_sharded_* needs a communicator (dcp_comm_init)");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    NmfShape<T> s{N, F, K, DCP_LIK_L2, false};
-    const NmfPenalty pen = nmf_penalty(h);
-    const int64_t W = F + K;
-    const bool want_resid = resid_trace != nullptr;
-    const int resid_blocks = 1024;
-
-    WsPlan plan;
-    nmf_plan_stats(plan, s, false);
-    plan.add<T>((size_t)K * W);   // stats
-    plan.add<T>((size_t)K * F);   // U: the swept, not yet normalised D
-    plan.add<T>((size_t)K * F);   // second D buffer
-    plan.add<T>((size_t)N * K);   // second x buffer
-    plan.add<T>((size_t)K);       // atom norms
-    plan.add<T>(2);               // max|dD| of the two iterations in flight
-    plan.add<unsigned int>(4);    // arrival ticket of the normalisation's workgroups
-    if (want_resid) {
-        plan.add<T>((size_t)N * F);
-        plan.add<double>(resid_blocks);
-    }
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    NmfStatsWs<T> ws;
-    DCP_TRY(nmf_carve_stats(h, ws, s, false));
-    T* stats = ws_alloc<T>(h, (size_t)K * W);
-    T* U = ws_alloc<T>(h, (size_t)K * F);
-    T* D2 = ws_alloc<T>(h, (size_t)K * F);
-    T* X2 = ws_alloc<T>(h, (size_t)N * K);
-    T* nrm = ws_alloc<T>(h, (size_t)K);
-    T* maxdiff_dev = ws_alloc<T>(h, 2);
-    unsigned int* ticket = ws_alloc<unsigned int>(h, 4);
-    T* resid_tmp = nullptr;
-    double* resid_part = nullptr;
-    if (want_resid) {
-        resid_tmp = ws_alloc<T>(h, (size_t)N * F);
-        resid_part = ws_alloc<double>(h, resid_blocks);
-    }
-    if (!stats || !U || !D2 || !X2 || !nrm || !maxdiff_dev || !ticket || (want_resid && (!resid_tmp || !resid_part)))
-        return fail(h, DCP_ERR_INTERNAL, "hals workspace plan mismatch");
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, sizeof(double) * (resid_blocks + 4), &hostv));
-    T* host_md = reinterpret_cast<T*>(hostv);             // [2]
-    double* host_part = reinterpret_cast<double*>(hostv) + 2;
-    // the stop test polls the pinned word the normalisation's last workgroup stores max|dD| into (the MU loop's
-    // protocol: a sentinel of -1 is put there before the iteration is enqueued; max|dD| >= 0 or NaN)
-    auto wait_md = [&](int slot, T* out) -> int {
-        volatile T* v = host_md + slot;
-        bool seen = false;
-        for (long spin = 0; spin < 400000000L; ++spin) {
-            if (!(*v == T(-1))) { seen = true; break; }
-            __builtin_ia32_pause();
-        }
-        if (!seen) DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-        *out = *v;
-        return DCP_OK;
-    };
-    DCP_HIP_OK(h, hipMemsetAsync(maxdiff_dev, 0, 2 * sizeof(T), h->stream));
-    DCP_HIP_OK(h, hipMemsetAsync(ticket, 0, 4 * sizeof(unsigned int), h->stream));
-
-    // Iteration `it` reads (x_{it-1}, D_{it-1}) from (Xc, Dc) and writes (x_it, D_it) to (Xn, Dn); the stop test
-    // of iteration it-1 is evaluated after iteration it has been enqueued, and iteration it is discarded when
-    // it-1 has converged -- exactly the MU loop (nmf.hip, nmf_mu_solve).
-    T* Xc = X;  T* Xn = X2;
-    T* Dc = D;  T* Dn = D2;
-    int result_it = maxiter;
-    T md_last = T(0);
-    bool converged = false;
-    for (int it = 1; it < maxiter; ++it) {
-        const int slot = it & 1;
-        DCP_TRY(hals_x_side<T>(h, Y, Xc, Xn, Dc, s, stats, ws, pen));
-        if (sharded) {   // the one exchange of the step: the D sweep reads sums over all ranks' rows
-            ProfScope ps(h, DCP_PROF_EXCHANGE);
-            DCP_TRY(comm_allreduce_sum(h, stats, (size_t)K * W,
-                                       std::is_same<T, float>::value ? COMM_F32 : COMM_F64));
-        }
-        DCP_TRY(hals_d_sweep<T>(h, Dc, U, F, K, stats));
-        *reinterpret_cast<volatile T*>(host_md + slot) = T(-1);
-        DCP_TRY(hals_normalize_rescale<T>(h, U, Dc, Dn, Xn, N, F, K, nrm, maxdiff_dev + slot,
-                                          maxdiff_dev + (slot ^ 1), ticket, host_md + slot));
-        if (want_resid) {   // parity/debug mode: synchronous
-            DCP_TRY(nmf_residual<T>(h, Y, nullptr, Xn, Dn, N, F, K, resid_tmp, resid_part, resid_blocks));
-            DCP_HIP_OK(h, hipMemcpyAsync(host_part, resid_part, sizeof(double) * resid_blocks,
-                                         hipMemcpyDeviceToHost, h->stream));
-            DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-            double acc = 0.0;
-            for (int i = 0; i < resid_blocks; ++i) acc += host_part[i];
-            resid_trace[it - 1] = (T)sqrt(acc);
-        }
-        if (it > 1) {   // stop test of the PREVIOUS iteration
-            DCP_TRY(wait_md(slot ^ 1, &md_last));
-            if (md_last < tol) {   // a NaN compares false
-                result_it = it - 1;
-                converged = true;
-                break;
-            }
-        }
-        T* t = Xc; Xc = Xn; Xn = t;
-        t = Dc; Dc = Dn; Dn = t;
-    }
-    if (!converged && maxiter > 1) {
-        const int slot = (maxiter - 1) & 1;
-        DCP_TRY(wait_md(slot, &md_last));
-        if (md_last < tol) result_it = maxiter - 1;
-    }
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));   // drain (incl. a discarded iteration)
-    if (Xc != X)
-        DCP_HIP_OK(h, hipMemcpyAsync(X, Xc, sizeof(T) * (size_t)N * K, hipMemcpyDeviceToDevice, h->stream));
-    if (Dc != D)
-        DCP_HIP_OK(h, hipMemcpyAsync(D, Dc, sizeof(T) * (size_t)K * F, hipMemcpyDeviceToDevice, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    *it_out = result_it;
-    if (last_maxdiff) *last_maxdiff = md_last;
-    return DCP_OK;
+    HalsStep<T> step{Y, NmfShape<T>{N, F, K, DCP_LIK_L2, false}, nmf_penalty(h), sharded};
+    return nmf_lagged_loop<T>(h, step, Y, (const T*)nullptr, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff,
+                              resid_trace);
 }
 
 // dcp_nmf_hals_stats_*: the x side of one iteration, up to the exchange point.  Same kernels in the same order
@@ -232,7 +153,7 @@ int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, 
 template <class T>
 int nmf_hals_stats_api(dcp_handle* h, const T* Y, const T* X, T* X_out, const T* D, int64_t N, int64_t F, int64_t K,
                        T* stats) {
-    DCP_TRY(check_hals_args(h, Y, X, D, N, F, K));
+    DCP_TRY(check_nmf_dims(h, Y, X, D, N, F, K));
     if (!stats || !X_out) return fail(h, DCP_ERR_INVALID, "stats / X_out is null");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     NmfShape<T> s{N, F, K, DCP_LIK_L2, false};
@@ -249,11 +170,8 @@ int nmf_hals_stats_api(dcp_handle* h, const T* Y, const T* X, T* X_out, const T*
 template <class T>
 int nmf_hals_update_api(dcp_handle* h, const T* stats, const T* D, T* D_new, T* X, int64_t N, int64_t F,
                         int64_t K, T* maxdiff_dev, T* maxdiff_next) {
-    if (!h) return DCP_ERR_INVALID;
-    if (!stats || !D || !D_new || !X || !maxdiff_dev) return fail(h, DCP_ERR_INVALID, "null pointer");
-    if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
-    if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL || F + K > 0x3fffffffLL)
-        return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
+    if (h && (!D_new || !maxdiff_dev)) return fail(h, DCP_ERR_INVALID, "null pointer");
+    DCP_TRY(check_nmf_dims(h, stats, D, X, N, F, K, "null pointer"));
     DCP_HIP_OK(h, hipSetDevice(h->device));
     // shares the arena with dcp_nmf_hals_stats_*: its temporaries are dead by now (same stream)
     WsPlan plan;

@@ -51,6 +51,17 @@ struct NmfShape {
     bool masked;
 };
 
+// The checks every entry point on an [N,F] = [N,K] [K,F] problem starts with: handle, three arrays, sizes.
+inline int check_nmf_dims(dcp_handle* h, const void* a, const void* b, const void* c, int64_t N, int64_t F, int64_t K,
+                          const char* null_msg = "null array pointer") {
+    if (!h) return DCP_ERR_INVALID;
+    if (!a || !b || !c) return fail(h, DCP_ERR_INVALID, null_msg);
+    if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
+    if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL || F + K > 0x3fffffffLL)
+        return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
+    return DCP_OK;
+}
+
 // ---- workspace ---------------------------------------------------------------------
 template <class T>
 struct NmfStatsWs {
@@ -573,15 +584,26 @@ inline int nmf_beta_divergence(dcp_handle* h, const T* Y, const T* mask, const T
 
 namespace dcp {
 
+// *Ypre = Y o mask, written to Ym, or Y itself without a mask: what nmf_stats / nmf_grad_x take as their data.
+template <class T>
+inline int nmf_premask(dcp_handle* h, const T* Y, const T* mask, int64_t N, int64_t F, T* Ym, const T** Ypre) {
+    *Ypre = Y;
+    if (mask == nullptr) return DCP_OK;
+    hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for(N * F)), dim3(256), 0, h->stream, Y, mask,
+                       (long)N, (long)F, (long)F, Ym);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    *Ypre = Ym;
+    return DCP_OK;
+}
+
 // Loop-invariant part of a masked solve: Ym = Y o M (grads.py:114,124 recompute it every call) and,
 // for float, the row-bit image of a 0/1 mask.  *binary (host) tells whether `bits` may stand in for
 // the mask.  Synchronises the stream once (the flag read-back).
 template <class T>
 inline int nmf_mask_prepare(dcp_handle* h, const T* Y, const T* mask, int64_t N, int64_t F, T* Ym,
                             uint32_t* bits, int* flag_dev, int* binary) {
-    hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for(N * F)), dim3(256), 0, h->stream, Y, mask,
-                       (long)N, (long)F, (long)F, Ym);
-    DCP_LAUNCH_OK(h, hipGetLastError());
+    const T* Ypre = nullptr;
+    DCP_TRY(nmf_premask<T>(h, Y, mask, N, F, Ym, &Ypre));
     *binary = 0;
     if (!std::is_same<T, float>::value || bits == nullptr) return DCP_OK;
     void* hostv = nullptr;

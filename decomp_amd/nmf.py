@@ -289,35 +289,44 @@ def _solve_streamed(y, D_dev, x_given, tol, minibatch, maxiter, method, likeliho
     return it, Dout, xout
 
 
-def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None, beta=None, penalty=(0.0, 0.0)):
-    """batch_mu.solve on device arrays; x and D are updated in place.  Returns it.  ``beta`` goes with
-    lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes."""
+def _loop_call(method, sharded, y, mask, x, D, lik, beta, penalty, tol, maxiter, resid_trace=None):
+    """One full-batch solver loop inside the library, ``dcp_nmf_{mu,hals}[_sharded]_*``, on device arrays; x and D
+    are updated in place.  Returns it.  The hals entries take neither mask nor likelihood (``lik`` None), the
+    sharded ones no residual trace.  ``beta`` goes with lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes,
+    set on the handle for this call alone."""
     from .nmf_methods.grads import set_beta
     lib, h = _arrays.lib_handle(D)
-    sfx = _arrays.suffix(D)
-    N, F = y.shape
-    K = D.shape[0]
-    ctype = ctypes.c_float if sfx == 'f32' else ctypes.c_double
+    name = 'dcp_nmf_%s_%s%s' % (method, 'sharded_' if sharded else '', _arrays.suffix(D))
+    ctype = ctypes.c_float if name.endswith('f32') else ctypes.c_double
     it = ctypes.c_int(0)
     last = ctype(0)
+    mu = method == 'mu'
+    args = [h, _arrays.ptr(y)] + ([_arrays.ptr(mask)] if mu else []) + [_arrays.ptr(x), _arrays.ptr(D)]
+    args += list(y.shape) + [D.shape[0]] + ([lik] if mu else [])
+    args += [ctype(tol), int(maxiter), ctypes.byref(it), ctypes.byref(last)]
     trace = None
-    if resid_trace is not None:
-        trace = (ctype * max(int(maxiter), 1))()
-    fn = getattr(lib, 'dcp_nmf_mu_' + sfx)
+    if not sharded:
+        if resid_trace is not None:
+            trace = (ctype * max(int(maxiter), 1))()
+        args.append(trace)
     set_beta(h, lik, beta)
     _set_penalty(h, penalty)
     try:
-        rc = fn(h, _arrays.ptr(y), _arrays.ptr(mask), _arrays.ptr(x), _arrays.ptr(D),
-                N, F, K, lik, ctype(tol), int(maxiter), ctypes.byref(it), ctypes.byref(last),
-                trace)
+        rc = getattr(lib, name)(*args)
     finally:
         if penalty != (0.0, 0.0):
             _set_penalty(h, (0.0, 0.0))
-    _hip.check(h, rc, 'dcp_nmf_mu_' + sfx)
-    if resid_trace is not None:
+    _hip.check(h, rc, name)
+    if trace is not None:
         n_done = it.value if it.value < maxiter else maxiter - 1
         resid_trace.extend(float(trace[i]) for i in range(max(n_done, 0)))
     return it.value
+
+
+def _run_mu(y, mask, x, D, lik, tol, maxiter, resid_trace=None, beta=None, penalty=(0.0, 0.0)):
+    """batch_mu.solve on device arrays; x and D are updated in place.  Returns it.  ``beta`` goes with
+    lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes."""
+    return _loop_call('mu', False, y, mask, x, D, lik, beta, penalty, tol, maxiter, resid_trace)
 
 
 def _check_hals_scope(likelihood, mask):
@@ -334,29 +343,7 @@ def _run_hals(y, x, D, tol, maxiter, resid_trace=None, penalty=(0.0, 0.0)):
     """HALS (exact block coordinate descent) on device arrays, D l2_strict normalised; x and D are updated
     in place.  Same stop rule and return convention as ``_run_mu``; ``penalty`` is (l1, l2) on the codes.
     Returns it."""
-    lib, h = _arrays.lib_handle(D)
-    sfx = _arrays.suffix(D)
-    N, F = y.shape
-    K = D.shape[0]
-    ctype = ctypes.c_float if sfx == 'f32' else ctypes.c_double
-    it = ctypes.c_int(0)
-    last = ctype(0)
-    trace = None
-    if resid_trace is not None:
-        trace = (ctype * max(int(maxiter), 1))()
-    fn = getattr(lib, 'dcp_nmf_hals_' + sfx)
-    _set_penalty(h, penalty)
-    try:
-        rc = fn(h, _arrays.ptr(y), _arrays.ptr(x), _arrays.ptr(D), N, F, K, ctype(tol), int(maxiter),
-                ctypes.byref(it), ctypes.byref(last), trace)
-    finally:
-        if penalty != (0.0, 0.0):
-            _set_penalty(h, (0.0, 0.0))
-    _hip.check(h, rc, 'dcp_nmf_hals_' + sfx)
-    if resid_trace is not None:
-        n_done = it.value if it.value < maxiter else maxiter - 1
-        resid_trace.extend(float(trace[i]) for i in range(max(n_done, 0)))
-    return it.value
+    return _loop_call('hals', False, y, None, x, D, None, None, penalty, tol, maxiter, resid_trace)
 
 
 def _run_mu_user(y, mask, x_dev, D_dev, lik, tol, maxiter, kind):

@@ -146,68 +146,79 @@ def comm_allreduce_(t):
 def mu_solve_in_library(y, mask, x, D, lik, tol, maxiter, beta=None, penalty=(0.0, 0.0)):
     """``dcp_nmf_mu_sharded_*`` on this rank's rows (x and D updated in place).  Returns it.  ``beta`` goes
     with lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes (``nmf.solve``'s l1_penalty / l2_penalty)."""
-    from .nmf_methods.grads import set_beta
-    from .nmf import _set_penalty
-    lib, h = _arrays.lib_handle(D)
-    sfx = _arrays.suffix(D)
-    fn = getattr(lib, 'dcp_nmf_mu_sharded_' + sfx)
-    set_beta(h, lik, beta)
-    it = ctypes.c_int(0)
-    ctol = ctypes.c_float(tol) if sfx == 'f32' else ctypes.c_double(tol)
-    _set_penalty(h, penalty)
-    try:
-        _hip.check(h, fn(h, _arrays.ptr(y), _arrays.ptr(mask), _arrays.ptr(x), _arrays.ptr(D), y.shape[0],
-                         y.shape[1], D.shape[0], lik, ctol, int(maxiter), ctypes.byref(it), None),
-                   'dcp_nmf_mu_sharded_' + sfx)
-    finally:
-        if penalty != (0.0, 0.0):
-            _set_penalty(h, (0.0, 0.0))
-    return it.value
+    from .nmf import _loop_call
+    return _loop_call('mu', True, y, mask, x, D, lik, beta, penalty, tol, maxiter)
 
 
 def hals_solve_in_library(y, x, D, tol, maxiter, penalty=(0.0, 0.0)):
     """``dcp_nmf_hals_sharded_*`` on this rank's rows (x and D updated in place).  Returns it.  ``penalty`` as
     in ``mu_solve_in_library``."""
-    from .nmf import _set_penalty
-    lib, h = _arrays.lib_handle(D)
-    sfx = _arrays.suffix(D)
-    fn = getattr(lib, 'dcp_nmf_hals_sharded_' + sfx)
-    it = ctypes.c_int(0)
-    ctol = ctypes.c_float(tol) if sfx == 'f32' else ctypes.c_double(tol)
-    _set_penalty(h, penalty)
-    try:
-        _hip.check(h, fn(h, _arrays.ptr(y), _arrays.ptr(x), _arrays.ptr(D), y.shape[0], y.shape[1], D.shape[0],
-                         ctol, int(maxiter), ctypes.byref(it), None), 'dcp_nmf_hals_sharded_' + sfx)
-    finally:
-        if penalty != (0.0, 0.0):
-            _set_penalty(h, (0.0, 0.0))
-    return it.value
+    from .nmf import _loop_call
+    return _loop_call('hals', True, y, None, x, D, None, None, penalty, tol, maxiter)
 
 
-class HipStepBackend(object):
-    """The two halves of one MU iteration on this rank's GPU, through the C ABI.
+class _StepBackend(object):
+    """What ``mu_loop`` drives, for a method given as two ctypes calls (``_stats_call`` / ``_update_call``).
 
     x is double buffered: ``local_stats`` reads the current x and writes the next one, so
     the iteration that was enqueued speculatively (see ``mu_loop``) can be discarded with
-    ``rollback``.  ``x`` is always the buffer holding the current iterate.  ``beta`` goes with
-    lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes, set on the handle before every x step."""
+    ``rollback``.  ``x`` is always the buffer holding the current iterate.  ``penalty`` is (l1, l2) on the
+    codes, set on the handle before every x step.  max|dD| is formed in the two ping-pong words of ``maxdiff``
+    (the one of this step zero on entry, the other cleared for the next, see the C ABI) and published to a
+    pinned host slot by a copy with an event behind it."""
 
-    def __init__(self, y, mask, x, D, lik, beta=None, penalty=(0.0, 0.0)):
+    def __init__(self, y, x, D, stats_width, penalty):
         import torch
         self.torch = torch
-        self.y, self.mask, self.lik, self.beta = y, mask, lik, beta
+        self.y = y
         self.penalty = penalty
         self.x = x
         self._x_other = torch.empty_like(x)
         self.N, self.F = y.shape
         self.K = D.shape[0]
         self.sfx = _arrays.suffix(D)
-        lib = _hip.load()
-        self.W = lib.dcp_nmf_mu_stats_width(self.F, self.K, lik, 0 if mask is None else 1)
-        self.stats = torch.empty((self.K, self.W), dtype=D.dtype, device=D.device)
+        self.stats = torch.empty((self.K, stats_width), dtype=D.dtype, device=D.device)
         self.maxdiff = torch.zeros((2,), dtype=D.dtype, device=D.device)
         self._host = torch.zeros((2,), dtype=D.dtype).pin_memory()
         self._events = [None, None]
+
+    def local_stats(self, D):
+        from .nmf import _set_penalty
+        lib, h = _arrays.lib_handle(D)
+        _set_penalty(h, self.penalty)
+        self._stats_call(lib, h, D)                 # self.x -> self._x_other
+        self.x, self._x_other = self._x_other, self.x
+        return self.stats
+
+    def rollback(self):
+        """Forget the last local_stats (and what update did to its x): x is again the iterate it started from."""
+        self.x, self._x_other = self._x_other, self.x
+
+    def update(self, stats, D, D_new, slot):
+        """Enqueue the D update; its max|dD| lands asynchronously in host slot ``slot``."""
+        lib, h = _arrays.lib_handle(D)
+        md = self.maxdiff[slot:slot + 1]
+        self._update_call(lib, h, stats, D, D_new, md, self.maxdiff[(slot ^ 1):(slot ^ 1) + 1])
+        self._host[slot:slot + 1].copy_(md, non_blocking=True)
+        ev = self.torch.cuda.Event()
+        ev.record()
+        self._events[slot] = ev
+
+    def read_maxdiff(self, slot):
+        self._events[slot].synchronize()
+        return float(self._host[slot])
+
+
+class HipStepBackend(_StepBackend):
+    """The two halves of one MU iteration on this rank's GPU, through the C ABI (``dcp_nmf_mu_stats[_prepared]_*``
+    / ``dcp_nmf_mu_update_*``).  ``beta`` goes with lik == DCP_LIK_BETA."""
+
+    def __init__(self, y, mask, x, D, lik, beta=None, penalty=(0.0, 0.0)):
+        import torch
+        lib = _hip.load()
+        self.W = lib.dcp_nmf_mu_stats_width(y.shape[1], D.shape[0], lik, 0 if mask is None else 1)
+        _StepBackend.__init__(self, y, x, D, self.W, penalty)
+        self.mask, self.lik, self.beta = mask, lik, beta
         self._ym = self._bits = None
         if mask is not None:
             # loop-invariant mask work, once per run: y o mask and (float32, 0/1 mask) its row bits
@@ -221,12 +232,9 @@ class HipStepBackend(object):
                              _arrays.ptr(bits), ctypes.byref(binary)), 'dcp_nmf_mask_prepare')
             self._bits = bits if binary.value else None
 
-    def local_stats(self, D):
+    def _stats_call(self, lib, h, D):
         from .nmf_methods.grads import set_beta
-        from .nmf import _set_penalty
-        lib, h = _arrays.lib_handle(D)
         set_beta(h, self.lik, self.beta)
-        _set_penalty(h, self.penalty)
         if self.mask is not None:
             fn = getattr(lib, 'dcp_nmf_mu_stats_prepared_' + self.sfx)
             _hip.check(h, fn(h, _arrays.ptr(self._ym), _arrays.ptr(self.mask), _arrays.ptr(self._bits),
@@ -237,83 +245,31 @@ class HipStepBackend(object):
             _hip.check(h, fn(h, _arrays.ptr(self.y), None, _arrays.ptr(self.x),
                              _arrays.ptr(self._x_other), _arrays.ptr(D), self.N, self.F, self.K,
                              self.lik, _arrays.ptr(self.stats)), 'dcp_nmf_mu_stats')
-        self.x, self._x_other = self._x_other, self.x
-        return self.stats
 
-    def rollback(self):
-        """Forget the last local_stats: x is again the iterate it started from."""
-        self.x, self._x_other = self._x_other, self.x
-
-    def update(self, stats, D, D_new, slot):
-        """Enqueue the D update; its max|dD| lands asynchronously in host slot ``slot``."""
-        lib, h = _arrays.lib_handle(D)
+    def _update_call(self, lib, h, stats, D, D_new, md, nxt):
         fn = getattr(lib, 'dcp_nmf_mu_update_' + self.sfx)
-        md = self.maxdiff[slot:slot + 1]            # zero on entry (ping-pong, see the C ABI)
-        nxt = self.maxdiff[(slot ^ 1):(slot ^ 1) + 1]
         _hip.check(h, fn(h, _arrays.ptr(stats), _arrays.ptr(D), _arrays.ptr(D_new), self.F,
                          self.K, self.lik, 0 if self.mask is None else 1, _arrays.ptr(md),
                          _arrays.ptr(nxt)), 'dcp_nmf_mu_update')
-        self._host[slot:slot + 1].copy_(md, non_blocking=True)
-        ev = self.torch.cuda.Event()
-        ev.record()
-        self._events[slot] = ev
-
-    def read_maxdiff(self, slot):
-        self._events[slot].synchronize()
-        return float(self._host[slot])
 
 
-class HipHalsStepBackend(object):
+class HipHalsStepBackend(_StepBackend):
     """The two halves of one HALS iteration on this rank's GPU (``dcp_nmf_hals_stats_*`` /
-    ``dcp_nmf_hals_update_*``), with the protocol of ``HipStepBackend``: x is double buffered,
-    ``local_stats`` writes the next x into the other buffer, ``update`` rescales that new x in place, and
-    ``rollback`` returns to the untouched previous one.  ``penalty`` as in ``HipStepBackend``."""
+    ``dcp_nmf_hals_update_*``): the update also rescales the new x in place; ``rollback`` returns to the
+    untouched previous one."""
 
     def __init__(self, y, x, D, penalty=(0.0, 0.0)):
-        import torch
-        self.torch = torch
-        self.y = y
-        self.penalty = penalty
-        self.x = x
-        self._x_other = torch.empty_like(x)
-        self.N, self.F = y.shape
-        self.K = D.shape[0]
-        self.sfx = _arrays.suffix(D)
-        self.stats = torch.empty((self.K, self.F + self.K), dtype=D.dtype, device=D.device)
-        self.maxdiff = torch.zeros((2,), dtype=D.dtype, device=D.device)
-        self._host = torch.zeros((2,), dtype=D.dtype).pin_memory()
-        self._events = [None, None]
+        _StepBackend.__init__(self, y, x, D, y.shape[1] + D.shape[0], penalty)
 
-    def local_stats(self, D):
-        from .nmf import _set_penalty
-        lib, h = _arrays.lib_handle(D)
-        _set_penalty(h, self.penalty)
+    def _stats_call(self, lib, h, D):
         fn = getattr(lib, 'dcp_nmf_hals_stats_' + self.sfx)
         _hip.check(h, fn(h, _arrays.ptr(self.y), _arrays.ptr(self.x), _arrays.ptr(self._x_other), _arrays.ptr(D),
                          self.N, self.F, self.K, _arrays.ptr(self.stats)), 'dcp_nmf_hals_stats')
-        self.x, self._x_other = self._x_other, self.x
-        return self.stats
 
-    def rollback(self):
-        """Forget the last local_stats (and the rescale of its x by update)."""
-        self.x, self._x_other = self._x_other, self.x
-
-    def update(self, stats, D, D_new, slot):
-        """Enqueue the D sweep, normalisation and x rescale; max|dD| lands asynchronously in host slot ``slot``."""
-        lib, h = _arrays.lib_handle(D)
+    def _update_call(self, lib, h, stats, D, D_new, md, nxt):
         fn = getattr(lib, 'dcp_nmf_hals_update_' + self.sfx)
-        md = self.maxdiff[slot:slot + 1]            # zero on entry (ping-pong, see the C ABI)
-        nxt = self.maxdiff[(slot ^ 1):(slot ^ 1) + 1]
         _hip.check(h, fn(h, _arrays.ptr(stats), _arrays.ptr(D), _arrays.ptr(D_new), _arrays.ptr(self.x), self.N,
                          self.F, self.K, _arrays.ptr(md), _arrays.ptr(nxt)), 'dcp_nmf_hals_update')
-        self._host[slot:slot + 1].copy_(md, non_blocking=True)
-        ev = self.torch.cuda.Event()
-        ev.record()
-        self._events[slot] = ev
-
-    def read_maxdiff(self, slot):
-        self._events[slot].synchronize()
-        return float(self._host[slot])
 
 
 def mu_loop(backend, D, tol, maxiter, group=None, world_size=1, new_like=None):
