@@ -23,14 +23,20 @@
 // core otherwise.
 //
 // Staging: fp32 panels go global -> registers, are split into the three planes in registers
-// (v_cvt_pk_bf16_f32 and an fp32 residual) and written to the other LDS buffer; one barrier per K block.
-// Global -> LDS DMA cannot transform data.  The loads run two blocks ahead and the split runs inside the
-// MFMA stream: during block kb a wave issues the first 2 TN products of each 32-row A block, then splits and
-// stores one panel of block kb + 1 (A panel in the first A block, B panel in the second) and issues that
-// panel's loads for block kb + 2, then the other 4 TN products.  Only MFMAs remain between the last staging
-// and the barrier, so the waves of a SIMD no longer meet the barrier with the matrix pipe idle while all of
-// them split (the 62 % pipe-busy body of round 6).  The register ring stays one block deep: the split frees
-// ra / rb before the loads refill them.
+// (v_cvt_pk_bf16_f32 and an fp32 residual) and written to another LDS buffer; one barrier per K block.
+// Global -> LDS DMA cannot transform data.  The split runs inside the MFMA stream: during block kb a wave
+// issues the first 2 TN products of each 32-row A block, then splits and stores one panel of a later block
+// (A panel in the first A block, B panel in the second) and issues that panel's next loads, then the other
+// 4 TN products, so the waves of a SIMD do not all split with the matrix pipe idle (the 62 % pipe-busy body
+// of round 6).  The register ring stays one block deep: the split frees ra / rb before the loads refill them.
+//   128 x 128 tile: two LDS buffers (three would cost one of its three workgroups per CU).  Block kb + 1 is
+//     staged during block kb, the loads run two blocks ahead, and the barrier sits between the blocks: every
+//     wave leaves it needing its first fragments at once.
+//   256 x 256 tile: a ring of three buffers (3 x 48 KiB; one workgroup per CU either way).  Block kb + 2 is
+//     staged during block kb, the loads run three blocks ahead, and the barrier sits inside the block, after a
+//     wave's last fragment read and before its last 6 TN products.  Nothing but MFMAs lies between a block's
+//     last staging and the next block's first fragment reads, so the waves cross the block boundary staggered
+//     by the matrix pipe instead of aligned by a barrier (the conditions are at the K loop).
 //   KMAJOR panel (reduction index contiguous): one 16-byte load = 4 k of one row.
 //     LDS image of one plane: [rows][16 k] bf16, 32 bytes per row, two 16-byte chunks (k 0..7, 8..15);
 //     chunk q of row r sits at chunk q ^ ((r >> 3) & 1).  A lane (l31, h) of the 32x32x16 MFMA reads
@@ -52,14 +58,15 @@ typedef __bf16 x6_bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 x6_bf16x8 __attribute__((ext_vector_type(8)));
 
 // 64-row wave tiles of 32x32 accumulator blocks, 16-deep K blocks
-template <int BM_, int BN_, int WM_, int WN_, int MINW_>
+template <int BM_, int BN_, int WM_, int WN_, int MINW_, int STAGES_>
 struct X6Cfg {
     static constexpr int BM = BM_, BN = BN_, BK = 16, WM = WM_, WN = WN_, MINW = MINW_;
     static constexpr int NWAVES = (BM_ / WM_) * (BN_ / WN_);
     static constexpr int NTHREADS = 64 * NWAVES;
+    static constexpr int STAGES = STAGES_;   // LDS buffers of planes: 2 (barrier between K blocks) or a ring of 3
 };
-typedef X6Cfg<256, 256, 64, 64, 1> X6Huge;    // 16 waves, 2 x 48 KiB of planes
-typedef X6Cfg<128, 128, 64, 64, 2> X6Large;   // 4 waves, 2 x 24 KiB of planes
+typedef X6Cfg<256, 256, 64, 64, 1, 3> X6Huge;    // 16 waves, 3 x 48 KiB of planes, one workgroup per CU
+typedef X6Cfg<128, 128, 64, 64, 2, 2> X6Large;   // 4 waves, 2 x 24 KiB of planes (a third would cost a workgroup per CU)
 
 template <int ROWS>
 struct X6Panel {
@@ -200,15 +207,36 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    // Pipeline (one barrier per K block): on entry to block kb, buffer kb & 1 holds block kb's planes and
-    // ra / rb hold block kb + 1's fp32 values.  Block kb's MFMAs run in two groups of 6 TN, one per 32-row A
-    // block; the split and the ds_writes of block kb + 1's A panel follow the first 2 TN MFMAs of the first
-    // group, those of its B panel the first 2 TN of the second, each followed by that panel's loads for block
-    // kb + 2.  The
-    // other buffer was last read in block kb - 1, before the barrier that ended it, so it may be written
-    // now.  The loads of the last block re-read block nkb - 1 (in bounds; never used), which keeps the
-    // interior branch free.
+    // Pipeline, STAGES == 2 (one barrier per K block, at the block boundary): on entry to block kb, buffer
+    // kb & 1 holds block kb's planes and ra / rb hold block kb + 1's fp32 values.  Block kb's MFMAs run in two
+    // groups of 6 TN, one per 32-row A block; the split and the ds_writes of block kb + 1's A panel follow the
+    // first 2 TN MFMAs of the first group, those of its B panel the first 2 TN of the second, each followed by
+    // that panel's loads for block kb + 2.  The other buffer was last read in block kb - 1, before the barrier
+    // that ended it, so it may be written now.  The loads of the last block re-read block nkb - 1 (in bounds;
+    // never used), which keeps the interior branch free.
+    //
+    // Pipeline, STAGES == 3 (one barrier per K block, inside the block): on entry to block kb, buffer kb % 3
+    // holds block kb, buffer (kb + 1) % 3 holds block kb + 1 (complete) and ra / rb hold block kb + 2's fp32
+    // values.  During block kb a wave stages block kb + 2 into buffer (kb + 2) % 3 at the same two places and
+    // issues the loads of block kb + 3 behind each store.  The barrier B(kb) sits after the wave's last
+    // fragment read of block kb (the A fragments of the second group) and before that group's MFMAs and B-panel
+    // staging; only MFMAs lie between B(kb) + staging and the first fragment reads of block kb + 1, so the waves
+    // of a SIMD cross the block boundary staggered by the matrix pipe and one wave's fragment reads run under
+    // the others' MFMAs.  Why one barrier is enough:
+    //   - a buffer is overwritten only after a barrier that follows every wave's reads of it: buffer
+    //     (kb + 2) % 3 = (kb - 1) % 3 was last read in block kb - 1, all of those reads precede B(kb - 1), and
+    //     both stagings of block kb follow B(kb - 1);
+    //   - a buffer is read only after a barrier that follows every wave's writes of it: block kb + 2 is read
+    //     after B(kb + 1), and both stagings of block kb precede B(kb + 1).
+    // (With two buffers the second condition fails for the B panel: hence the boundary barrier above.)
+    // The prologue stores blocks 0 and 1 and loads block 2 (clamped to nkb - 1: a short product re-reads its
+    // last block into a buffer nobody reads).  The last two blocks are peeled: block nkb - 2 stages nothing but
+    // keeps its barrier (block nkb - 1's B panel was written after B(nkb - 3)); block nkb - 1 has neither.  The
+    // tail therefore writes no LDS at all, and the last staged block nkb - 3 writes buffer (nkb - 1) % 3, which
+    // nobody has read since B(nkb - 4).
     static_assert(TM == 2, "one panel's staging per 32-row A block");
+    constexpr int STAGES = Cfg::STAGES;
+    static_assert(STAGES == 2 || STAGES == 3, "two buffers and a boundary barrier, or a ring of three");
     f32x4 ra[GA], rb[GB];
     const int nkb = (kend - kbeg) / BK;   // whole K blocks (x6_eligible)
     if (nkb > 0) {
@@ -219,6 +247,13 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
         const int k1 = kbeg + min(1, nkb - 1) * BK;
         x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k1, tid);
         x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k1, tid);
+        if constexpr (STAGES == 3) {
+            x6_lds_store<ALAY, BM, NT>(x6_smem + BUF, ra, tid);
+            x6_lds_store<BLAY, BN, NT>(x6_smem + BUF + X6Panel<BM>::BYTES, rb, tid);
+            const int k2 = kbeg + min(2, nkb - 1) * BK;
+            x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k2, tid);
+            x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k2, tid);
+        }
     }
     __syncthreads();
 
@@ -231,13 +266,15 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
 
     // products (of six) that go out before a group's staging
     constexpr int STAGE_AFTER = 2;
-    auto kblock = [&](int kb, auto stage_tag) {
+    // One K block: fragments from the buffer at byte offset cur; with STAGE, ra / rb are split and stored into
+    // the buffer at nxt and refilled from K offset knext; with BAR, the block's barrier follows its last
+    // fragment read (the ring of three; the two-buffer loop puts its barrier after the block).
+    auto kblock = [&](int cur, int nxt_off, int knext, auto stage_tag, auto bar_tag) {
         constexpr bool STAGE = decltype(stage_tag)::value;
-        const int cur = kb & 1;
-        const char* sA = x6_smem + cur * BUF;
+        constexpr bool BAR = decltype(bar_tag)::value;
+        const char* sA = x6_smem + cur;
         const char* sB = sA + X6Panel<BM>::BYTES;
-        char* nxt = x6_smem + (cur ^ 1) * BUF;
-        const int k2 = kbeg + min(kb + 2, nkb - 1) * BK;
+        char* nxt = x6_smem + nxt_off;
         // B fragments of the block first, then the A fragments of one 32-row block at a time: at four waves
         // per SIMD (128 VGPRs) all of them at once would spill
         x6_bf16x8 fb[3][TN];
@@ -253,6 +290,13 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
             x6_bf16x8 fa[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) fa[pl] = x6_frag<ALAY, BM>(sA + pl * PA, aoff[i]);
+            if constexpr (BAR && i == 1) {
+                // B(kb): every fragment of the block is on its way to registers; hipcc moves MFMAs across a
+                // barrier that nothing pins
+                __builtin_amdgcn_sched_barrier(0);
+                __syncthreads();
+                __builtin_amdgcn_sched_barrier(0);
+            }
             auto mfmas = [&](int t0, int t1) {
 #pragma unroll
                 for (int tt = t0; tt < t1; ++tt)
@@ -262,17 +306,17 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
                             __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[TA[tt]], fb[TB[tt]][j], acc[i][j], 0, 0, 0);
             };
             if constexpr (STAGE) {
-                // the first products go out, then this wave splits and stores one panel of block kb + 1 and
-                // issues its loads for block kb + 2 while they (and the other waves' MFMAs) run; the sched
+                // the first products go out, then this wave splits and stores one panel of the block to stage
+                // and issues that panel's next loads while they (and the other waves' MFMAs) run; the sched
                 // barriers keep hipcc from sinking the staging to the end of the group
                 mfmas(0, STAGE_AFTER);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (i == 0) {
                     x6_lds_store<ALAY, BM, NT>(nxt, ra, tid);
-                    x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k2, tid);
+                    x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, knext, tid);
                 } else {
                     x6_lds_store<BLAY, BN, NT>(nxt + X6Panel<BM>::BYTES, rb, tid);
-                    x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k2, tid);
+                    x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, knext, tid);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 mfmas(STAGE_AFTER, 6);
@@ -284,11 +328,25 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
         group(std::integral_constant<int, 0>{});
         group(std::integral_constant<int, 1>{});
     };
-    for (int kb = 0; kb + 1 < nkb; ++kb) {
-        kblock(kb, std::true_type{});
-        __syncthreads();
+    if constexpr (STAGES == 2) {
+        for (int kb = 0; kb + 1 < nkb; ++kb) {
+            const int cur = (kb & 1) * BUF;
+            kblock(cur, cur ^ BUF, kbeg + min(kb + 2, nkb - 1) * BK, std::true_type{}, std::false_type{});
+            __syncthreads();
+        }
+        if (nkb > 0) kblock(((nkb - 1) & 1) * BUF, 0, 0, std::false_type{}, std::false_type{});
+    } else {
+        int b0 = 0, b1 = BUF, b2 = 2 * BUF;   // byte offsets of the buffers of blocks kb, kb + 1, kb + 2
+        for (int kb = 0; kb + 2 < nkb; ++kb) {
+            kblock(b0, b2, kbeg + min(kb + 3, nkb - 1) * BK, std::true_type{}, std::true_type{});
+            const int t0 = b0;
+            b0 = b1;
+            b1 = b2;
+            b2 = t0;
+        }
+        if (nkb > 1) kblock(b0, 0, 0, std::false_type{}, std::true_type{});
+        if (nkb > 0) kblock(nkb > 1 ? b1 : b0, 0, 0, std::false_type{}, std::false_type{});
     }
-    if (nkb > 0) kblock(nkb - 1, std::false_type{});
 
     // ---- epilogue: the 32x32x16 bf16 MFMA has the C layout of the fp32 one:
     //      col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----
@@ -359,7 +417,7 @@ inline hipError_t launch_gemm_bf16x6(hipStream_t stream, GemmProblem p, const Ep
     p.al_mask = 0;
     const int grid = p.tiles_m * p.tiles_n * p.ksplits;
     if (grid <= 0) return hipSuccess;
-    constexpr int lds_bytes = 2 * (X6Panel<Cfg::BM>::BYTES + X6Panel<Cfg::BN>::BYTES);
+    constexpr int lds_bytes = Cfg::STAGES * (X6Panel<Cfg::BM>::BYTES + X6Panel<Cfg::BN>::BYTES);
     const void* fn = reinterpret_cast<const void*>(&gemm_bf16x6_kernel<Cfg, ALAY, BLAY, Epi>);
     if constexpr (lds_bytes > 65536) {
         static DynLdsRaised raised;   // per instantiation
