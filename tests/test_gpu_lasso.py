@@ -166,7 +166,9 @@ def test_masked_against_oracle_medium_fp32(method, mask_kind):
 @pytest.mark.parametrize('dt', ['float32', 'float64', 'complex64', 'complex128'])
 def test_random_shapes_against_oracle(dt):
     """Seeded random (samples, channels, atoms) off every tile grid, all gradient methods and masks of
-    every rank, 20 iterations without early stop: the same iterate as the oracle (lasso.py restated)."""
+    every rank, 20 iterations without early stop: the same iterate as the oracle (lasso.py restated).  'cd' is left
+    out here (the as-written sweep costs N K^2 F): test_gpu_lasso_cd.py sweeps it at every width, dtype and mask
+    against a Gram-form restatement; 'parallel_cd' and 'admm' are pinned in test_gpu_lasso_extra.py."""
     from decomp_amd import lasso
     from oracle import lasso as olasso
     cplx = dt.startswith('complex')
