@@ -152,6 +152,16 @@ SIGNATURES = {
                                           _P(_c_int), _P(_c_f32)]),
     'dcp_nmf_hals_sharded_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int,
                                           _P(_c_int), _P(_c_f64)]),
+    'dcp_nmf_impute_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
+    'dcp_nmf_impute_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
+    'dcp_nmf_emhals_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f32, _c_int,
+                                    _P(_c_int), _P(_c_f32), _P(_c_f32)]),
+    'dcp_nmf_emhals_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int,
+                                    _P(_c_int), _P(_c_f64), _P(_c_f64)]),
+    'dcp_nmf_emhals_sharded_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f32,
+                                            _c_int, _P(_c_int), _P(_c_f32)]),
+    'dcp_nmf_emhals_sharded_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64,
+                                            _c_int, _P(_c_int), _P(_c_f64)]),
     'dcp_nmf_hals_stats_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
     'dcp_nmf_hals_stats_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
     'dcp_nmf_hals_update_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),

@@ -913,6 +913,43 @@ struct EpiMulMaskBits {
     __device__ __forceinline__ void operator()(int, int, float, int) const {}
 };
 
+// out = w y + (1 - w) acc,  w = mask in [0, 1]: the data with its missing part filled in from the current model
+// (the E step of em-hals, nmf_hals.hip).  Formed as one multiply (1 - w) acc and one fma with w y, so that for
+// finite operands w == 1 returns y and w == 0 returns acc bit for bit.  No select: every element loads y and w
+// and runs the same two operations.
+__device__ __forceinline__ float fma_np(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_np(double a, double b, double c) { return __builtin_fma(a, b, c); }
+template <class T>
+struct EpiImpute {
+    const T* y;      // y, mask and out are [rows, ld] with one leading dimension: one offset per element
+    const T* mask;
+    T* out;
+    long ld;
+    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
+        const long o = (long)r * ld + c;
+        const T w = mask[o];
+        const T yy = y[o];
+        const T t = (T(1) - w) * v;
+        out[o] = fma_np(w, yy, t);
+    }
+    static constexpr bool kVec4 = std::is_same<T, float>::value;   // two loads per element: 16-byte form
+    bool vec_ok() const { return al16_ptr(y) && al16_ptr(mask) && al16_ptr(out) && (ld % 4) == 0; }
+    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
+        if constexpr (std::is_same<T, float>::value) {
+            const long o = (long)r * ld + c0;
+            const f32x4 w = *reinterpret_cast<const f32x4*>(mask + o);
+            const f32x4 yy = *reinterpret_cast<const f32x4*>(y + o);
+            f32x4 q;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float t = (1.0f - w[e]) * v[e];
+                q[e] = fma_np(w[e], yy[e], t);
+            }
+            *reinterpret_cast<f32x4*>(out + o) = q;
+        }
+    }
+};
+
 // KL ratio: out = (y [* mask]) / (acc + 1e-15)   (grads.py:145-149,154-158)
 template <class T>
 struct EpiKlRatio {

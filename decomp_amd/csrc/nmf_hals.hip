@@ -1,6 +1,7 @@
 // C ABI: NMF by HALS (exact block coordinate descent, squared loss, no mask), its row-sharded loop and split
-// step, and the non-negative coordinate sweep on its own.  Contract in include/decomp_hip.h; the kernels in
-// nmf_hals.hpp.
+// step, the non-negative coordinate sweep on its own, and em-hals (HALS on the data with its missing entries
+// imputed from the current model: dcp_nmf_impute_*, dcp_nmf_emhals_*).  Contract in include/decomp_hip.h; the
+// sweep kernels in nmf_hals.hpp, the imputing epilogue (EpiImpute) in gemm.hpp.
 #include <cmath>
 
 #include "comm.hpp"
@@ -73,6 +74,19 @@ int hals_x_side(dcp_handle* h, const T* Y, const T* Xc, T* Xn, const T* Dc, cons
     return nmf_stats<T>(h, Y, nullptr, Xn, Xn, Dc, s, stats, w, 2);
 }
 
+// Yi = mask o Y + (1 - mask) o (Xc Dc): the E step of em-hals.  One fp32 / fp64-core product with the imputing
+// epilogue (EpiImpute); an exact HALS iteration on Yi cannot increase 1/2 sum mask o (Y - x D)^2, which
+// 1/2 |Yi - x D|^2 majorises and touches at (Xc, Dc).
+template <class T>
+int hals_impute(dcp_handle* h, const T* Y, const T* mask, const T* Xc, const T* Dc, int64_t N, int64_t F, int64_t K,
+                T* Yi) {
+    ProfScope ps(h, DCP_PROF_FWD);
+    GemmArgs<T> a;
+    a.A = Xc; a.lda = (int)K; a.B = Dc; a.ldb = (int)F; a.M = (int)N; a.N = (int)F; a.K = (int)K;
+    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiImpute<T>{Y, mask, Yi, (long)F})));
+    return DCP_OK;
+}
+
 template <class T>
 int hals_d_sweep(dcp_handle* h, const T* Dc, T* U, int64_t F, int64_t K, const T* stats) {
     ProfScope ps(h, DCP_PROF_DUPDATE);
@@ -96,12 +110,16 @@ int hals_normalize_rescale(dcp_handle* h, const T* U, const T* Dc, T* Dn, T* X, 
 }
 
 // One HALS iteration for nmf_lagged_loop:  hals_x_side  [all-reduce of `stats`]  hals_d_sweep  normalise + rescale
+// With a mask (em-hals) the iteration starts with hals_impute and both half-steps read the imputed data Yi
+// instead of Y; without one exactly the kernels above run.
 template <class T>
 struct HalsStep {
     const T* Y;
     NmfShape<T> s;
     NmfPenalty pen;
     bool sharded;
+    const T* mask = nullptr;
+    T* Yi = nullptr;    // [N, F] imputed data (mask only)
     NmfStatsWs<T> ws;
     T* stats = nullptr;
     T* U = nullptr;     // the swept, not yet normalised D
@@ -112,6 +130,7 @@ struct HalsStep {
         plan.add<T>((size_t)s.K * (s.F + s.K));
         plan.add<T>((size_t)s.K * s.F);
         plan.add<T>((size_t)s.K);
+        if (mask) plan.add<T>((size_t)s.N * s.F);
     }
     int carve(dcp_handle* h) {
         DCP_TRY(nmf_carve_stats(h, ws, s, false));
@@ -119,11 +138,20 @@ struct HalsStep {
         U = ws_alloc<T>(h, (size_t)s.K * s.F);
         nrm = ws_alloc<T>(h, (size_t)s.K);
         if (!stats || !U || !nrm) return fail(h, DCP_ERR_INTERNAL, "hals workspace plan mismatch");
+        if (mask) {
+            Yi = ws_alloc<T>(h, (size_t)s.N * s.F);
+            if (!Yi) return fail(h, DCP_ERR_INTERNAL, "em-hals workspace plan mismatch");
+        }
         return DCP_OK;
     }
     int prepare(dcp_handle*) { return DCP_OK; }
     int iterate(dcp_handle* h, const T* Xc, T* Xn, const T* Dc, T* Dn, const NmfStopSlots<T>& slots) {
-        DCP_TRY(hals_x_side<T>(h, Y, Xc, Xn, Dc, s, stats, ws, pen));
+        const T* Yd = Y;
+        if (mask) {   // one imputation per iteration, from the iterate both half-steps start from
+            DCP_TRY(hals_impute<T>(h, Y, mask, Xc, Dc, s.N, s.F, s.K, Yi));
+            Yd = Yi;
+        }
+        DCP_TRY(hals_x_side<T>(h, Yd, Xc, Xn, Dc, s, stats, ws, pen));
         if (sharded) {   // the one exchange of the step: the D sweep reads sums over all ranks' rows
             ProfScope ps(h, DCP_PROF_EXCHANGE);
             DCP_TRY(comm_allreduce_sum(h, stats, (size_t)s.K * (s.F + s.K),
@@ -137,15 +165,26 @@ struct HalsStep {
 
 template <class T>
 int nmf_hals_solve(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, int64_t K, T tol, int maxiter,
-                   int* it_out, T* last_maxdiff, T* resid_trace, bool sharded = false) {
+                   int* it_out, T* last_maxdiff, T* resid_trace, bool sharded = false, const T* mask = nullptr) {
     DCP_TRY(check_nmf_dims(h, Y, X, D, N, F, K));
     if (!it_out) return fail(h, DCP_ERR_INVALID, "it_out is null");
     if (sharded && !comm_active(h))
-        return fail(h, DCP_ERR_COMM, "dcp_nmf_hals_sharded_* needs a communicator (dcp_comm_init)");
+        return fail(h, DCP_ERR_COMM, mask ? "dcp_nmf_emhals_sharded_* needs a communicator (dcp_comm_init)"
+                                          : "dcp_nmf_hals_sharded_* needs a communicator (dcp_comm_init)");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    HalsStep<T> step{Y, NmfShape<T>{N, F, K, DCP_LIK_L2, false}, nmf_penalty(h), sharded};
-    return nmf_lagged_loop<T>(h, step, Y, (const T*)nullptr, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff,
-                              resid_trace);
+    // the shape stays "not masked": the statistics are those of plain HALS on the imputed data
+    HalsStep<T> step{Y, NmfShape<T>{N, F, K, DCP_LIK_L2, false}, nmf_penalty(h), sharded, mask};
+    return nmf_lagged_loop<T>(h, step, Y, mask, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, resid_trace);
+}
+
+// dcp_nmf_impute_*: the E step on its own, asynchronous (no workspace).
+template <class T>
+int nmf_impute_api(dcp_handle* h, const T* Y, const T* mask, const T* X, const T* D, int64_t N, int64_t F, int64_t K,
+                   T* Y_out) {
+    DCP_TRY(check_nmf_dims(h, Y, X, D, N, F, K));
+    if (!mask || !Y_out) return fail(h, DCP_ERR_INVALID, "mask / Y_out is null");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    return hals_impute<T>(h, Y, mask, X, D, N, F, K, Y_out);
 }
 
 // dcp_nmf_hals_stats_*: the x side of one iteration, up to the exchange point.  Same kernels in the same order
@@ -222,6 +261,31 @@ int dcp_nmf_hals_sharded_f32(dcp_handle* h, const float* Y, float* X, float* D, 
 int dcp_nmf_hals_sharded_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
                              double tol, int maxiter, int* it_out, double* last_maxdiff) {
     return nmf_hals_solve<double>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, nullptr, true);
+}
+int dcp_nmf_impute_f32(dcp_handle* h, const float* Y, const float* mask, const float* X, const float* D, int64_t N,
+                       int64_t F, int64_t K, float* Y_out) {
+    return nmf_impute_api<float>(h, Y, mask, X, D, N, F, K, Y_out);
+}
+int dcp_nmf_impute_f64(dcp_handle* h, const double* Y, const double* mask, const double* X, const double* D,
+                       int64_t N, int64_t F, int64_t K, double* Y_out) {
+    return nmf_impute_api<double>(h, Y, mask, X, D, N, F, K, Y_out);
+}
+int dcp_nmf_emhals_f32(dcp_handle* h, const float* Y, const float* mask, float* X, float* D, int64_t N, int64_t F,
+                       int64_t K, float tol, int maxiter, int* it_out, float* last_maxdiff, float* resid_trace) {
+    return nmf_hals_solve<float>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, resid_trace, false, mask);
+}
+int dcp_nmf_emhals_f64(dcp_handle* h, const double* Y, const double* mask, double* X, double* D, int64_t N,
+                       int64_t F, int64_t K, double tol, int maxiter, int* it_out, double* last_maxdiff,
+                       double* resid_trace) {
+    return nmf_hals_solve<double>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, resid_trace, false, mask);
+}
+int dcp_nmf_emhals_sharded_f32(dcp_handle* h, const float* Y, const float* mask, float* X, float* D, int64_t N,
+                               int64_t F, int64_t K, float tol, int maxiter, int* it_out, float* last_maxdiff) {
+    return nmf_hals_solve<float>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, nullptr, true, mask);
+}
+int dcp_nmf_emhals_sharded_f64(dcp_handle* h, const double* Y, const double* mask, double* X, double* D, int64_t N,
+                               int64_t F, int64_t K, double tol, int maxiter, int* it_out, double* last_maxdiff) {
+    return nmf_hals_solve<double>(h, Y, X, D, N, F, K, tol, maxiter, it_out, last_maxdiff, nullptr, true, mask);
 }
 int dcp_nmf_hals_stats_f32(dcp_handle* h, const float* Y, const float* X, float* X_out, const float* D, int64_t N,
                            int64_t F, int64_t K, float* stats) {

@@ -5,7 +5,8 @@ reference's decomp/nmf.py:16-113: the full-batch multiplicative update
 (``minibatch=None, method='mu'``) and the stochastic minibatch variants
 (decomp_amd/nmf_minibatch.py).  Beyond the reference: ``method='hals'`` (l2, no mask,
 full batch), exact block coordinate descent in libdecomp_hip.so (``dcp_nmf_hals_*``,
-decomp_amd/csrc/nmf_hals.hpp).  The full-batch MU iteration itself
+decomp_amd/csrc/nmf_hals.hpp) and ``method='em-hals'`` (the same with missing or weighted entries,
+``dcp_nmf_emhals_*``).  The full-batch MU iteration itself
 (decomp/nmf_methods/batch_mu.py:8-26 with the update rules of
 decomp/nmf_methods/grads.py:77-160) runs in libdecomp_hip.so: see
 include/decomp_hip.h ``dcp_nmf_mu_*`` and decomp_amd/csrc/nmf_impl.hpp.  Also beyond the reference: an L1/L2
@@ -126,7 +127,17 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
     Non-negative matrix factorisation  argmin_{x, D} |y - xD|^2,  x >= 0, D >= 0,
     |D_j| = 1, by multiplicative updates (method='mu'), or, for the l2 likelihood without a
     mask, by HALS (method='hals': exact block coordinate descent on the columns of x and the
-    atoms of D, then the atoms rescaled to unit norm with x rescaled so that xD is unchanged).
+    atoms of D, then the atoms rescaled to unit norm with x rescaled so that xD is unchanged),
+    or, for the l2 likelihood with missing or weighted entries, by method='em-hals'.
+
+    method='em-hals' minimises  1/2 sum mask o (y - xD)^2  (+ the penalty below) for weights mask in [0, 1]
+    (anything else, NaN included: ValueError).  Each iteration fills the unobserved part of y in from the
+    current model,  y' = mask o y + (1 - mask) o (xD),  and runs one HALS iteration on y' (EM for weighted
+    low-rank factorisation, Srebro & Jaakkola 2003, with HALS as the M step).  1/2 |y' - xD|^2 majorises the
+    masked objective and touches it at the current iterate, so no iteration can increase the objective; the
+    smaller the observed fraction, the slower the convergence (the imputed part pulls every step towards the
+    previous iterate).  Defaults, return convention and penalties as for 'hals'; mask=None runs plain HALS.
+    Full batch and l2 only (NotImplementedError otherwise).
 
     l1_penalty, l2_penalty (lambda1, lambda2 >= 0, default 0): a penalty on the codes.  The objective
     becomes  loss(y, xD) + lambda1 sum(x) + lambda2/2 |x|^2,  loss = 1/2 |M o (y - xD)|^2 for 'l2' (M the
@@ -151,6 +162,8 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
     max|D - D_new| < tol was met, or ``maxiter`` when it never was.
     """
     penalty = _check_penalty(l1_penalty, l2_penalty)
+    if method == 'em-hals':
+        _check_emhals_scope(likelihood, minibatch, kwargs)
     _check_penalty_scope(penalty, minibatch, method, likelihood)
     kind = get_array_module(D)
     x_given = x
@@ -219,6 +232,14 @@ def solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu',
             if y_dev is None:
                 y_dev = _arrays.to_device(y, dev)
             it = _run_hals(y_dev, x_dev, D_dev, tol, maxiter, penalty=penalty)
+            return it, _arrays.to_caller(D_dev, kind), _arrays.to_caller(x_dev, kind)
+        if method == 'em-hals':
+            get_array_module(y, mask)
+            if y_dev is None:
+                y_dev = _arrays.to_device(y, dev)
+            m_dev = _arrays.to_device(mask, dev)
+            _check_weights(m_dev)
+            it = _run_emhals(y_dev, m_dev, x_dev, D_dev, tol, maxiter, penalty=penalty)
             return it, _arrays.to_caller(D_dev, kind), _arrays.to_caller(x_dev, kind)
         raise NotImplementedError('Batch-NMF with {} algorithm is not yet '
                                   'implemented.'.format(method))
@@ -290,8 +311,9 @@ def _solve_streamed(y, D_dev, x_given, tol, minibatch, maxiter, method, likeliho
 
 
 def _loop_call(method, sharded, y, mask, x, D, lik, beta, penalty, tol, maxiter, resid_trace=None):
-    """One full-batch solver loop inside the library, ``dcp_nmf_{mu,hals}[_sharded]_*``, on device arrays; x and D
-    are updated in place.  Returns it.  The hals entries take neither mask nor likelihood (``lik`` None), the
+    """One full-batch solver loop inside the library, ``dcp_nmf_{mu,hals,emhals}[_sharded]_*``, on device arrays; x
+    and D are updated in place.  Returns it.  The hals entries take neither mask nor likelihood (``lik`` None), the
+    emhals entries a mask (or None) but no likelihood, the
     sharded ones no residual trace.  ``beta`` goes with lik == DCP_LIK_BETA; ``penalty`` is (l1, l2) on the codes,
     set on the handle for this call alone."""
     from .nmf_methods.grads import set_beta
@@ -301,7 +323,8 @@ def _loop_call(method, sharded, y, mask, x, D, lik, beta, penalty, tol, maxiter,
     it = ctypes.c_int(0)
     last = ctype(0)
     mu = method == 'mu'
-    args = [h, _arrays.ptr(y)] + ([_arrays.ptr(mask)] if mu else []) + [_arrays.ptr(x), _arrays.ptr(D)]
+    masked = mu or method == 'emhals'
+    args = [h, _arrays.ptr(y)] + ([_arrays.ptr(mask)] if masked else []) + [_arrays.ptr(x), _arrays.ptr(D)]
     args += list(y.shape) + [D.shape[0]] + ([lik] if mu else [])
     args += [ctype(tol), int(maxiter), ctypes.byref(it), ctypes.byref(last)]
     trace = None
@@ -344,6 +367,31 @@ def _run_hals(y, x, D, tol, maxiter, resid_trace=None, penalty=(0.0, 0.0)):
     in place.  Same stop rule and return convention as ``_run_mu``; ``penalty`` is (l1, l2) on the codes.
     Returns it."""
     return _loop_call('hals', False, y, None, x, D, None, None, penalty, tol, maxiter, resid_trace)
+
+
+def _check_emhals_scope(likelihood, minibatch, kwargs):
+    """What method='em-hals' covers: the squared loss, full batch, no extra keyword.  Runs before any GPU call."""
+    if kwargs:
+        raise TypeError('solve() got an unexpected keyword argument %r' % sorted(kwargs)[0])
+    if minibatch is not None:
+        raise NotImplementedError('NMF with the em-hals algorithm is a full-batch method (minibatch=None)')
+    if not (isinstance(likelihood, str) and likelihood in ('l2', 'gaussian')):
+        raise NotImplementedError('NMF with the em-hals algorithm supports only the l2 likelihood, '
+                                  'not {} (use method=\'mu\')'.format(likelihood))
+
+
+def _check_weights(mask):
+    """The weights of em-hals must lie in [0, 1] (one pass on the device, once per solve; a NaN fails both
+    comparisons).  None passes."""
+    if mask is not None and not bool(((mask >= 0) & (mask <= 1)).all()):
+        raise ValueError('mask must lie in [0, 1] for the em-hals algorithm')
+
+
+def _run_emhals(y, mask, x, D, tol, maxiter, resid_trace=None, penalty=(0.0, 0.0)):
+    """em-hals on device arrays (``dcp_nmf_emhals_*``): every iteration imputes the entries the weights ``mask``
+    in [0, 1] leave out from the current x D, then runs one HALS iteration on the result.  ``mask`` None runs
+    plain HALS.  Conventions of ``_run_hals``; ``resid_trace`` collects |(y - x D) o mask|_F.  Returns it."""
+    return _loop_call('emhals', False, y, mask, x, D, None, None, penalty, tol, maxiter, resid_trace)
 
 
 def _run_mu_user(y, mask, x_dev, D_dev, lik, tol, maxiter, kind):

@@ -21,7 +21,9 @@ serve (several ranks on one GPU).
 HALS (``nmf_solve_sharded(..., method='hals')``) shards the same way: its D sweep reads exactly the
 [x^T Y | x^T x] statistics MU all-reduces, so ``dcp_nmf_hals_sharded_*`` all-reduces them between the x side
 and the D sweep, and ``HipHalsStepBackend`` drives the split step (``dcp_nmf_hals_stats_*`` /
-``dcp_nmf_hals_update_*``) through the same ``mu_loop``.
+``dcp_nmf_hals_update_*``) through the same ``mu_loop``.  ``method='em-hals'`` adds a mask to it: the
+imputation is local to a row, so the exchange is the same (``dcp_nmf_emhals_sharded_*``, or
+``HipEmHalsStepBackend``: ``dcp_nmf_impute_*`` in front of the HALS statistics).
 """
 import ctypes
 import os
@@ -157,6 +159,13 @@ def hals_solve_in_library(y, x, D, tol, maxiter, penalty=(0.0, 0.0)):
     return _loop_call('hals', True, y, None, x, D, None, None, penalty, tol, maxiter)
 
 
+def emhals_solve_in_library(y, mask, x, D, tol, maxiter, penalty=(0.0, 0.0)):
+    """``dcp_nmf_emhals_sharded_*`` on this rank's rows (x and D updated in place; ``mask`` may be None).
+    Returns it.  ``penalty`` as in ``mu_solve_in_library``."""
+    from .nmf import _loop_call
+    return _loop_call('emhals', True, y, mask, x, D, None, None, penalty, tol, maxiter)
+
+
 class _StepBackend(object):
     """What ``mu_loop`` drives, for a method given as two ctypes calls (``_stats_call`` / ``_update_call``).
 
@@ -272,6 +281,27 @@ class HipHalsStepBackend(_StepBackend):
                          self.F, self.K, _arrays.ptr(md), _arrays.ptr(nxt)), 'dcp_nmf_hals_update')
 
 
+class HipEmHalsStepBackend(HipHalsStepBackend):
+    """``HipHalsStepBackend`` for em-hals: the x side first imputes this rank's rows from the current (x, D)
+    (``dcp_nmf_impute_*`` into a buffer of its own), then runs the HALS statistics on the imputed rows.  The
+    same kernels in the same order as ``dcp_nmf_emhals_*``.  ``mask`` None: exactly ``HipHalsStepBackend``."""
+
+    def __init__(self, y, mask, x, D, penalty=(0.0, 0.0)):
+        HipHalsStepBackend.__init__(self, y, x, D, penalty=penalty)
+        self.mask = mask
+        self._yi = None if mask is None else self.torch.empty_like(y)
+
+    def _stats_call(self, lib, h, D):
+        if self.mask is None:
+            return HipHalsStepBackend._stats_call(self, lib, h, D)
+        fn = getattr(lib, 'dcp_nmf_impute_' + self.sfx)
+        _hip.check(h, fn(h, _arrays.ptr(self.y), _arrays.ptr(self.mask), _arrays.ptr(self.x), _arrays.ptr(D),
+                         self.N, self.F, self.K, _arrays.ptr(self._yi)), 'dcp_nmf_impute')
+        fn = getattr(lib, 'dcp_nmf_hals_stats_' + self.sfx)
+        _hip.check(h, fn(h, _arrays.ptr(self._yi), _arrays.ptr(self.x), _arrays.ptr(self._x_other), _arrays.ptr(D),
+                         self.N, self.F, self.K, _arrays.ptr(self.stats)), 'dcp_nmf_hals_stats')
+
+
 def mu_loop(backend, D, tol, maxiter, group=None, world_size=1, new_like=None):
     """batch_mu.py:16-26 with the statistics all-reduced over ``group``.
 
@@ -304,7 +334,8 @@ def mu_loop(backend, D, tol, maxiter, group=None, world_size=1, new_like=None):
 def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likelihood='l2',
                       mask_local=None, group=None, method='mu', l1_penalty=0.0, l2_penalty=0.0):
     """``decomp.nmf.solve(method='mu')`` -- or, with ``method='hals'``, ``nmf.solve(method='hals')``
-    (l2, no mask) -- for a row-sharded problem.
+    (l2, no mask), or, with ``method='em-hals'``, ``nmf.solve(method='em-hals')`` (l2, weights ``mask_local`` in
+    [0, 1] on this rank's rows, or None) -- for a row-sharded problem.
 
     Every rank passes its own rows (torch CUDA tensors) and the same D.  Returns
     (it, D, x_local); D and it are identical on all ranks.  torch.distributed must be
@@ -321,6 +352,8 @@ def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likeli
     _nmf._check_penalty_scope(penalty, None, method, likelihood)
     if method == 'hals':
         _nmf._check_hals_scope(likelihood, mask_local)
+    elif method == 'em-hals':
+        _nmf._check_emhals_scope(likelihood, None, None)
     elif method != 'mu':
         raise NotImplementedError('Sharded NMF with {} algorithm is not yet implemented.'.format(method))
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -341,16 +374,22 @@ def nmf_solve_sharded(y_local, D, x_local=None, tol=1.0e-3, maxiter=1000, likeli
     if likelihood in ['kl']:
         assertion.assert_nonnegative(y)
     _nmf._check_beta_data(likelihood, y, m)
+    if method == 'em-hals':
+        _nmf._check_weights(m)
     _arrays.l2_normalize_(Dd, strict=True)
     if world > 1 and attach_communicator(Dd, group):
         # the shipped multi-GPU path: the whole loop, collective included, behind the C ABI
         if method == 'hals':
             it = hals_solve_in_library(y, x, Dd, tol, maxiter, penalty=penalty)
+        elif method == 'em-hals':
+            it = emhals_solve_in_library(y, m, x, Dd, tol, maxiter, penalty=penalty)
         else:
             it = mu_solve_in_library(y, m, x, Dd, lik, tol, maxiter, beta=beta, penalty=penalty)
         return it, Dd, x
     if method == 'hals':
         backend = HipHalsStepBackend(y, x, Dd, penalty=penalty)
+    elif method == 'em-hals':
+        backend = HipEmHalsStepBackend(y, m, x, Dd, penalty=penalty)
     else:
         backend = HipStepBackend(y, m, x, Dd, lik, beta=beta, penalty=penalty)
     try:

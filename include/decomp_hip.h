@@ -254,6 +254,36 @@ int dcp_nmf_hals_update_f32(dcp_handle* h, const float* stats, const float* D, f
                             int64_t F, int64_t K, float* maxdiff_dev, float* maxdiff_next);
 int dcp_nmf_hals_update_f64(dcp_handle* h, const double* stats, const double* D, double* D_new, double* X,
                             int64_t N, int64_t F, int64_t K, double* maxdiff_dev, double* maxdiff_next);
+/* ---- NMF, em-hals: HALS for data with missing entries (weights mask in [0, 1]) ------------------------ */
+/* Y_out[N, F] = mask o Y + (1 - mask) o (X D): the data with its missing part filled in from the model (the E
+ * step of EM for weighted low-rank factorisation, Srebro & Jaakkola 2003).  One X D product with the imputation
+ * in its epilogue, formed as  fma(w, y, (1 - w) * acc): for finite operands an entry with w == 1 is y and one
+ * with w == 0 is (X D) bit for bit.  mask values outside [0, 1] are not checked here.  Y_out must not overlap an
+ * input.  Nothing outside Y_out[N, F] is written.  Deterministic.  Asynchronous on the handle's stream. */
+int dcp_nmf_impute_f32(dcp_handle* h, const float* Y, const float* mask, const float* X, const float* D, int64_t N,
+                       int64_t F, int64_t K, float* Y_out);
+int dcp_nmf_impute_f64(dcp_handle* h, const double* Y, const double* mask, const double* X, const double* D,
+                       int64_t N, int64_t F, int64_t K, double* Y_out);
+/* em-hals minimises  1/2 sum mask o (Y - X D)^2  (plus the penalty of dcp_set_nmf_penalty).  One iteration from
+ * (X, D):  Yi = impute(Y, mask, X, D)  as dcp_nmf_impute_*, then ONE iteration of dcp_nmf_hals_* on Yi (both
+ * half-steps read the same Yi).  1/2 |Yi - X' D'|^2 majorises the masked objective and equals it at (X, D), and
+ * the HALS iteration does not increase it, so no iteration increases the masked objective; the fewer entries are
+ * observed, the slower the convergence.  mask == NULL: exactly dcp_nmf_hals_* (the same kernels).  The stop rule,
+ * the return convention, last_maxdiff and the product modes are those of dcp_nmf_hals_*; resid_trace reports
+ * ||(Y - X D_new) o mask||_F.  Workspace: N F elements more than dcp_nmf_hals_*.
+ * The sharded entries are dcp_nmf_hals_sharded_* with this iteration (Y, mask, X: this rank's rows; the
+ * imputation is local to a row, so the exchange is unchanged); DCP_ERR_COMM without a communicator.
+ * The split step needs no entry of its own: dcp_nmf_impute_* into a caller's buffer, dcp_nmf_hals_stats_* on
+ * that buffer and dcp_nmf_hals_update_* reproduce the loop bit for bit. */
+int dcp_nmf_emhals_f32(dcp_handle* h, const float* Y, const float* mask, float* X, float* D, int64_t N, int64_t F,
+                       int64_t K, float tol, int maxiter, int* it_out, float* last_maxdiff, float* resid_trace);
+int dcp_nmf_emhals_f64(dcp_handle* h, const double* Y, const double* mask, double* X, double* D, int64_t N,
+                       int64_t F, int64_t K, double tol, int maxiter, int* it_out, double* last_maxdiff,
+                       double* resid_trace);
+int dcp_nmf_emhals_sharded_f32(dcp_handle* h, const float* Y, const float* mask, float* X, float* D, int64_t N,
+                               int64_t F, int64_t K, float tol, int maxiter, int* it_out, float* last_maxdiff);
+int dcp_nmf_emhals_sharded_f64(dcp_handle* h, const double* Y, const double* mask, double* X, double* D, int64_t N,
+                               int64_t F, int64_t K, double tol, int maxiter, int* it_out, double* last_maxdiff);
 /* The non-negative coordinate sweep of HALS on R independent vectors: for k = 0 .. K-1 in order, with the
  * current V (coordinates < k already updated),
  *   if G[k,k] > 0:  V[:,k] = max(0, V[:,k] - (V G[:,k] - C[:,k]) / G[k,k])      (else V[:,k] unchanged)
@@ -374,6 +404,7 @@ int dcp_set_nmf_beta(dcp_handle* h, double beta);
  *   dcp_nmf_mu_*, dcp_nmf_mu_sharded_*, dcp_nmf_mu_stats_*, dcp_nmf_mu_stats_prepared_*   the MU x update
  *       x <- x * max(pos, 0) / max(neg + l1 + l2 x, 1e-15)    (x before the update; pos / neg as without it)
  *   dcp_nmf_hals_*, dcp_nmf_hals_sharded_*, dcp_nmf_hals_stats_*                           the HALS x sweep
+ *   dcp_nmf_emhals_*, dcp_nmf_emhals_sharded_*                                  (the same sweep, on the imputed data)
  *       the exact coordinate minimiser: the sweep on C = Y D^T - l1 and G = D D^T + l2 I, i.e. where
  *       G[k,k] + l2 > 0:  X[:,k] = max(0, X[:,k] - (X G[:,k] + l2 X[:,k] - C[:,k] + l1) / (G[k,k] + l2))
  * Every other entry ignores it (dcp_nmf_grads_*, dcp_nmf_grad_x_*, dcp_nn_cd_sweep_*, the D updates, the
