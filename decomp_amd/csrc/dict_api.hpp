@@ -2,8 +2,22 @@
 #pragma once
 #include "dict_impl.hpp"
 #include "lasso_api.hpp"
+#include "omp.hpp"
 
 namespace dcp {
+
+// workspace of the step's inner coder: the LASSO solvers' plan, or the (smaller) one of DCP_LASSO_OMP -- both fill
+// a LassoWs
+template <class T>
+inline void dict_coder_plan(WsPlan& p, int64_t Nb, int64_t F, int64_t K, int mask_ndim, int base) {
+    if (base == DCP_LASSO_OMP) omp_plan<T>(p, Nb, F, K);
+    else lasso_plan<T>(p, Nb, F, K, mask_ndim, base);
+}
+template <class T>
+inline int dict_coder_carve(dcp_handle* h, LassoWs<T>& w, int64_t Nb, int64_t F, int64_t K, int mask_ndim, int base) {
+    if (base == DCP_LASSO_OMP) return omp_carve<T>(h, w, Nb, F, K);
+    return lasso_carve<T>(h, w, Nb, F, K, mask_ndim, base);
+}
 
 template <class T>
 inline void dict_plan_extra(WsPlan& p, int64_t Nb, int64_t F, int64_t K) {
@@ -53,6 +67,7 @@ inline int dict_check(dcp_handle* h, const void* a, const void* b, const void* c
 // lasso_method arrives as DCP_LASSO_* optionally OR'ed with DCP_LASSO_POSITIVE ('_pos' solvers)
 inline bool dict_lasso_method_ok(int lasso_method) {
     const int base = lasso_method & ~DCP_LASSO_POSITIVE;
+    if (base == DCP_LASSO_OMP) return lasso_method == DCP_LASSO_OMP;   // no non-negative OMP
     return base >= DCP_LASSO_ISTA && base <= DCP_LASSO_ADMM;
 }
 
@@ -63,6 +78,27 @@ inline int dict_lasso(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_nd
     typedef real_t<T> R;
     const int base = lasso_method & ~DCP_LASSO_POSITIVE;
     const bool positive = (lasso_method & DCP_LASSO_POSITIVE) != 0;
+    if (base == DCP_LASSO_OMP) {
+        // lasso_iter = the sparsity, lasso_tol = the residual tolerance; alpha and the warm start are not read.  The
+        // step count reaches *it through a pinned word that lasso_settle_deferred() reads at the end of the step.
+        if (positive) return fail(h, DCP_ERR_INVALID, "omp has no non-negative form");
+        if (M != nullptr || mask_ndim != 0) return fail(h, DCP_ERR_INVALID, "omp does not take a mask");
+        if (lasso_tol != lasso_tol) return fail(h, DCP_ERR_INVALID, "omp: tol is NaN");
+        DCP_TRY(omp_check_sparsity(h, K, lasso_iter, omp_cap<T>()));
+        h->lasso_deferred_flag = nullptr;
+        h->lasso_deferred_it = nullptr;
+        void* hostv = nullptr;
+        DCP_TRY(host_scratch(h, 64, &hostv));
+        int* host_it = reinterpret_cast<int*>(reinterpret_cast<char*>(hostv) + 32);
+        *host_it = -1;
+        DCP_TRY(omp_solve<T>(h, Y, D, X, (int)Nb, (int)F, (int)K, lasso_iter, lasso_tol, lw));
+        hipLaunchKernelGGL(flag_publish_kernel<void>, dim3(1), dim3(64), 0, h->stream, lw.flag, host_it);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        h->lasso_deferred_flag = host_it;
+        h->lasso_deferred_it = it;
+        h->lasso_deferred_copy = true;
+        return DCP_OK;
+    }
     LassoExtra extra;
     extra.no_final_sync = true;            // the statistics product follows on the same stream
     extra.start_prefetch = false;          // the prefetch runs beside the atom sweep (dict_step_core)
@@ -113,13 +149,13 @@ inline int dict_stats_api(dcp_handle* h, const T* Y, T* X, const T* D, int64_t N
         return fail(h, DCP_ERR_INVALID, "bad lasso method");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     WsPlan plan;
-    lasso_plan<T>(plan, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE);
+    dict_coder_plan<T>(plan, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE);
     dict_plan_extra<T>(plan, Nb, F, K);
     DCP_TRY(ws_reserve(h, plan.total));
     ws_reset(h);
     LassoWs<T> lw;
     DictWs<T> dw;
-    DCP_TRY(lasso_carve<T>(h, lw, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE));
+    DCP_TRY(dict_coder_carve<T>(h, lw, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE));
     DCP_TRY(dict_carve_extra<T>(h, dw, Nb, F, K));
     return dict_stats_core<T>(h, Y, X, D, Nb, F, K, alpha, lasso_method, lasso_iter, lasso_tol, stats,
                               lasso_it, lw, dw);
@@ -177,13 +213,13 @@ inline int dict_step_core(dcp_handle* h, const T* Y, T* X, const T* D, T* Dnew, 
         return fail(h, DCP_ERR_INVALID, "bad lasso method");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     WsPlan plan;
-    lasso_plan<T>(plan, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE);
+    dict_coder_plan<T>(plan, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE);
     dict_plan_extra<T>(plan, Nb, F, K);
     DCP_TRY(ws_reserve(h, plan.total));
     ws_reset(h);
     LassoWs<T> lw;
     DictWs<T> dw;
-    DCP_TRY(lasso_carve<T>(h, lw, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE));
+    DCP_TRY(dict_coder_carve<T>(h, lw, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE));
     DCP_TRY(dict_carve_extra<T>(h, dw, Nb, F, K));
     // one GPU: the statistics stay as ordered split-K partials (no [K, F+K] sum is formed: `stats` = null) and
     // are summed by the A / B accumulation itself
@@ -248,7 +284,7 @@ inline int dict_mask_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, T* 
     DCP_HIP_OK(h, hipSetDevice(h->device));
     hipStream_t st = h->stream;
     WsPlan plan;
-    lasso_plan<T>(plan, Nb, F, K, 2, lasso_method & ~DCP_LASSO_POSITIVE);
+    dict_coder_plan<T>(plan, Nb, F, K, 2, lasso_method & ~DCP_LASSO_POSITIVE);
     dict_plan_extra<T>(plan, Nb, F, K);
     plan.add<T>((size_t)Nb * F);   // y o m
     plan.add<T>((size_t)K * F);    // x^H (y o m)
@@ -256,7 +292,7 @@ inline int dict_mask_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, T* 
     ws_reset(h);
     LassoWs<T> lw;
     DictWs<T> dw;
-    DCP_TRY(lasso_carve<T>(h, lw, Nb, F, K, 2, lasso_method & ~DCP_LASSO_POSITIVE));
+    DCP_TRY(dict_coder_carve<T>(h, lw, Nb, F, K, 2, lasso_method & ~DCP_LASSO_POSITIVE));
     DCP_TRY(dict_carve_extra<T>(h, dw, Nb, F, K));
     T* Ym = ws_alloc<T>(h, (size_t)Nb * F);
     T* sB = ws_alloc<T>(h, (size_t)K * F);

@@ -53,6 +53,7 @@ struct dcp_handle {
     int* lasso_deferred_flag = nullptr;
     int* lasso_deferred_it = nullptr;
     int lasso_deferred_it_met = 0;
+    bool lasso_deferred_copy = false;   // the pinned word holds the count itself (orthogonal matching pursuit)
     int lasso_it_sink = 0;
     // parallel_cd inside the dictionary step: the caller-supplied shuffle table (dcp_dict_set_pcd_order)
     const int* pcd_order = nullptr;

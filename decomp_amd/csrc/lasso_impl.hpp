@@ -859,8 +859,14 @@ inline int lasso_settle_deferred(dcp_handle* h) {
     if (h->lasso_deferred_flag == nullptr) return DCP_OK;
     int* f = h->lasso_deferred_flag;
     h->lasso_deferred_flag = nullptr;
+    const bool copy = h->lasso_deferred_copy;   // DCP_LASSO_OMP: the word IS the count (dict_lasso)
+    h->lasso_deferred_copy = false;
     DCP_TRY(poll_host_flag(h, f));
-    if (*f == 0 && h->lasso_deferred_it != nullptr) *h->lasso_deferred_it = h->lasso_deferred_it_met;
+    if (copy) {
+        if (h->lasso_deferred_it != nullptr) *h->lasso_deferred_it = *f;
+    } else if (*f == 0 && h->lasso_deferred_it != nullptr) {
+        *h->lasso_deferred_it = h->lasso_deferred_it_met;
+    }
     h->lasso_deferred_it = nullptr;
     return DCP_OK;
 }
@@ -913,6 +919,7 @@ inline int lasso_solve(dcp_handle* h, const T* Y, const real_t<T>* mask, int mas
     hipStream_t st = h->stream;
     h->lasso_deferred_flag = nullptr;   // (a deferral an earlier, failed call never settled dies here)
     h->lasso_deferred_it = nullptr;
+    h->lasso_deferred_copy = false;
     const int N = (int)N64, F = (int)F64, K = (int)K64;
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, 64, &hostv));

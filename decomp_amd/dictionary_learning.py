@@ -45,6 +45,12 @@ def solve(y, D, alpha, x=None, tol=1.0e-3,
     y: [n_samples, n_channels], x: [n_samples, n_features], D: [n_features, n_channels];
     float or complex, NumPy (results returned as NumPy) or torch CUDA tensors.
     ``minibatch`` is required.  Returns (it, D, x) as the reference does.
+
+    ``lasso_method='omp'`` (not in the reference) codes every minibatch by orthogonal matching pursuit
+    (decomp_amd.omp) instead of an L1 solver: ``lasso_iter`` is the sparsity (at most that many atoms per row,
+    <= 64 real, <= 32 complex), ``lasso_tol`` the residual tolerance |y - xD|^2 <= lasso_tol (None: none), ``x``
+    is not read.  ``alpha`` must be 0 (there is no penalty to apply: ValueError otherwise); ``mask`` is not
+    supported (NotImplementedError).
     """
     import torch
     kind = get_array_module(D)
@@ -67,6 +73,8 @@ def solve(y, D, alpha, x=None, tol=1.0e-3,
         raise NotImplementedError('Method %s is not yet implemented' % method)
     lasso._dict_method_code(lasso_method)      # NotImplementedError for unknown solvers
     assert _arrays.np_dtype(D).kind != 'c' or not lasso_method.endswith('_pos')   # lasso.py:92
+    if lasso_method == 'omp':
+        lasso_iter, lasso_tol = _check_omp(D, alpha, lasso_iter, lasso_tol, mask)
 
     Dd = _arrays.to_device(D, copy=True)
     dev = Dd.device.index
@@ -111,6 +119,19 @@ def solve(y, D, alpha, x=None, tol=1.0e-3,
         it, Dout, xout = solve_cd_mask(ybat, Dd, alpha, xbat, tol, minibatch, maxiter,
                                        lasso_method, lasso_iter, lasso_tol, rng, kind, mbat)
     return it, _arrays.to_caller(Dout, kind), _arrays.to_caller(xout, kind)
+
+
+def _check_omp(D, alpha, lasso_iter, lasso_tol, mask):
+    """lasso_method='omp' (decomp_amd.omp as the inner coder): lasso_iter is the sparsity and lasso_tol the
+    residual tolerance (None: none).  Returns them as the library takes them."""
+    from . import omp
+    if not (isinstance(alpha, (int, float, np.integer, np.floating)) and alpha == 0):
+        raise ValueError("lasso_method='omp' solves the sparsity-constrained problem, which has no L1 penalty: "
+                         'alpha must be 0. Given {!r}'.format(alpha))
+    if mask is not None:
+        raise NotImplementedError("lasso_method='omp' does not take a mask (a masked row has its own Gram matrix).")
+    s = omp.check_sparsity(lasso_iter, int(D.shape[0]), _arrays.np_dtype(D), what="lasso_iter (the sparsity of 'omp')")
+    return s, omp.check_tol(lasso_tol, what="lasso_tol (the residual tolerance of 'omp')")
 
 
 def solve_cd_indexed(y, D, alpha, x, tol, minibatch, maxiter,

@@ -32,6 +32,8 @@ _METHOD_CODE = {'ista': _hip.LASSO_ISTA, 'acc_ista': _hip.LASSO_ACC_ISTA,
 
 def _dict_method_code(lasso_method):
     """Code of a solver name for the dcp_dict_* entry points ('_pos' -> DCP_LASSO_POSITIVE)."""
+    if lasso_method == 'omp':      # orthogonal matching pursuit: a coder of the dictionary step only (decomp_amd.omp)
+        return _hip.LASSO_OMP
     base = lasso_method[:-4] if lasso_method.endswith('_pos') else lasso_method
     if base not in _METHOD_CODE:                                      # lasso.py:157-159
         raise NotImplementedError('Method ' + base + ' is not yet implemented.')

@@ -413,6 +413,8 @@ class HipDictBackend(object):
         self.torch = torch
         self.sfx = _arrays.suffix(D)
         self.K, self.F = D.shape
+        if lasso_method == 'omp':
+            raise NotImplementedError("lasso_method='omp' is not available in the sharded dictionary loop.")
         self.code = lasso._dict_method_code(lasso_method)
         self._pcd_table = lasso._dict_pcd_table(lasso_method, self.K, lasso_iter, D)
         self.lasso_iter, self.lasso_tol, self.alpha = int(lasso_iter), float(lasso_tol), float(alpha)
@@ -581,6 +583,8 @@ def dictionary_learning_sharded(y_local, D, alpha, x_local=None, tol=1.0e-3, min
     from . import lasso
     if minibatch is None:
         raise NotImplementedError('Only online methods are implemented. minibatch is required.')
+    if lasso_method == 'omp':
+        raise NotImplementedError("lasso_method='omp' is not available in the sharded dictionary loop.")
     lasso._dict_method_code(lasso_method)      # NotImplementedError for unknown solvers
     init = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if init else 1

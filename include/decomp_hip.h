@@ -49,6 +49,10 @@ enum { DCP_LIK_L2 = 0, DCP_LIK_KL = 1, DCP_LIK_BETA = 2 };
 /* LASSO solver codes: decomp/lasso.py:13 */
 enum { DCP_LASSO_ISTA = 0, DCP_LASSO_ACC_ISTA = 1, DCP_LASSO_FISTA = 2, DCP_LASSO_CD = 3,
        DCP_LASSO_PARALLEL_CD = 4, DCP_LASSO_ADMM = 5 };
+/* dcp_dict_* only: orthogonal matching pursuit as the inner coder (dcp_omp_*).  lasso_iter is the sparsity
+ * n_nonzero, lasso_tol the residual tolerance (< 0: none); alpha and the warm start X are not read; with
+ * DCP_LASSO_POSITIVE, with a mask or with n_nonzero outside [1, min(K, cap)] the call is DCP_ERR_INVALID. */
+enum { DCP_LASSO_OMP = 6 };
 /* dcp_dict_*: OR this into lasso_method for the '_pos' (non-negative) solvers */
 enum { DCP_LASSO_POSITIVE = 0x100 };
 
@@ -509,6 +513,36 @@ int dcp_lasso_admm_c64(dcp_handle* h, const void* Y, const float* mask, int mask
 int dcp_lasso_admm_c128(dcp_handle* h, const void* Y, const double* mask, int mask_ndim, const void* A,
                         void* X, int64_t N, int64_t F, int64_t K, double alpha, double tol, int maxiter,
                         int positive, double rho, int* it_out);
+
+/* ---- orthogonal matching pursuit (not in the reference; csrc/omp.hpp) ------------------------ */
+/* argmin_x |y - x A|^2  s.t.  |x|_0 <= n_nonzero  for every row of Y[N,F], A[K,F], greedily (batch OMP in Gram
+ * form, Rubinstein, Zibulevsky & Elad 2008): at most n_nonzero times, stop when tol >= 0 and |r|^2 <= tol; pick the
+ * atom k outside the support with the largest |r . a_k^H| / |a_k| (lowest index on ties; zero atoms never; stop when
+ * that maximum is <= 0); stop when its Cholesky pivot d = G_kk - |w|^2 <= 4096 eps G_kk (the atom is numerically in
+ * the span of the support: the previous solution is kept); else add it and solve the least squares on the support
+ * through the extended Cholesky factor.  X[N,K] is written in full (zeros off the support; the coefficients are
+ * those for the caller's A); no initial estimate is read.  tol < 0: no residual stop.  n_nonzero in
+ * [1, min(K, cap)], cap = 64 for real and 32 for complex dtypes, else DCP_ERR_INVALID.  *it_out (host) = the
+ * largest number of atoms any row selected.  Bitwise reproducible.  Synchronises the stream before returning.
+ *   dcp_omp_*      : alpha0 = Y A^H and G = A A^H on the GEMM cores, then the greedy kernel.
+ *   dcp_omp_gram_* : the greedy kernel alone on the caller's alpha0[N,K] (= Y A^H), G[K,K] (= A A^H, Hermitian)
+ *                    and ynorm2[N] (= |y|^2 per row, real; may be NULL when tol < 0). */
+int dcp_omp_f32(dcp_handle* h, const float* Y, const float* A, float* X, int64_t N, int64_t F, int64_t K,
+                int n_nonzero, double tol, int* it_out);
+int dcp_omp_f64(dcp_handle* h, const double* Y, const double* A, double* X, int64_t N, int64_t F, int64_t K,
+                int n_nonzero, double tol, int* it_out);
+int dcp_omp_c64(dcp_handle* h, const void* Y, const void* A, void* X, int64_t N, int64_t F, int64_t K,
+                int n_nonzero, double tol, int* it_out);
+int dcp_omp_c128(dcp_handle* h, const void* Y, const void* A, void* X, int64_t N, int64_t F, int64_t K,
+                 int n_nonzero, double tol, int* it_out);
+int dcp_omp_gram_f32(dcp_handle* h, const float* alpha0, const float* G, const float* ynorm2, float* X,
+                     int64_t N, int64_t K, int n_nonzero, double tol, int* it_out);
+int dcp_omp_gram_f64(dcp_handle* h, const double* alpha0, const double* G, const double* ynorm2, double* X,
+                     int64_t N, int64_t K, int n_nonzero, double tol, int* it_out);
+int dcp_omp_gram_c64(dcp_handle* h, const void* alpha0, const void* G, const float* ynorm2, void* X,
+                     int64_t N, int64_t K, int n_nonzero, double tol, int* it_out);
+int dcp_omp_gram_c128(dcp_handle* h, const void* alpha0, const void* G, const double* ynorm2, void* X,
+                      int64_t N, int64_t K, int n_nonzero, double tol, int* it_out);
 
 /* ---- row movers of the minibatch containers (decomp/utils/data.py:124-156, 214-313) ------ */
 /* gather : out[i, :] = in[index[i], :]      scatter: out[index[i], :] = in[i, :]      i < rows
