@@ -354,68 +354,27 @@ inline size_t atom_slab_elems(int64_t F) {
 }
 
 template <class T>
-inline void atom_plan(WsPlan& p, int64_t F, int64_t K) {
-    p.add<T>((size_t)K * K);
-    p.add<T>((size_t)K * K);
-    p.add<T>((size_t)K * kAtomBlkMax);
-    p.add<T>((size_t)2 * kAtomBlkMax * F);
-    p.add<T>((size_t)kAtomBlkMax * kAtomBlkMax);
-    p.add<T>((size_t)kAtomBlkMax * kAtomBlkMax);
-    p.add<T>((size_t)K * kAtomBlkMax);
-    p.add<T>((size_t)K);
-    p.add<T>(atom_slab_elems(F));
-    if (scalar_traits<T>::is_complex) p.add<real_t<T> >((size_t)4 * (K > kAtomBlkMax ? K : kAtomBlkMax) * F);
-    if (scalar_traits<T>::is_complex) {
-        p.add<real_t<T> >((size_t)2 * K * K);
-        p.add<real_t<T> >((size_t)2 * K * K);
-        p.add<real_t<T> >((size_t)2 * K * kAtomBlkMax);
-        p.add<real_t<T> >((size_t)2 * kAtomBlkMax * kAtomBlkMax);
-    }
-    if (std::is_same<T, c64>::value && atom_fused_c64_shape(F, K)) p.add<real_t<T> >(atom_fused_c64_real_count(F, K));
-}
-
-template <class T>
-inline int atom_carve(dcp_handle* h, AtomWs<T>& w, int64_t F, int64_t K) {
-    w.Ablk = ws_alloc<T>(h, (size_t)K * K);
-    w.Alook = ws_alloc<T>(h, (size_t)K * K);
-    w.Aprev = ws_alloc<T>(h, (size_t)K * kAtomBlkMax);
-    w.P = ws_alloc<T>(h, (size_t)2 * kAtomBlkMax * F);
-    w.G = ws_alloc<T>(h, (size_t)kAtomBlkMax * kAtomBlkMax);
-    w.E = ws_alloc<T>(h, (size_t)kAtomBlkMax * kAtomBlkMax);
-    w.Wl = ws_alloc<T>(h, (size_t)K * kAtomBlkMax);
-    w.rden = ws_alloc<T>(h, (size_t)K);
+inline void atom_layout(WsLayout& a, AtomWs<T>& w, int64_t F, int64_t K) {
+    a.take(w.Ablk, (size_t)K * K);
+    a.take(w.Alook, (size_t)K * K);
+    a.take(w.Aprev, (size_t)K * kAtomBlkMax);
+    a.take(w.P, (size_t)2 * kAtomBlkMax * F);
+    a.take(w.G, (size_t)kAtomBlkMax * kAtomBlkMax);
+    a.take(w.E, (size_t)kAtomBlkMax * kAtomBlkMax);
+    a.take(w.Wl, (size_t)K * kAtomBlkMax);
+    a.take(w.rden, (size_t)K);
     w.slab_count = atom_slab_elems(F);
-    w.slabs = ws_alloc<T>(h, w.slab_count);
+    a.take(w.slabs, w.slab_count);
     if (scalar_traits<T>::is_complex) {
-        w.ext = ws_alloc<real_t<T> >(h, (size_t)4 * (K > kAtomBlkMax ? K : kAtomBlkMax) * F);
-        if (!w.ext) return fail(h, DCP_ERR_INTERNAL, "atom sweep workspace plan");
+        a.take(w.ext, (size_t)4 * (K > kAtomBlkMax ? K : kAtomBlkMax) * F);
+        a.take(w.rows_blk, (size_t)2 * K * K);
+        a.take(w.rows_look, (size_t)2 * K * K);
+        a.take(w.rows_prev, (size_t)2 * K * kAtomBlkMax);
+        a.take(w.rows_E, (size_t)2 * kAtomBlkMax * kAtomBlkMax);
     }
-    if (scalar_traits<T>::is_complex) {
-        w.rows_blk = ws_alloc<real_t<T> >(h, (size_t)2 * K * K);
-        w.rows_look = ws_alloc<real_t<T> >(h, (size_t)2 * K * K);
-        w.rows_prev = ws_alloc<real_t<T> >(h, (size_t)2 * K * kAtomBlkMax);
-        w.rows_E = ws_alloc<real_t<T> >(h, (size_t)2 * kAtomBlkMax * kAtomBlkMax);
-        if (!w.rows_blk || !w.rows_look || !w.rows_prev || !w.rows_E)
-            return fail(h, DCP_ERR_INTERNAL, "atom sweep workspace plan");
-    }
-    if (std::is_same<T, c64>::value && atom_fused_c64_shape(F, K)) {
-        w.fused_reals = ws_alloc<real_t<T> >(h, atom_fused_c64_real_count(F, K));
-        if (!w.fused_reals) return fail(h, DCP_ERR_INTERNAL, "atom sweep workspace plan");
-    }
-    if (!w.Ablk || !w.Alook || !w.Aprev || !w.P || !w.G || !w.E || !w.Wl || !w.rden || !w.slabs)
-        return fail(h, DCP_ERR_INTERNAL, "atom sweep workspace plan");
-    return DCP_OK;
+    if (std::is_same<T, c64>::value && atom_fused_c64_shape(F, K))
+        a.take(w.fused_reals, atom_fused_c64_real_count(F, K));
 }
-
-#ifndef DCP_LAUNCH_OK
-#define DCP_LAUNCH_OK(h, what)                                                        \
-    do {                                                                              \
-        hipError_t _e = (what);                                                       \
-        if (_e != hipSuccess)                                                         \
-            return dcp::fail((h), DCP_ERR_HIP, std::string("launch failed: ") +       \
-                                                   hipGetErrorString(_e));            \
-    } while (0)
-#endif
 
 // D_new (holding a copy of D on entry) <- the swept dictionary.  A [K,K], B [K,F] statistics.
 template <class T>

@@ -6,52 +6,33 @@
 
 namespace dcp {
 
-// workspace of the step's inner coder: the LASSO solvers' plan, or the (smaller) one of DCP_LASSO_OMP -- both fill
+// workspace of the step's inner coder: the LASSO solvers' layout, or the (smaller) one of DCP_LASSO_OMP -- both fill
 // a LassoWs
 template <class T>
-inline void dict_coder_plan(WsPlan& p, int64_t Nb, int64_t F, int64_t K, int mask_ndim, int base) {
-    if (base == DCP_LASSO_OMP) omp_plan<T>(p, Nb, F, K);
-    else lasso_plan<T>(p, Nb, F, K, mask_ndim, base);
-}
-template <class T>
-inline int dict_coder_carve(dcp_handle* h, LassoWs<T>& w, int64_t Nb, int64_t F, int64_t K, int mask_ndim, int base) {
-    if (base == DCP_LASSO_OMP) return omp_carve<T>(h, w, Nb, F, K);
-    return lasso_carve<T>(h, w, Nb, F, K, mask_ndim, base);
+inline void dict_coder_layout(WsLayout& a, LassoWs<T>& w, int64_t Nb, int64_t F, int64_t K, int mask_ndim, int base) {
+    if (base == DCP_LASSO_OMP) omp_layout<T>(a, w, Nb, F, K);
+    else lasso_layout<T>(a, w, Nb, F, K, mask_ndim, base);
 }
 
+// the atom sweep's buffers on the padded sizes, then the padded copies (dict_pads)
 template <class T>
-inline void dict_plan_extra(WsPlan& p, int64_t Nb, int64_t F, int64_t K) {
-    typedef real_t<T> R;
-    p.add<T>(dict_slab_elems<T>(Nb, F, K));
-    p.add<R>((size_t)2 * ((F + 63) / 64) + 512);
-    p.add<R>(4);
+inline void dict_sweep_layout(WsLayout& a, DictWs<T>& w, int64_t F, int64_t K) {
     const bool pads = dict_pads<T>(F, K);
     const int64_t Kp = pads ? pad64(K) : K, Fp = pads ? pad64(F) : F;
-    atom_plan<T>(p, Fp, Kp);
+    atom_layout<T>(a, w.atom, Fp, Kp);
     if (pads) {
-        p.add<T>((size_t)Kp * Kp);
-        p.add<T>((size_t)Kp * Fp);
-        p.add<T>((size_t)Kp * Fp);
+        a.take(w.padA, (size_t)Kp * Kp);
+        a.take(w.padB, (size_t)Kp * Fp);
+        a.take(w.padD, (size_t)Kp * Fp);
     }
 }
 template <class T>
-inline int dict_carve_extra(dcp_handle* h, DictWs<T>& w, int64_t Nb, int64_t F, int64_t K) {
-    typedef real_t<T> R;
+inline void dict_extra_layout(WsLayout& a, DictWs<T>& w, int64_t Nb, int64_t F, int64_t K) {
     w.slab_count = dict_slab_elems<T>(Nb, F, K);
-    w.slabs = ws_alloc<T>(h, w.slab_count);
-    w.partial = ws_alloc<R>(h, (size_t)2 * ((F + 63) / 64) + 512);
-    w.scal = ws_alloc<R>(h, 4);
-    const bool pads = dict_pads<T>(F, K);
-    const int64_t Kp = pads ? pad64(K) : K, Fp = pads ? pad64(F) : F;
-    DCP_TRY(atom_carve<T>(h, w.atom, Fp, Kp));
-    if (pads) {
-        w.padA = ws_alloc<T>(h, (size_t)Kp * Kp);
-        w.padB = ws_alloc<T>(h, (size_t)Kp * Fp);
-        w.padD = ws_alloc<T>(h, (size_t)Kp * Fp);
-        if (!w.padA || !w.padB || !w.padD) return fail(h, DCP_ERR_INTERNAL, "dict workspace plan");
-    }
-    if (!w.slabs || !w.partial || !w.scal) return fail(h, DCP_ERR_INTERNAL, "dict workspace plan");
-    return DCP_OK;
+    a.take(w.slabs, w.slab_count);
+    a.take(w.partial, (size_t)2 * ((F + 63) / 64) + 512);
+    a.take(w.scal, 4);
+    dict_sweep_layout<T>(a, w, F, K);
 }
 
 template <class T>
@@ -148,15 +129,12 @@ inline int dict_stats_api(dcp_handle* h, const T* Y, T* X, const T* D, int64_t N
     if (!dict_lasso_method_ok(lasso_method))
         return fail(h, DCP_ERR_INVALID, "bad lasso method");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    dict_coder_plan<T>(plan, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE);
-    dict_plan_extra<T>(plan, Nb, F, K);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     LassoWs<T> lw;
     DictWs<T> dw;
-    DCP_TRY(dict_coder_carve<T>(h, lw, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE));
-    DCP_TRY(dict_carve_extra<T>(h, dw, Nb, F, K));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        dict_coder_layout<T>(a, lw, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE);
+        dict_extra_layout<T>(a, dw, Nb, F, K);
+    }));
     return dict_stats_core<T>(h, Y, X, D, Nb, F, K, alpha, lasso_method, lasso_iter, lasso_tol, stats,
                               lasso_it, lw, dw);
 }
@@ -169,28 +147,11 @@ inline int dict_update_api(dcp_handle* h, const T* stats, double beta, T* A, T* 
     if (!stats || !A || !B || !D || !Dnew || !maxdiff_dev) return fail(h, DCP_ERR_INVALID, "null pointer");
     if (F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    const bool pads = dict_pads<T>(F, K);
-    const int64_t Kp = pads ? pad64(K) : K, Fp = pads ? pad64(F) : F;
-    WsPlan plan;
-    plan.add<R>((size_t)2 * ((F + 63) / 64) + 512);
-    atom_plan<T>(plan, Fp, Kp);
-    if (pads) {
-        plan.add<T>((size_t)Kp * Kp);
-        plan.add<T>((size_t)Kp * Fp);
-        plan.add<T>((size_t)Kp * Fp);
-    }
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     DictWs<T> dw;
-    dw.partial = ws_alloc<R>(h, (size_t)2 * ((F + 63) / 64) + 512);
-    DCP_TRY(atom_carve<T>(h, dw.atom, Fp, Kp));
-    if (pads) {
-        dw.padA = ws_alloc<T>(h, (size_t)Kp * Kp);
-        dw.padB = ws_alloc<T>(h, (size_t)Kp * Fp);
-        dw.padD = ws_alloc<T>(h, (size_t)Kp * Fp);
-        if (!dw.padA || !dw.padB || !dw.padD) return fail(h, DCP_ERR_INTERNAL, "dict workspace plan");
-    }
-    if (!dw.partial) return fail(h, DCP_ERR_INTERNAL, "dict workspace plan");
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        a.take(dw.partial, (size_t)2 * ((F + 63) / 64) + 512);
+        dict_sweep_layout<T>(a, dw, F, K);
+    }));
     DCP_TRY(dict_update<T>(h, stats, (R)beta, A, B, D, Dnew, F, K, maxdiff_dev, dw));
     if (h->pf_inflight) {     // a registered row prefetch was started beside the sweep: join it
         DCP_TRY(main_after_side(h));
@@ -212,15 +173,12 @@ inline int dict_step_core(dcp_handle* h, const T* Y, T* X, const T* D, T* Dnew, 
     if (!dict_lasso_method_ok(lasso_method))
         return fail(h, DCP_ERR_INVALID, "bad lasso method");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    dict_coder_plan<T>(plan, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE);
-    dict_plan_extra<T>(plan, Nb, F, K);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     LassoWs<T> lw;
     DictWs<T> dw;
-    DCP_TRY(dict_coder_carve<T>(h, lw, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE));
-    DCP_TRY(dict_carve_extra<T>(h, dw, Nb, F, K));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        dict_coder_layout<T>(a, lw, Nb, F, K, 0, lasso_method & ~DCP_LASSO_POSITIVE);
+        dict_extra_layout<T>(a, dw, Nb, F, K);
+    }));
     // one GPU: the statistics stay as ordered split-K partials (no [K, F+K] sum is formed: `stats` = null) and
     // are summed by the A / B accumulation itself
     DCP_TRY(dict_stats_core<T>(h, Y, X, D, Nb, F, K, alpha, lasso_method, lasso_iter, lasso_tol, (T*)nullptr,
@@ -283,20 +241,16 @@ inline int dict_mask_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, T* 
         return fail(h, DCP_ERR_INVALID, "bad lasso method");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     hipStream_t st = h->stream;
-    WsPlan plan;
-    dict_coder_plan<T>(plan, Nb, F, K, 2, lasso_method & ~DCP_LASSO_POSITIVE);
-    dict_plan_extra<T>(plan, Nb, F, K);
-    plan.add<T>((size_t)Nb * F);   // y o m
-    plan.add<T>((size_t)K * F);    // x^H (y o m)
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     LassoWs<T> lw;
     DictWs<T> dw;
-    DCP_TRY(dict_coder_carve<T>(h, lw, Nb, F, K, 2, lasso_method & ~DCP_LASSO_POSITIVE));
-    DCP_TRY(dict_carve_extra<T>(h, dw, Nb, F, K));
-    T* Ym = ws_alloc<T>(h, (size_t)Nb * F);
-    T* sB = ws_alloc<T>(h, (size_t)K * F);
-    if (!Ym || !sB) return fail(h, DCP_ERR_INTERNAL, "dict workspace plan");
+    T* Ym = nullptr;   // y o m
+    T* sB = nullptr;   // x^H (y o m)
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        dict_coder_layout<T>(a, lw, Nb, F, K, 2, lasso_method & ~DCP_LASSO_POSITIVE);
+        dict_extra_layout<T>(a, dw, Nb, F, K);
+        a.take(Ym, (size_t)Nb * F);
+        a.take(sB, (size_t)K * F);
+    }));
     int it = 0;
     DCP_TRY(dict_lasso<T>(h, Y, M, 2, D, X, Nb, F, K, alpha, lasso_tol, lasso_iter, lasso_method, &it, lw));
     DCP_TRY(lasso_settle_deferred(h));   // (the masked solvers never defer; kept next to the local it belongs to)

@@ -67,14 +67,12 @@ int normalize_diff_api(dcp_handle* h, const T* U, const T* ref, T* out, int64_t 
     if (K <= 0 || F <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
     if (K > 0x7fffffffLL) return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    plan.add<T>((size_t)K);
-    plan.add<T>(2);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    T* rowmax = ws_alloc<T>(h, (size_t)K);
-    T* md = ws_alloc<T>(h, 2);
-    if (!rowmax || !md) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+    T* rowmax = nullptr;
+    T* md = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        a.take(rowmax, (size_t)K);
+        a.take(md, 2);
+    }));
     hipLaunchKernelGGL((row_normalize_kernel<T>), dim3((unsigned)K), dim3(256), 0, h->stream, U, (long)F,
                        (long)F, strict, ref, (long)F, out, (long)F, rowmax, (T*)nullptr, (T*)nullptr,
                        (T*)nullptr);
@@ -189,14 +187,12 @@ int inv_api(dcp_handle* h, const T* X, int64_t batch, int64_t n, T* out) {
     if (batch == 0) return DCP_OK;
     if (batch > 0x7fffffffLL) return fail(h, DCP_ERR_INVALID, "batch exceeds 2^31-1");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    plan.add<TW>((size_t)batch * n * 2 * n);
-    plan.add<TW>((size_t)batch * n);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    TW* W = ws_alloc<TW>(h, (size_t)batch * n * 2 * n);
-    TW* col = ws_alloc<TW>(h, (size_t)batch * n);
-    if (!W || !col) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+    TW* W = nullptr;
+    TW* col = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        a.take(W, (size_t)batch * n * 2 * n);
+        a.take(col, (size_t)batch * n);
+    }));
     hipLaunchKernelGGL((inv_batched_kernel<T>), dim3((unsigned)batch), dim3(256), 0, h->stream, X, (int)n, W, col,
                        out);
     DCP_HIP_OK(h, hipGetLastError());

@@ -25,9 +25,9 @@ struct dcp_handle {
     // ordered against the main stream with events only (side_after_main / main_after_side).
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
-    // Workspace: one grow-only arena.  A public call plans its total need, reserves it
-    // (ws_reserve: reallocates only when the plan outgrows the arena, i.e. on the first
-    // call of a given problem size, never in steady state), then bumps (ws_alloc).
+    // Workspace: one grow-only arena.  A public call describes its buffers once (ws_lay_out): the description is
+    // walked to size the total, the total is reserved (ws_reserve: reallocates only when it outgrows the arena,
+    // i.e. on the first call of a given problem size, never in steady state), and walked again to hand them out.
     char* arena = nullptr;
     size_t arena_bytes = 0;
     size_t arena_used = 0;
@@ -89,6 +89,15 @@ inline int fail(dcp_handle* h, int code, const std::string& msg) {
         if (_e != hipSuccess)                                                                \
             return dcp::fail((h), DCP_ERR_HIP,                                               \
                              std::string(#expr) + ": " + hipGetErrorString(_e));             \
+    } while (0)
+
+// the status of a kernel launch (hipGetLastError() after it, or what a launcher returned)
+#define DCP_LAUNCH_OK(h, what)                                                        \
+    do {                                                                              \
+        hipError_t _e = (what);                                                       \
+        if (_e != hipSuccess)                                                         \
+            return dcp::fail((h), DCP_ERR_HIP, std::string("launch failed: ") +       \
+                                                   hipGetErrorString(_e));            \
     } while (0)
 
 #define DCP_TRY(expr)                  \
@@ -165,10 +174,6 @@ inline int start_registered_prefetch(dcp_handle* h) {
     return DCP_OK;
 }
 
-inline void ws_reset(dcp_handle* h) {
-    h->arena_used = 0;
-}
-
 // The arena's previous user may still be running on another stream: the current stream waits for it
 // (an event recorded on the previous stream, no host sync).  decomp_hip.h makes the caller keep that stream
 // alive until this point; the device synchronisation below only covers a FAILED record / wait on a live
@@ -221,25 +226,34 @@ inline int ws_reserve(dcp_handle* h, size_t bytes) {
 
 inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
-// Bump allocation from the reserved arena; nullptr when the reservation was too small
-// (a library bug, reported by the caller as DCP_ERR_INTERNAL).
-template <class T>
-inline T* ws_alloc(dcp_handle* h, size_t count) {
-    const size_t bytes = align256(count * sizeof(T));
-    if (h->arena_used + bytes > h->arena_bytes) return nullptr;
-    T* p = reinterpret_cast<T*>(h->arena + h->arena_used);
-    h->arena_used += bytes;
-    return p;
-}
-
-// Sizing helper mirroring ws_alloc.
-struct WsPlan {
-    size_t total = 0;
+// One walk over a call's workspace items.  Without a base it only adds up the sizes (every pointer comes back null);
+// based at the arena it hands out the same items in the same order, each 256-byte aligned.
+struct WsLayout {
+    char* base = nullptr;
+    size_t used = 0;
     template <class T>
-    void add(size_t count) {
-        total += align256(count * sizeof(T));
+    void take(T*& p, size_t count) {
+        p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += align256(count * sizeof(T));
     }
 };
+
+// Sizes, reserves and hands out a call's whole workspace from ONE description: `items(WsLayout&)` runs twice, first
+// to size the reservation, then based at the arena.  It may only call take() and set fields derived from the sizes
+// (slab_count): it must not read the pointers, touch the handle or enqueue anything.  A workspace struct has one
+// layout function (lasso_layout, atom_layout, ...) that entry points compose inside `items`.
+template <class Items>
+inline int ws_lay_out(dcp_handle* h, Items&& items) {
+    WsLayout sizing;
+    items(sizing);
+    DCP_TRY(ws_reserve(h, sizing.used));
+    WsLayout carving{h->arena};
+    items(carving);
+    h->arena_used = carving.used;
+    if (carving.used != sizing.used)
+        return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch: the sizing walk and the carving walk differ");
+    return DCP_OK;
+}
 
 inline int host_scratch(dcp_handle* h, size_t bytes, void** out) {
     if (bytes > h->host_pinned_bytes) {

@@ -1,4 +1,4 @@
-// C-ABI glue for the LASSO solvers: argument checks, workspace planning, prox selection.
+// C-ABI glue for the LASSO solvers: argument checks, workspace layout, prox selection.
 #pragma once
 #include "lasso_impl.hpp"
 
@@ -23,12 +23,8 @@ inline int lasso_api(dcp_handle* h, const T* Y, const real_t<T>* mask, int mask_
     if (positive && scalar_traits<T>::is_complex)
         return fail(h, DCP_ERR_INVALID, "positive solvers need a real dtype (lasso.py:92)");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    lasso_plan<T>(plan, N, F, K, mask_ndim, method);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     LassoWs<T> w;
-    DCP_TRY(lasso_carve<T>(h, w, N, F, K, mask_ndim, method));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { lasso_layout<T>(a, w, N, F, K, mask_ndim, method); }));
     if constexpr (scalar_traits<T>::is_complex) {
         return lasso_solve<T, PROX_COMPLEX>(h, Y, mask, mask_ndim, A, X, N, F, K, (R)alpha, (R)tol,
                                             maxiter, method, it_out, w, extra);

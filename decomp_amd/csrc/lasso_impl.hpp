@@ -23,7 +23,7 @@
 #include "gemm.hpp"
 #include "handle.hpp"
 #include "kernels_small.hpp"
-#include "nmf_impl.hpp"  // DCP_LAUNCH_OK, column_sums
+#include "nmf_impl.hpp"  // kMaxSplits, column_sums
 #include "lasso_extra.hpp"  // parallel_cd and admm kernels
 
 namespace dcp {
@@ -737,85 +737,40 @@ struct LassoWs {
 };
 
 template <class T>
-inline void lasso_plan(WsPlan& p, int64_t N, int64_t F, int64_t K, int mask_ndim, int method) {
-    typedef real_t<T> R;
-    p.add<T>((size_t)K * F);
-    if (mask_ndim != 0) p.add<T>((size_t)N * F);
-    p.add<T>((size_t)N * K);
-    p.add<T>((size_t)K * K);
-    if (mask_ndim == 2) p.add<T>((size_t)K * F);
-    p.add<T>((size_t)kMaxSplits * K * K);
-    for (int i = 0; i < 4; ++i) p.add<T>((size_t)N * K);
-    if ((method == DCP_LASSO_CD || method == DCP_LASSO_PARALLEL_CD) && mask_ndim != 2)
-        p.add<T>((size_t)N * K);
-    if (mask_ndim == 2) p.add<T>((size_t)N * F);
-    if (method == DCP_LASSO_ADMM) {
-        if (mask_ndim == 2) {
-            p.add<work_t<T> >((size_t)N * K * K);
-        } else {
-            p.add<work_t<T> >((size_t)K * K);
-            p.add<work_t<T> >((size_t)K * K);
-        }
-    }
-    for (int i = 0; i < 4; ++i) p.add<R>((size_t)K);
-    p.add<R>((size_t)N);
-    p.add<R>((size_t)F);
-    p.add<R>((size_t)64 * F);
-    p.add<R>(4);
-    p.add<R>((size_t)64 * K);
-    p.add<int>(4);
-    if (scalar_traits<T>::is_complex) {
-        p.add<R>((size_t)4 * K * F);
-        p.add<R>((size_t)4 * K * K);
-    }
-}
-
-template <class T>
-inline int lasso_carve(dcp_handle* h, LassoWs<T>& w, int64_t N, int64_t F, int64_t K, int mask_ndim,
-                       int method) {
-    typedef real_t<T> R;
-    w.An = ws_alloc<T>(h, (size_t)K * F);
-    if (mask_ndim != 0) w.Ym = ws_alloc<T>(h, (size_t)N * F);
-    w.yAt = ws_alloc<T>(h, (size_t)N * K);
-    w.AAt = ws_alloc<T>(h, (size_t)K * K);
-    if (mask_ndim == 2) w.Am = ws_alloc<T>(h, (size_t)K * F);
+inline void lasso_layout(WsLayout& a, LassoWs<T>& w, int64_t N, int64_t F, int64_t K, int mask_ndim, int method) {
+    a.take(w.An, (size_t)K * F);
+    if (mask_ndim != 0) a.take(w.Ym, (size_t)N * F);
+    a.take(w.yAt, (size_t)N * K);
+    a.take(w.AAt, (size_t)K * K);
+    if (mask_ndim == 2) a.take(w.Am, (size_t)K * F);
     w.slab_count = (size_t)kMaxSplits * K * K;
-    w.slabs = ws_alloc<T>(h, w.slab_count);
-    for (int i = 0; i < 4; ++i) w.xb[i] = ws_alloc<T>(h, (size_t)N * K);
-    const bool wants_g = (method == DCP_LASSO_CD || method == DCP_LASSO_PARALLEL_CD) && mask_ndim != 2;
-    if (wants_g) w.G = ws_alloc<T>(h, (size_t)N * K);
-    if (mask_ndim == 2) w.T1 = ws_alloc<T>(h, (size_t)N * F);
+    a.take(w.slabs, w.slab_count);
+    for (int i = 0; i < 4; ++i) a.take(w.xb[i], (size_t)N * K);
+    if ((method == DCP_LASSO_CD || method == DCP_LASSO_PARALLEL_CD) && mask_ndim != 2)
+        a.take(w.G, (size_t)N * K);
+    if (mask_ndim == 2) a.take(w.T1, (size_t)N * F);
     if (method == DCP_LASSO_ADMM) {
         if (mask_ndim == 2) {
-            w.inv_a = ws_alloc<work_t<T> >(h, (size_t)N * K * K);
+            a.take(w.inv_a, (size_t)N * K * K);
         } else {
-            w.inv_a = ws_alloc<work_t<T> >(h, (size_t)K * K);
-            w.inv_b = ws_alloc<work_t<T> >(h, (size_t)K * K);
-            if (!w.inv_b) return fail(h, DCP_ERR_INTERNAL, "lasso workspace plan mismatch");
+            a.take(w.inv_a, (size_t)K * K);
+            a.take(w.inv_b, (size_t)K * K);
         }
-        if (!w.inv_a) return fail(h, DCP_ERR_INTERNAL, "lasso workspace plan mismatch");
     }
-    w.s = ws_alloc<R>(h, (size_t)K);
-    w.alphak = ws_alloc<R>(h, (size_t)K);
-    w.tolk = ws_alloc<R>(h, (size_t)K);
-    w.akk = ws_alloc<R>(h, (size_t)K);
-    w.rowscale = ws_alloc<R>(h, (size_t)N);
-    w.mbar = ws_alloc<R>(h, (size_t)F);
-    w.part = ws_alloc<R>(h, (size_t)64 * F);
-    w.scal = ws_alloc<R>(h, 4);
-    w.gpart = ws_alloc<R>(h, (size_t)64 * K);
-    w.flag = ws_alloc<int>(h, 4);
+    a.take(w.s, (size_t)K);
+    a.take(w.alphak, (size_t)K);
+    a.take(w.tolk, (size_t)K);
+    a.take(w.akk, (size_t)K);
+    a.take(w.rowscale, (size_t)N);
+    a.take(w.mbar, (size_t)F);
+    a.take(w.part, (size_t)64 * F);
+    a.take(w.scal, 4);
+    a.take(w.gpart, (size_t)64 * K);
+    a.take(w.flag, 4);
     if (scalar_traits<T>::is_complex) {
-        w.ext1 = ws_alloc<R>(h, (size_t)4 * K * F);
-        w.ext2 = ws_alloc<R>(h, (size_t)4 * K * K);
-        if (!w.ext1 || !w.ext2) return fail(h, DCP_ERR_INTERNAL, "lasso workspace plan mismatch");
+        a.take(w.ext1, (size_t)4 * K * F);
+        a.take(w.ext2, (size_t)4 * K * K);
     }
-    if (!w.An || !w.yAt || !w.AAt || !w.slabs || !w.xb[3] || !w.s || !w.alphak || !w.tolk ||
-        !w.akk || !w.rowscale || !w.mbar || !w.part || !w.scal || !w.gpart || !w.flag ||
-        (mask_ndim != 0 && !w.Ym) || (mask_ndim == 2 && (!w.Am || !w.T1)) ||
-        (wants_g && !w.G))
-        return fail(h, DCP_ERR_INTERNAL, "lasso workspace plan mismatch");
-    return DCP_OK;
 }
 
 // C[K,K] = P . Q^H for [K,F] operands, reduction over F split into ordered slabs.

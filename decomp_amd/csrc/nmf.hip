@@ -33,26 +33,14 @@ struct MuStep {
 
     int64_t W() const { return nmf_stats_width(s.F, s.K, s.lik, s.masked); }
     bool want_bits() const { return s.masked && std::is_same<T, float>::value && s.lik == DCP_LIK_L2; }
-    void plan(WsPlan& plan) const {
-        nmf_plan_stats(plan, s, s.masked);
-        nmf_plan_update<T>(plan, s.F, s.K);
-        plan.add<T>((size_t)s.K * W());   // stats
+    void layout(WsLayout& a) {
+        nmf_stats_layout(a, ws, s, s.masked);
+        nmf_update_layout(a, wu, s.F, s.K);
+        a.take(stats, (size_t)s.K * W());
         if (want_bits()) {
-            plan.add<uint32_t>(mask_bits_words(s.N, s.F));
-            plan.add<int>(4);
+            a.take(mbits, mask_bits_words(s.N, s.F));
+            a.take(mflag, 4);
         }
-    }
-    int carve(dcp_handle* h) {
-        DCP_TRY(nmf_carve_stats(h, ws, s, s.masked));
-        DCP_TRY(nmf_carve_update(h, wu, s.F, s.K));
-        stats = ws_alloc<T>(h, (size_t)s.K * W());
-        if (want_bits()) {
-            mbits = ws_alloc<uint32_t>(h, mask_bits_words(s.N, s.F));
-            mflag = ws_alloc<int>(h, 4);
-        }
-        if (!stats || (want_bits() && (!mbits || !mflag)))
-            return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
-        return DCP_OK;
     }
     int prepare(dcp_handle* h) {
         Ypre = Y;
@@ -100,14 +88,10 @@ struct NmfScalarWs {
     double* part = nullptr;
     double* host = nullptr;
     int reserve(dcp_handle* h, int64_t N, int64_t F) {
-        WsPlan plan;
-        plan.add<T>((size_t)N * F);
-        plan.add<double>(blocks);
-        DCP_TRY(ws_reserve(h, plan.total));
-        ws_reset(h);
-        tmp = ws_alloc<T>(h, (size_t)N * F);
-        part = ws_alloc<double>(h, blocks);
-        if (!tmp || !part) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+        DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+            a.take(tmp, (size_t)N * F);
+            a.take(part, blocks);
+        }));
         void* hostv = nullptr;
         DCP_TRY(host_scratch(h, sizeof(double) * blocks, &hostv));
         host = reinterpret_cast<double*>(hostv);
@@ -124,12 +108,8 @@ int nmf_mu_stats_api(dcp_handle* h, const T* Y, const T* mask, const T* X, T* X_
     DCP_HIP_OK(h, hipSetDevice(h->device));
     const bool masked = mask != nullptr;
     NmfShape<T> s{N, F, K, lik, masked};
-    WsPlan plan;
-    nmf_plan_stats(plan, s, masked);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     NmfStatsWs<T> ws;
-    DCP_TRY(nmf_carve_stats(h, ws, s, masked));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { nmf_stats_layout(a, ws, s, masked); }));
     const T* Ypre = nullptr;
     DCP_TRY(nmf_premask<T>(h, Y, mask, N, F, ws.Ym, &Ypre));
     return nmf_stats<T>(h, Ypre, mask, X, X_out, D, s, stats, ws, 3, nmf_penalty(h));
@@ -143,12 +123,8 @@ int nmf_mu_stats_prepared_api(dcp_handle* h, const T* Ym, const T* mask, const u
     if (!stats || !X_out || !mask) return fail(h, DCP_ERR_INVALID, "stats / X_out / mask is null");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     NmfShape<T> s{N, F, K, lik, true};
-    WsPlan plan;
-    nmf_plan_stats(plan, s, false);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     NmfStatsWs<T> ws;
-    DCP_TRY(nmf_carve_stats(h, ws, s, false));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { nmf_stats_layout(a, ws, s, false); }));
     ws.mbits = bits;
     return nmf_stats<T>(h, Ym, mask, X, X_out, D, s, stats, ws, 3, nmf_penalty(h));
 }
@@ -160,12 +136,8 @@ int nmf_mask_prepare_api(dcp_handle* h, const T* Y, const T* mask, int64_t N, in
     if (!Y || !mask || !Ym || !binary) return fail(h, DCP_ERR_INVALID, "null pointer");
     if (N <= 0 || F <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    plan.add<int>(4);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    int* flag = ws_alloc<int>(h, 4);
-    if (!flag) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+    int* flag = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { a.take(flag, 4); }));
     return nmf_mask_prepare<T>(h, Y, mask, N, F, Ym, bits, flag, binary);
 }
 
@@ -178,12 +150,8 @@ int nmf_mu_update_api(dcp_handle* h, const T* stats, const T* D, T* D_new, int64
     DCP_HIP_OK(h, hipSetDevice(h->device));
     // NOTE: shares the arena with dcp_nmf_mu_stats_*: the stats call's temporaries are dead
     // by now (same stream), `stats` itself is caller memory.
-    WsPlan plan;
-    nmf_plan_update<T>(plan, F, K);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     NmfUpdateWs<T> wu;
-    DCP_TRY(nmf_carve_update(h, wu, F, K));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { nmf_update_layout(a, wu, F, K); }));
     return nmf_update<T>(h, stats, D, D_new, F, K, lik, masked != 0, maxdiff_dev, wu, maxdiff_next);
 }
 
@@ -214,15 +182,12 @@ int nmf_grads_api(dcp_handle* h, const T* Y, const T* mask, T* X, const T* D, in
     const bool gram = (lik == DCP_LIK_L2 && !masked);
     NmfShape<T> s{N, F, K, lik, masked};
     const int64_t W = nmf_stats_width(F, K, lik, masked);
-    WsPlan plan;
-    nmf_plan_stats(plan, s, masked);
-    plan.add<T>((size_t)K * W);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     NmfStatsWs<T> ws;
-    DCP_TRY(nmf_carve_stats(h, ws, s, masked));
-    T* stats = ws_alloc<T>(h, (size_t)K * W);
-    if (!stats) return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
+    T* stats = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        nmf_stats_layout(a, ws, s, masked);
+        a.take(stats, (size_t)K * W);
+    }));
     const T* Ypre = nullptr;
     DCP_TRY(nmf_premask<T>(h, Y, mask, N, F, ws.Ym, &Ypre));
     for (int i = 0; i < n_x_updates; ++i)
@@ -252,12 +217,8 @@ int nmf_grad_x_api(dcp_handle* h, const T* Y, const T* mask, const T* X, const T
     DCP_HIP_OK(h, hipSetDevice(h->device));
     const bool masked = mask != nullptr;
     NmfShape<T> s{N, F, K, lik, masked};
-    WsPlan plan;
-    nmf_plan_stats(plan, s, masked);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     NmfStatsWs<T> ws;
-    DCP_TRY(nmf_carve_stats(h, ws, s, masked));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { nmf_stats_layout(a, ws, s, masked); }));
     const T* Ypre = nullptr;
     DCP_TRY(nmf_premask<T>(h, Y, mask, N, F, ws.Ym, &Ypre));
     return nmf_grad_x<T>(h, Ypre, mask, X, D, s, grad_pos, grad_neg, ws);
@@ -335,15 +296,12 @@ int nmf_apply_api(dcp_handle* h, const T* D, const T* P, const T* Q, double alph
     if (!D || !P || !Q || !D_new || !maxdiff) return fail(h, DCP_ERR_INVALID, "null pointer");
     if (K <= 0 || F <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    nmf_plan_update<T>(plan, F, K);
-    plan.add<T>(2);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     NmfUpdateWs<T> wu;
-    DCP_TRY(nmf_carve_update(h, wu, F, K));
-    T* md = ws_alloc<T>(h, 2);
-    if (!md) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+    T* md = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        nmf_update_layout(a, wu, F, K);
+        a.take(md, 2);
+    }));
     hipLaunchKernelGGL((nmf_rule_kernel<T>), dim3(grid_for(K * F)), dim3(256), 0, h->stream, D, P, Q,
                        (long)(K * F), (T)alpha, wu.U);
     DCP_HIP_OK(h, hipGetLastError());

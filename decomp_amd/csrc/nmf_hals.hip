@@ -125,24 +125,12 @@ struct HalsStep {
     T* U = nullptr;     // the swept, not yet normalised D
     T* nrm = nullptr;   // atom norms
 
-    void plan(WsPlan& plan) const {
-        nmf_plan_stats(plan, s, false);
-        plan.add<T>((size_t)s.K * (s.F + s.K));
-        plan.add<T>((size_t)s.K * s.F);
-        plan.add<T>((size_t)s.K);
-        if (mask) plan.add<T>((size_t)s.N * s.F);
-    }
-    int carve(dcp_handle* h) {
-        DCP_TRY(nmf_carve_stats(h, ws, s, false));
-        stats = ws_alloc<T>(h, (size_t)s.K * (s.F + s.K));
-        U = ws_alloc<T>(h, (size_t)s.K * s.F);
-        nrm = ws_alloc<T>(h, (size_t)s.K);
-        if (!stats || !U || !nrm) return fail(h, DCP_ERR_INTERNAL, "hals workspace plan mismatch");
-        if (mask) {
-            Yi = ws_alloc<T>(h, (size_t)s.N * s.F);
-            if (!Yi) return fail(h, DCP_ERR_INTERNAL, "em-hals workspace plan mismatch");
-        }
-        return DCP_OK;
+    void layout(WsLayout& a) {
+        nmf_stats_layout(a, ws, s, false);
+        a.take(stats, (size_t)s.K * (s.F + s.K));
+        a.take(U, (size_t)s.K * s.F);
+        a.take(nrm, (size_t)s.K);
+        if (mask) a.take(Yi, (size_t)s.N * s.F);
     }
     int prepare(dcp_handle*) { return DCP_OK; }
     int iterate(dcp_handle* h, const T* Xc, T* Xn, const T* Dc, T* Dn, const NmfStopSlots<T>& slots) {
@@ -196,12 +184,8 @@ int nmf_hals_stats_api(dcp_handle* h, const T* Y, const T* X, T* X_out, const T*
     if (!stats || !X_out) return fail(h, DCP_ERR_INVALID, "stats / X_out is null");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     NmfShape<T> s{N, F, K, DCP_LIK_L2, false};
-    WsPlan plan;
-    nmf_plan_stats(plan, s, false);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     NmfStatsWs<T> ws;
-    DCP_TRY(nmf_carve_stats(h, ws, s, false));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { nmf_stats_layout(a, ws, s, false); }));
     return hals_x_side<T>(h, Y, X, X_out, D, s, stats, ws, nmf_penalty(h));
 }
 
@@ -213,14 +197,12 @@ int nmf_hals_update_api(dcp_handle* h, const T* stats, const T* D, T* D_new, T* 
     DCP_TRY(check_nmf_dims(h, stats, D, X, N, F, K, "null pointer"));
     DCP_HIP_OK(h, hipSetDevice(h->device));
     // shares the arena with dcp_nmf_hals_stats_*: its temporaries are dead by now (same stream)
-    WsPlan plan;
-    plan.add<T>((size_t)K * F);   // U
-    plan.add<T>((size_t)K);       // atom norms
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    T* U = ws_alloc<T>(h, (size_t)K * F);
-    T* nrm = ws_alloc<T>(h, (size_t)K);
-    if (!U || !nrm) return fail(h, DCP_ERR_INTERNAL, "hals workspace plan mismatch");
+    T* U = nullptr;     // the swept, not yet normalised D
+    T* nrm = nullptr;   // atom norms
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        a.take(U, (size_t)K * F);
+        a.take(nrm, (size_t)K);
+    }));
     DCP_TRY(hals_d_sweep<T>(h, D, U, F, K, stats));
     // without a ping-pong partner the max is formed from zero here (the kernel's atomic max needs it)
     if (!maxdiff_next) DCP_HIP_OK(h, hipMemsetAsync(maxdiff_dev, 0, sizeof(T), h->stream));

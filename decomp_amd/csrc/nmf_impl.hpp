@@ -129,34 +129,17 @@ inline size_t nmf_slab_elems(const NmfShape<T>& s) {
 }
 
 template <class T>
-inline void nmf_plan_stats(WsPlan& plan, const NmfShape<T>& s, bool need_ym) {
+inline void nmf_stats_layout(WsLayout& a, NmfStatsWs<T>& w, const NmfShape<T>& s, bool need_ym) {
     const bool gram = (s.lik == DCP_LIK_L2 && !s.masked);
-    plan.add<T>((size_t)s.N * s.K);                       // Q
-    if (gram) plan.add<T>((size_t)s.K * s.K);             // G
-    if (!gram) plan.add<T>((size_t)s.N * s.F);            // f
-    if (s.lik == DCP_LIK_BETA) plan.add<T>((size_t)s.N * s.F);   // f2
-    if (need_ym) plan.add<T>((size_t)s.N * s.F);          // Ym
-    plan.add<T>(nmf_slab_elems(s));                       // slabs
-    plan.add<T>((size_t)s.K);                             // vecK
-    plan.add<T>((size_t)64 * (s.K > s.F ? s.K : s.F));    // part
-}
-
-template <class T>
-inline int nmf_carve_stats(dcp_handle* h, NmfStatsWs<T>& w, const NmfShape<T>& s, bool need_ym) {
-    const bool gram = (s.lik == DCP_LIK_L2 && !s.masked);
-    w.Q = ws_alloc<T>(h, (size_t)s.N * s.K);
-    if (gram) w.G = ws_alloc<T>(h, (size_t)s.K * s.K);
-    if (!gram) w.f = ws_alloc<T>(h, (size_t)s.N * s.F);
-    if (s.lik == DCP_LIK_BETA) w.f2 = ws_alloc<T>(h, (size_t)s.N * s.F);
-    if (need_ym) w.Ym = ws_alloc<T>(h, (size_t)s.N * s.F);
+    a.take(w.Q, (size_t)s.N * s.K);
+    if (gram) a.take(w.G, (size_t)s.K * s.K);
+    if (!gram) a.take(w.f, (size_t)s.N * s.F);
+    if (s.lik == DCP_LIK_BETA) a.take(w.f2, (size_t)s.N * s.F);
+    if (need_ym) a.take(w.Ym, (size_t)s.N * s.F);
     w.slab_count = nmf_slab_elems(s);
-    w.slabs = ws_alloc<T>(h, w.slab_count);
-    w.vecK = ws_alloc<T>(h, (size_t)s.K);
-    w.part = ws_alloc<T>(h, (size_t)64 * (s.K > s.F ? s.K : s.F));
-    if (!w.Q || !w.slabs || !w.vecK || !w.part || (gram && !w.G) || (!gram && !w.f) ||
-        (need_ym && !w.Ym) || (s.lik == DCP_LIK_BETA && !w.f2))
-        return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
-    return DCP_OK;
+    a.take(w.slabs, w.slab_count);
+    a.take(w.vecK, (size_t)s.K);
+    a.take(w.part, (size_t)64 * (s.K > s.F ? s.K : s.F));
 }
 
 template <class T>
@@ -165,25 +148,10 @@ struct NmfUpdateWs {
     T* rowmax = nullptr;   // [K]
 };
 template <class T>
-inline void nmf_plan_update(WsPlan& plan, int64_t F, int64_t K) {
-    plan.add<T>((size_t)K * F);
-    plan.add<T>((size_t)K);
+inline void nmf_update_layout(WsLayout& a, NmfUpdateWs<T>& w, int64_t F, int64_t K) {
+    a.take(w.U, (size_t)K * F);
+    a.take(w.rowmax, (size_t)K);
 }
-template <class T>
-inline int nmf_carve_update(dcp_handle* h, NmfUpdateWs<T>& w, int64_t F, int64_t K) {
-    w.U = ws_alloc<T>(h, (size_t)K * F);
-    w.rowmax = ws_alloc<T>(h, (size_t)K);
-    if (!w.U || !w.rowmax) return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
-    return DCP_OK;
-}
-
-#define DCP_LAUNCH_OK(h, what)                                                        \
-    do {                                                                              \
-        hipError_t _e = (what);                                                       \
-        if (_e != hipSuccess)                                                         \
-            return dcp::fail((h), DCP_ERR_HIP, std::string("launch failed: ") +       \
-                                                   hipGetErrorString(_e));            \
-    } while (0)
 
 // out[K] = column sums of a[rows, cols] (deterministic two-stage).
 template <class T>

@@ -15,8 +15,7 @@ struct NmfStopSlots {
 };
 
 // batch_mu.py:16-26 for a method given as a Step:
-//   void plan(WsPlan&)        adds the method's own workspace items
-//   int  carve(h)             carves them, in the order of plan()
+//   void layout(WsLayout&)    takes the method's own workspace items (run twice by ws_lay_out: sizing, then carving)
 //   int  prepare(h)           loop-invariant work on h->stream (may synchronise)
 //   int  iterate(h, Xc, Xn, Dc, Dn, slots)   enqueues one iteration from (Xc, Dc) into (Xn, Dn)
 // Iteration `it` reads (x_{it-1}, D_{it-1}) from (Xc, Dc) and writes (x_it, D_it) to (Xn, Dn); its max|dD| lands in
@@ -31,27 +30,23 @@ int nmf_lagged_loop(dcp_handle* h, Step& step, const T* Y, const T* mask, T* X, 
                     T tol, int maxiter, int* it_out, T* last_maxdiff, T* resid_trace) {
     const bool want_resid = resid_trace != nullptr;
     const int resid_blocks = 1024;
-    WsPlan plan;
-    step.plan(plan);
-    plan.add<T>((size_t)K * F);   // second D buffer
-    plan.add<T>((size_t)N * K);   // second x buffer
-    plan.add<T>(2);               // max|dD| of the two iterations in flight
-    plan.add<unsigned int>(4);    // arrival ticket of the normalisation's workgroups
-    if (want_resid) {
-        plan.add<T>((size_t)N * F);
-        plan.add<double>(resid_blocks);
-    }
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    DCP_TRY(step.carve(h));
-    T* D2 = ws_alloc<T>(h, (size_t)K * F);
-    T* X2 = ws_alloc<T>(h, (size_t)N * K);
-    T* maxdiff_dev = ws_alloc<T>(h, 2);
-    unsigned int* ticket = ws_alloc<unsigned int>(h, 4);
-    T* resid_tmp = want_resid ? ws_alloc<T>(h, (size_t)N * F) : nullptr;
-    double* resid_part = want_resid ? ws_alloc<double>(h, resid_blocks) : nullptr;
-    if (!D2 || !X2 || !maxdiff_dev || !ticket || (want_resid && (!resid_tmp || !resid_part)))
-        return fail(h, DCP_ERR_INTERNAL, "nmf workspace plan mismatch");
+    T* D2 = nullptr;                  // second D buffer
+    T* X2 = nullptr;                  // second x buffer
+    T* maxdiff_dev = nullptr;         // max|dD| of the two iterations in flight
+    unsigned int* ticket = nullptr;   // arrival ticket of the normalisation's workgroups
+    T* resid_tmp = nullptr;
+    double* resid_part = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        step.layout(a);
+        a.take(D2, (size_t)K * F);
+        a.take(X2, (size_t)N * K);
+        a.take(maxdiff_dev, 2);
+        a.take(ticket, 4);
+        if (want_resid) {
+            a.take(resid_tmp, (size_t)N * F);
+            a.take(resid_part, resid_blocks);
+        }
+    }));
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, sizeof(double) * (resid_blocks + 4), &hostv));
     T* host_md = reinterpret_cast<T*>(hostv);             // [2]

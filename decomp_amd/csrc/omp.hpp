@@ -341,35 +341,17 @@ inline int omp_greedy(dcp_handle* h, const T* alpha0, const T* G, const real_t<T
     return DCP_OK;
 }
 
-// ---- workspace: the fields of LassoWs the solve uses (the dictionary step carves them with the same plan) ----
+// ---- workspace: the fields of LassoWs the solve uses (the dictionary step lays them out with the same function) ----
 template <class T>
-inline void omp_plan(WsPlan& p, int64_t N, int64_t F, int64_t K) {
-    typedef real_t<T> R;
-    p.add<T>((size_t)N * K);                  // alpha0
-    p.add<T>((size_t)K * K);                  // G
-    p.add<T>((size_t)kMaxSplits * K * K);     // split-K partials of G
-    p.add<R>((size_t)K);                      // 1 / n_k
-    p.add<R>((size_t)N);                      // |y|^2
-    p.add<int>(4);
-    if (scalar_traits<T>::is_complex) p.add<R>((size_t)4 * K * F);
-}
-template <class T>
-inline int omp_carve(dcp_handle* h, LassoWs<T>& w, int64_t N, int64_t F, int64_t K) {
-    typedef real_t<T> R;
-    w.yAt = ws_alloc<T>(h, (size_t)N * K);
-    w.AAt = ws_alloc<T>(h, (size_t)K * K);
-    w.slab_count = (size_t)kMaxSplits * K * K;
-    w.slabs = ws_alloc<T>(h, w.slab_count);
-    w.s = ws_alloc<R>(h, (size_t)K);
-    w.rowscale = ws_alloc<R>(h, (size_t)N);
-    w.flag = ws_alloc<int>(h, 4);
-    if (scalar_traits<T>::is_complex) {
-        w.ext1 = ws_alloc<R>(h, (size_t)4 * K * F);
-        if (!w.ext1) return fail(h, DCP_ERR_INTERNAL, "omp workspace plan mismatch");
-    }
-    if (!w.yAt || !w.AAt || !w.slabs || !w.s || !w.rowscale || !w.flag)
-        return fail(h, DCP_ERR_INTERNAL, "omp workspace plan mismatch");
-    return DCP_OK;
+inline void omp_layout(WsLayout& a, LassoWs<T>& w, int64_t N, int64_t F, int64_t K) {
+    a.take(w.yAt, (size_t)N * K);                 // alpha0
+    a.take(w.AAt, (size_t)K * K);                 // G
+    w.slab_count = (size_t)kMaxSplits * K * K;    // split-K partials of G
+    a.take(w.slabs, w.slab_count);
+    a.take(w.s, (size_t)K);                       // 1 / n_k
+    a.take(w.rowscale, (size_t)N);                // |y|^2
+    a.take(w.flag, 4);
+    if (scalar_traits<T>::is_complex) a.take(w.ext1, (size_t)4 * K * F);
 }
 
 inline int omp_check_sparsity(dcp_handle* h, int64_t K, int n_nonzero, int cap) {
@@ -420,12 +402,8 @@ inline int omp_api(dcp_handle* h, const T* Y, const T* A, T* X, int64_t N, int64
     if (tol != tol) return fail(h, DCP_ERR_INVALID, "omp: tol is NaN");
     DCP_TRY(omp_check_sparsity(h, K, n_nonzero, omp_cap<T>()));
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    omp_plan<T>(plan, N, F, K);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
     LassoWs<T> w;
-    DCP_TRY(omp_carve<T>(h, w, N, F, K));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { omp_layout<T>(a, w, N, F, K); }));
     DCP_TRY(omp_solve<T>(h, Y, A, X, (int)N, (int)F, (int)K, n_nonzero, tol, w));
     return omp_read_it(h, w.flag, it_out);
 }
@@ -442,14 +420,12 @@ inline int omp_gram_api(dcp_handle* h, const T* alpha0, const T* G, const real_t
     if (tol >= 0.0 && !ynorm2) return fail(h, DCP_ERR_INVALID, "omp: ynorm2 is null but tol >= 0");
     DCP_TRY(omp_check_sparsity(h, K, n_nonzero, omp_cap<T>()));
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    WsPlan plan;
-    plan.add<R>((size_t)K);
-    plan.add<int>(4);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    R* invn = ws_alloc<R>(h, (size_t)K);
-    int* it_dev = ws_alloc<int>(h, 4);
-    if (!invn || !it_dev) return fail(h, DCP_ERR_INTERNAL, "omp workspace plan mismatch");
+    R* invn = nullptr;
+    int* it_dev = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        a.take(invn, (size_t)K);
+        a.take(it_dev, 4);
+    }));
     DCP_TRY(omp_greedy<T>(h, alpha0, G, ynorm2, X, (int)N, (int)K, n_nonzero, tol, invn, it_dev));
     return omp_read_it(h, it_dev, it_out);
 }

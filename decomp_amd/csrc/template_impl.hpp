@@ -566,29 +566,26 @@ inline int tm_lasso_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmG
     typedef real_t<T> R;
     hipStream_t st = h->stream;
     const long TC = g.T * g.C, BX = g.B * TC;
-    WsPlan plan;
-    for (int q = 0; q < 5; ++q) plan.add<R>(TC);          // rho, rinv, alphak, tolk, colsum
-    plan.add<R>(g.T);                                     // Toeplitz column sums
-    plan.add<T>(g.T * g.T * (2 * g.S - 1));              // lag correlations
-    plan.add<R>(4);
-    plan.add<int>(4);
-    plan.add<T>(g.B * g.N);                               // residual
-    for (int q = 0; q < 4; ++q) plan.add<T>(BX);          // iterates
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    R* rho = ws_alloc<R>(h, TC);
-    R* rinv = ws_alloc<R>(h, TC);
-    R* alphak = ws_alloc<R>(h, TC);
-    R* tolk = ws_alloc<R>(h, TC);
-    R* colsum = ws_alloc<R>(h, TC);
-    R* tsum = ws_alloc<R>(h, g.T);
-    T* corr = ws_alloc<T>(h, g.T * g.T * (2 * g.S - 1));
-    R* scal = ws_alloc<R>(h, 4);
-    int* flag = ws_alloc<int>(h, 4);
-    T* r = ws_alloc<T>(h, g.B * g.N);
-    T* xb[4];
-    for (int q = 0; q < 4; ++q) xb[q] = ws_alloc<T>(h, BX);
-    if (!xb[3]) return fail(h, DCP_ERR_INTERNAL, "template lasso workspace");
+    R *rho = nullptr, *rinv = nullptr, *alphak = nullptr, *tolk = nullptr, *colsum = nullptr;
+    R* tsum = nullptr;   // Toeplitz column sums
+    T* corr = nullptr;   // lag correlations
+    R* scal = nullptr;
+    int* flag = nullptr;
+    T* r = nullptr;      // residual
+    T* xb[4] = {nullptr, nullptr, nullptr, nullptr};   // iterates
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        a.take(rho, TC);
+        a.take(rinv, TC);
+        a.take(alphak, TC);
+        a.take(tolk, TC);
+        a.take(colsum, TC);
+        a.take(tsum, g.T);
+        a.take(corr, g.T * g.T * (2 * g.S - 1));
+        a.take(scal, 4);
+        a.take(flag, 4);
+        a.take(r, g.B * g.N);
+        for (int q = 0; q < 4; ++q) a.take(xb[q], BX);
+    }));
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, 64, &hostv));
     int* host_flag = reinterpret_cast<int*>(hostv);
@@ -720,30 +717,20 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
     typedef real_t<T> R;
     hipStream_t st = h->stream;
     const long nd = g.nd(), TS = g.T * g.S, hmax = tm_hmax(g);
-    WsPlan plan;
-    plan.add<T>(g.B * g.T * g.T * nd);
-    plan.add<T>(g.T * g.T * nd * hmax);
-    plan.add<T>(g.T * g.T * nd * hmax);
-    plan.add<T>(g.B * TS);
-    plan.add<R>(TS);
-    plan.add<T>(TS);
-    plan.add<T>(TS);
-    plan.add<T>(TS);
-    plan.add<R>(g.T);
-    plan.add<R>(4);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    T* mpart = ws_alloc<T>(h, g.B * g.T * g.T * nd);
-    T* eh = ws_alloc<T>(h, g.T * g.T * nd * hmax);
-    T* et = ws_alloc<T>(h, g.T * g.T * nd * hmax);
-    T* yxpart = ws_alloc<T>(h, g.B * TS);
-    R* colabs = ws_alloc<R>(h, TS);
-    T* step = ws_alloc<T>(h, TS);
-    T* U = ws_alloc<T>(h, TS);
-    T* Dn = ws_alloc<T>(h, TS);
-    R* rowmax = ws_alloc<R>(h, g.T);
-    R* scal = ws_alloc<R>(h, 4);
-    if (!scal) return fail(h, DCP_ERR_INTERNAL, "template dstep workspace");
+    T *mpart = nullptr, *eh = nullptr, *et = nullptr, *yxpart = nullptr, *step = nullptr, *U = nullptr, *Dn = nullptr;
+    R *colabs = nullptr, *rowmax = nullptr, *scal = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+        a.take(mpart, g.B * g.T * g.T * nd);
+        a.take(eh, g.T * g.T * nd * hmax);
+        a.take(et, g.T * g.T * nd * hmax);
+        a.take(yxpart, g.B * TS);
+        a.take(colabs, TS);
+        a.take(step, TS);
+        a.take(U, TS);
+        a.take(Dn, TS);
+        a.take(rowmax, g.T);
+        a.take(scal, 4);
+    }));
     {
         ProfScope ps(h, DCP_PROF_STATS);
         hipLaunchKernelGGL((tm_stats_core_kernel<T>), dim3(g.T, g.T, g.B), dim3(256), 0, st, X, g, mpart);

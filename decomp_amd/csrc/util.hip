@@ -35,12 +35,8 @@ int count_negative_api(dcp_handle* h, const T* x, int64_t n, int64_t* count) {
     if (n == 0) return DCP_OK;
     DCP_HIP_OK(h, hipSetDevice(h->device));
     const int blocks = grid_for(n, 1024);
-    WsPlan plan;
-    plan.add<unsigned long long>(blocks);
-    DCP_TRY(ws_reserve(h, plan.total));
-    ws_reset(h);
-    unsigned long long* part = ws_alloc<unsigned long long>(h, blocks);
-    if (!part) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+    unsigned long long* part = nullptr;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { a.take(part, blocks); }));
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, sizeof(unsigned long long) * blocks, &hostv));
     hipLaunchKernelGGL((count_negative_kernel<T>), dim3(blocks), dim3(256), 0, h->stream, x,
@@ -208,14 +204,11 @@ int gemm_api(dcp_handle* h, int form, const T* A, const T* B, T* C, int64_t M, i
         a.ksplits = (int)((K + a.klen - 1) / a.klen);
         // slabs for the larger of the two plans (complex products may re-plan over the real-extended 2K below)
         const size_t max_slabs = (size_t)(ksplits > a.ksplits ? ksplits : a.ksplits) + 1;
-        WsPlan plan;
-        plan.add<T>(max_slabs * M * N);
-        plan.add<RT>(ext_floats + 4);
-        DCP_TRY(ws_reserve(h, plan.total));
-        ws_reset(h);
-        T* slabs = ws_alloc<T>(h, max_slabs * M * N);
-        ext = ws_alloc<RT>(h, ext_floats + 4);
-        if (!slabs || !ext) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+        T* slabs = nullptr;
+        DCP_TRY(ws_lay_out(h, [&](WsLayout& w) {
+            w.take(slabs, max_slabs * M * N);
+            w.take(ext, ext_floats + 4);
+        }));
         if (ext_floats) {
             a.ext_ws = ext;
             bool planar = form == FORM_NN && cplx_planar_a<FORM_NN>(a.M, a.N, a.conjA, a.conjB, a.ext_ws);
@@ -238,12 +231,7 @@ int gemm_api(dcp_handle* h, int form, const T* A, const T* B, T* C, int64_t M, i
         DCP_HIP_OK(h, hipGetLastError());
     } else {
         if (ext_floats) {
-            WsPlan plan;
-            plan.add<RT>(ext_floats + 4);
-            DCP_TRY(ws_reserve(h, plan.total));
-            ws_reset(h);
-            ext = ws_alloc<RT>(h, ext_floats + 4);
-            if (!ext) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+            DCP_TRY(ws_lay_out(h, [&](WsLayout& w) { w.take(ext, ext_floats + 4); }));
             a.ext_ws = ext;
         }
         EpiStore<T> epi{C, (long)N};
@@ -471,8 +459,8 @@ int dcp_set_stream(dcp_handle* h, void* hip_stream) {
     if (!h) return DCP_ERR_INVALID;
     // Only the handle's current stream changes here.  Ordering of the shared workspace arena between
     // the old and the new stream is established lazily by the next call that actually uses the arena
-    // (ws_reserve -> ws_order_streams); calls that use none (dcp_gather_rows_bytes / dcp_scatter_rows_bytes
-    // on a copy stream) therefore overlap freely with compute enqueued on the other stream.
+    // (ws_lay_out -> ws_reserve -> ws_order_streams); calls that use none (dcp_gather_rows_bytes /
+    // dcp_scatter_rows_bytes on a copy stream) therefore overlap freely with compute enqueued on the other stream.
     h->stream = reinterpret_cast<hipStream_t>(hip_stream);
     return DCP_OK;
 }
@@ -580,12 +568,7 @@ int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B,
         a.klen = (int)(((kblocks + s - 1) / s) * 16);
         a.ksplits = (int)((K + a.klen - 1) / a.klen);
         a.split_planned = true;
-        WsPlan plan;
-        plan.add<float>((size_t)a.ksplits * M * N);
-        DCP_TRY(ws_reserve(h, plan.total));
-        ws_reset(h);
-        slabs = ws_alloc<float>(h, (size_t)a.ksplits * M * N);
-        if (!slabs) return fail(h, DCP_ERR_INTERNAL, "workspace plan mismatch");
+        DCP_TRY(ws_lay_out(h, [&](WsLayout& w) { w.take(slabs, (size_t)a.ksplits * M * N); }));
     }
     const bool ok = (form == FORM_NT) ? x6_tier<FORM_NT>(a) != X6_NONE : x6_tier<FORM_TN>(a) != X6_NONE;
     if (!ok) return fail(h, DCP_ERR_INVALID, "bf16x6: no split-bf16 kernel for this shape (tiles, alignment)");
