@@ -10,7 +10,7 @@ Drop-in for the reference's ``decomp.nmf.solve`` / ``decomp.lasso.solve`` /
 All arithmetic runs in hand-written HIP kernels (libdecomp_hip.so, gfx950) behind a
 plain C ABI (include/decomp_hip.h); there is no CPU fallback.
 """
-from . import nmf, lasso, nnls, omp, dictionary_learning, template_matching  # noqa: F401
+from . import nmf, lasso, nnls, omp, ksvd, dictionary_learning, template_matching  # noqa: F401
 from . import utils, math_utils, nmf_methods  # noqa: F401
 from .utils import exceptions  # noqa: F401
 

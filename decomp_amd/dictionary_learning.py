@@ -51,7 +51,14 @@ def solve(y, D, alpha, x=None, tol=1.0e-3,
     <= 64 real, <= 32 complex), ``lasso_tol`` the residual tolerance |y - xD|^2 <= lasso_tol (None: none), ``x``
     is not read.  ``alpha`` must be 0 (there is no penalty to apply: ValueError otherwise); ``mask`` is not
     supported (NotImplementedError).
+
+    ``method='ksvd'`` (not in the reference) is approximate K-SVD, the batch trainer for codes of a given sparsity
+    (decomp_amd.ksvd.solve, to which it forwards): it takes ``minibatch=None`` and ``lasso_method='omp'`` only
+    (NotImplementedError otherwise: online K-SVD is not built), with ``lasso_iter`` the sparsity, ``lasso_tol`` the
+    coder's residual tolerance, ``alpha`` 0 and no ``mask`` as for 'omp'; ``x`` and ``random_seed`` are not read.
     """
+    if method == 'ksvd':
+        return _solve_ksvd(y, D, alpha, tol, minibatch, maxiter, lasso_method, lasso_iter, lasso_tol, mask)
     import torch
     kind = get_array_module(D)
     x_given = x
@@ -119,6 +126,19 @@ def solve(y, D, alpha, x=None, tol=1.0e-3,
         it, Dout, xout = solve_cd_mask(ybat, Dd, alpha, xbat, tol, minibatch, maxiter,
                                        lasso_method, lasso_iter, lasso_tol, rng, kind, mbat)
     return it, _arrays.to_caller(Dout, kind), _arrays.to_caller(xout, kind)
+
+
+def _solve_ksvd(y, D, alpha, tol, minibatch, maxiter, lasso_method, lasso_iter, lasso_tol, mask):
+    """method='ksvd': the scope checks, then decomp_amd.ksvd.solve."""
+    from . import ksvd
+    if minibatch is not None:
+        raise NotImplementedError("method='ksvd' is a batch method: online (minibatch) K-SVD is not implemented. "
+                                  'minibatch must be None.')
+    if lasso_method != 'omp':
+        raise NotImplementedError("method='ksvd' codes by orthogonal matching pursuit: lasso_method must be 'omp'. "
+                                  'Given %s' % (lasso_method,))
+    s, _ = _check_omp(D, alpha, lasso_iter, lasso_tol, mask)
+    return ksvd.solve(y, D, s, tol=tol, maxiter=maxiter, coef_tol=lasso_tol)
 
 
 def _check_omp(D, alpha, lasso_iter, lasso_tol, mask):

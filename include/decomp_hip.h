@@ -544,6 +544,36 @@ int dcp_omp_gram_c64(dcp_handle* h, const void* alpha0, const void* G, const flo
 int dcp_omp_gram_c128(dcp_handle* h, const void* alpha0, const void* G, const double* ynorm2, void* X,
                       int64_t N, int64_t K, int n_nonzero, double tol, int* it_out);
 
+/* ---- approximate K-SVD (not in the reference; csrc/ksvd.hpp) ---------------------------------- */
+/* min |Y - X D|^2  s.t.  |x_i|_0 <= s, |d_k| = 1  for Y[N,F], X[N,K], D[K,F] (Rubinstein, Zibulevsky & Elad 2008).
+ * The atom sweep, on R = Y - X D formed once on the GEMM cores: for k = 0 .. K-1 in order, with I the rows where
+ * X[i,k] != 0 (ascending, fixed for the sweep), g = X[I,k], d = D[k]:  u = g^H R[I,:] + |g|^2 d;  d' = u / |u| (d is
+ * kept where !(|u| > 0));  g' = R[I,:] d'^H + g (d . d'^H);  R[I,:] += g d - g' d';  X[I,k] = g';  D[k] = d'.  An atom
+ * no row uses is left as it is.  The sweep never increases |Y - X D|^2.  *maxdiff_out (host) = max |D_new - D_old|
+ * over all entries.  Bitwise reproducible.  Both families synchronise the stream before returning.
+ *   dcp_ksvd_sweep_* : the residual and the sweep on the caller's X and D, both updated in place.  row_nnz_max in
+ *                      [1, K] bounds the non-zeros of a row of X (it sizes the lists): a row with more gives
+ *                      DCP_ERR_INVALID before X or D is written.
+ *   dcp_ksvd_step_*  : X = dcp_omp_*(Y, D, n_nonzero, coef_tol) (X is written in full; the limits on n_nonzero and
+ *                      coef_tol are those of dcp_omp_*; *it_out = its step count), then the residual and the sweep.
+ *                      D should have unit rows on entry. */
+int dcp_ksvd_sweep_f32(dcp_handle* h, const float* Y, float* X, float* D, int64_t N, int64_t F, int64_t K,
+                       int row_nnz_max, double* maxdiff_out);
+int dcp_ksvd_sweep_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
+                       int row_nnz_max, double* maxdiff_out);
+int dcp_ksvd_sweep_c64(dcp_handle* h, const void* Y, void* X, void* D, int64_t N, int64_t F, int64_t K,
+                       int row_nnz_max, double* maxdiff_out);
+int dcp_ksvd_sweep_c128(dcp_handle* h, const void* Y, void* X, void* D, int64_t N, int64_t F, int64_t K,
+                        int row_nnz_max, double* maxdiff_out);
+int dcp_ksvd_step_f32(dcp_handle* h, const float* Y, float* X, float* D, int64_t N, int64_t F, int64_t K,
+                      int n_nonzero, double coef_tol, double* maxdiff_out, int* it_out);
+int dcp_ksvd_step_f64(dcp_handle* h, const double* Y, double* X, double* D, int64_t N, int64_t F, int64_t K,
+                      int n_nonzero, double coef_tol, double* maxdiff_out, int* it_out);
+int dcp_ksvd_step_c64(dcp_handle* h, const void* Y, void* X, void* D, int64_t N, int64_t F, int64_t K,
+                      int n_nonzero, double coef_tol, double* maxdiff_out, int* it_out);
+int dcp_ksvd_step_c128(dcp_handle* h, const void* Y, void* X, void* D, int64_t N, int64_t F, int64_t K,
+                       int n_nonzero, double coef_tol, double* maxdiff_out, int* it_out);
+
 /* ---- row movers of the minibatch containers (decomp/utils/data.py:124-156, 214-313) ------ */
 /* gather : out[i, :] = in[index[i], :]      scatter: out[index[i], :] = in[i, :]      i < rows
  * Rows are row_bytes long (any dtype); index: int64 in DEVICE memory.  `in` / `out` may be
