@@ -236,8 +236,7 @@ inline int atom_sweep_fused_f32(dcp_handle* h, const float* A, const float* B, f
         plan_splits<FORM_NT>(g, 64, 64, 4);
         if ((size_t)g.ksplits * 64 * 64 > w.slab_count) return fail(h, DCP_ERR_INTERNAL, "atom slab plan");
         DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, g, EpiSlab<float>{w.slabs, 64L, 64L * 64})));
-        hipLaunchKernelGGL((reduce_slabs_kernel<float>), dim3(16), dim3(256), 0, st, (const float*)w.slabs,
-                           64L * 64, g.ksplits, 64L * 64, w.G);
+        launch_reduce_slabs_scalar<float>(st, (const float*)w.slabs, 64L * 64, g.ksplits, 64L * 64, w.G, 16);
         DCP_LAUNCH_OK(h, hipGetLastError());
     }
     for (int b = 0; b < nblk; ++b) {

@@ -138,29 +138,6 @@ struct EpiAddTo {
     }
 };
 
-// Sum of one double per lane over the 64 lanes of a wave, with DPP row shifts / row broadcasts
-// (VALU latency) instead of the LDS crossbar of __shfl_xor (six dependent ds_bpermute pairs are
-// the longest chain of a recursion step otherwise).  Invalid / masked-out source lanes contribute
-// +0.0 (bound_ctrl, old = 0).  The total lands in lane 63 and is read back as a wave-uniform value.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_add_f64(double x) {
-    const int lo = __double2loint(x), hi = __double2hiint(x);
-    const int slo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, true);
-    const int shi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, true);
-    return x + __hiloint2double(shi, slo);
-}
-__device__ __forceinline__ double wave_sum_f64(double x) {
-    x = dpp_add_f64<0x111, 0xf>(x);   // row_shr:1
-    x = dpp_add_f64<0x112, 0xf>(x);   // row_shr:2
-    x = dpp_add_f64<0x114, 0xf>(x);   // row_shr:4
-    x = dpp_add_f64<0x118, 0xf>(x);   // row_shr:8   -> lane 15 of every row holds its row sum
-    x = dpp_add_f64<0x142, 0xa>(x);   // row_bcast:15 into rows 1 and 3
-    x = dpp_add_f64<0x143, 0xc>(x);   // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), 63);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), 63);
-    return __hiloint2double(hi, lo);
-}
-
 // Step (3): the b dependent steps in coefficient space.  Lane i owns coefficient i.  Besides the rows
 // E_j the kernel keeps
 //     M_j = G E_j^H                                    (lane i holds (G E_j^H)[i])
@@ -435,8 +412,7 @@ inline int atom_sweep(dcp_handle* h, const T* A, const T* B, T* Dnew, int64_t F6
             plan_splits<FORM_NT>(g, 64, 64, 4);
             if ((size_t)g.ksplits * nb * nb > w.slab_count) return fail(h, DCP_ERR_INTERNAL, "atom slab plan");
             DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, g, EpiSlab<T>{w.slabs, (long)nb, (long)nb * nb})));
-            hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)nb * nb, 16)), dim3(256), 0, st,
-                               w.slabs, (long)nb * nb, g.ksplits, (long)nb * nb, w.G);
+            launch_reduce_slabs_scalar<T>(st, w.slabs, (long)nb * nb, g.ksplits, (long)nb * nb, w.G, 16);
             DCP_LAUNCH_OK(h, hipGetLastError());
         }
         if (has_next && lookahead) {

@@ -208,12 +208,7 @@ inline int dict_step_api(dcp_handle* h, const T* Y, T* X, const T* D, T* Dnew, T
     R* md = nullptr;
     DCP_TRY(dict_step_core<T>(h, Y, X, D, Dnew, A, B, Nb, F, K, beta, alpha, lasso_method, lasso_iter, lasso_tol,
                               (R*)nullptr, lasso_it, &md));
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, 64, &hostv));
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, md, sizeof(R), hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    *maxdiff_host = (double)(*reinterpret_cast<R*>(hostv));
-    return DCP_OK;
+    return read_scalar(h, md, maxdiff_host);
 }
 
 // The same step without the host read-back (dictionary_learning.py:161-162 is then evaluated by the caller one
@@ -270,8 +265,7 @@ inline int dict_mask_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, T* 
         plan_splits<FORM_TN>(a, kSplitTarget, kMaxSplits);
         if ((size_t)a.ksplits * K * F > dw.slab_count) return fail(h, DCP_ERR_INTERNAL, "dict slab plan");
         DCP_LAUNCH_OK(h, (gemm<FORM_TN>(st, a, EpiSlab<T>{dw.slabs, (long)F, (long)K * F})));
-        hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)K * F)), dim3(256), 0, st,
-                           dw.slabs, (long)K * F, a.ksplits, (long)K * F, sB);
+        launch_reduce_slabs_scalar<T>(st, dw.slabs, (long)K * F, a.ksplits, (long)K * F, sB);
         DCP_LAUNCH_OK(h, hipGetLastError());
         hipLaunchKernelGGL((scale_add_kernel<T>), dim3(grid_for((long)K * F)), dim3(256), 0, st,
                            (long)K * F, (R)beta, (const T*)sB, B);
@@ -281,18 +275,12 @@ inline int dict_mask_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, T* 
                        (const T*)B, D, (long)F, (int)K, Dnew);
     DCP_LAUNCH_OK(h, hipGetLastError());
     const int mb = grid_for((long)K * F, 256);
-    hipLaunchKernelGGL((maxabsdiff_partial_kernel<T>), dim3(mb), dim3(256), 0, st, D, (const T*)Dnew,
-                       (long)K * F, dw.partial);
+    hipLaunchKernelGGL((reduce_partial_kernel<MaxOp, MapAbsDiff<T>, R>), dim3(mb), dim3(256), 0, st,
+                       MapAbsDiff<T>{D, Dnew}, (long)K * F, dw.partial);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((final_max_kernel<R>), dim3(1), dim3(256), 0, st, (const R*)dw.partial, (long)mb,
-                       dw.scal);
+    launch_final_max<R>(st, dw.partial, (long)mb, dw.scal);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, 64, &hostv));
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, dw.scal, sizeof(R), hipMemcpyDeviceToHost, st));
-    DCP_HIP_OK(h, hipStreamSynchronize(st));
-    *maxdiff_host = (double)(*reinterpret_cast<R*>(hostv));
-    return DCP_OK;
+    return read_scalar(h, (const R*)dw.scal, maxdiff_host);
 }
 
 template <class T>

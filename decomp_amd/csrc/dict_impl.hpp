@@ -58,16 +58,7 @@ __global__ void __launch_bounds__(256) dict_accumulate_slabs_kernel(const T* __r
     if (Dsrc != nullptr)
         for (long i = blockIdx.x * 256L + threadIdx.x; i < K * F; i += (long)gridDim.x * 256L) Ddst[i] = Dsrc[i];
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
-        T v = slabs[i];
-        int s = 1;
-        for (; s + 7 < S; s += 8) {
-            T u[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) u[q] = slabs[(long)(s + q) * stride + i];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v = add(v, u[q]);
-        }
-        for (; s < S; ++s) v = add(v, slabs[(long)s * stride + i]);
+        const T v = slab_sum<8>(slabs, stride, S, i);
         const long r = i / W, c = i - r * W;
         if (c < F) B[r * F + c] = add(scale(B[r * F + c], beta), v);
         else A[r * K + (c - F)] = add(scale(A[r * K + (c - F)], beta), v);
@@ -85,25 +76,9 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const T* __restrict__ 
     }
 }
 
-// max_i |a_i - b_i| -> partial[block]  (then final_max_kernel)
-template <class T>
-__global__ void __launch_bounds__(256) maxabsdiff_partial_kernel(const T* __restrict__ a, const T* __restrict__ b,
-                                                                 long n, real_t<T>* __restrict__ partial) {
-    typedef real_t<T> R;
-    __shared__ R sh[4];
-    R m = 0;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
-        const R d = absval(sub(a[i], b[i]));
-        m = (d > m || d != d) ? d : m;
-    }
-    R r = block_max_256(m, sh);
-    if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-
-// max_i |a_i - b_i| -> *out in ONE launch: a returning atomic max per workgroup (|.| >= 0: the bit pattern is monotone,
-// a NaN wins as in np.max), then an arrival ticket whose increment depends on the returned value; the workgroup that
-// arrives last stores the finished maximum (`out` may be device-mapped pinned host memory the caller polls).
-// scratch[0] (gmax) and the ticket behind it must be zero on entry: the step's accumulate kernel clears them.
+// max_i |a_i - b_i| -> *out in ONE launch (publish_max; `out` may be device-mapped pinned host memory the caller polls).
+// scratch[0] (gmax) and the ticket behind it must be zero on entry: the step's accumulate kernel clears them, so the
+// ticket is not reset here.
 // (Few, large workgroups: the two atomics of every workgroup arrive in one burst at the end and same-address atomics
 // serialise at the memory side -- 512 workgroups of 256 threads spent 20 us here, 13 of them queueing.)
 template <class T>
@@ -123,24 +98,12 @@ __global__ void __launch_bounds__(1024) maxabsdiff_publish_kernel(const T* __res
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const R d = absval(sub(va[u], vb[u]));
-            m = (d > m || d != d) ? d : m;
+            m = max_np(d, m);
         }
     }
-    for (; i < n; i += stride) {
-        const R d = absval(sub(a[i], b[i]));
-        m = (d > m || d != d) ? d : m;
-    }
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        R r = sh[0];
-        for (int w = 1; w < 16; ++w) r = (sh[w] > r || sh[w] != sh[w]) ? sh[w] : r;
-        unsigned int inc = 1u;
-        R old = atomic_max_nonneg_ret(gmax, r);
-        asm volatile("; the arrival is counted behind the max" : "+v"(inc) : "v"(old));
-        if (atomicAdd(ticket, inc) == gridDim.x - 1u) *out = atomic_read_nonneg(gmax);
-    }
+    for (; i < n; i += stride) m = max_np(absval(sub(a[i], b[i])), m);
+    const R r = block_max_256<16>(m, sh);
+    if (threadIdx.x == 0) publish_max(r, gmax, ticket, out, false);
 }
 
 // ---- masked dictionary learning (dictionary_learning.py:171-231) ----------------------------
@@ -180,7 +143,7 @@ __global__ void __launch_bounds__(256) dict_mask_atom_kernel(const T* __restrict
                                                              const T* __restrict__ D, long F, int K,
                                                              T* __restrict__ Dnew) {
     typedef real_t<T> R;
-    __shared__ R sh_re[4], sh_im[4];
+    __shared__ R sh[4];
     __shared__ T s_akk;
     __shared__ R s_nrm;
     const int k = blockIdx.x;
@@ -188,15 +151,10 @@ __global__ void __launch_bounds__(256) dict_mask_atom_kernel(const T* __restrict
     for (long f = threadIdx.x; f < F; f += 256) {
         const T v = add(A3[((long)k * F + f) * K + k], from_real<T>(R(1.0e-15)));
         are += real_part(v);
-        if constexpr (scalar_traits<T>::is_complex) aim += v.im;
+        aim += imag_part(v);
     }
-    const R tre = block_sum_256(are, sh_re);
-    R tim = 0;
-    if constexpr (scalar_traits<T>::is_complex) tim = block_sum_256(aim, sh_im);
-    if (threadIdx.x == 0) {
-        if constexpr (scalar_traits<T>::is_complex) { s_akk.re = tre; s_akk.im = tim; }
-        else s_akk = tre;
-    }
+    const T asum = block_sum_256_parts<T>(are, aim, sh);
+    if (threadIdx.x == 0) s_akk = asum;
     __syncthreads();
     const T akk = s_akk;
     R part = 0;
@@ -208,7 +166,7 @@ __global__ void __launch_bounds__(256) dict_mask_atom_kernel(const T* __restrict
         Dnew[(long)k * F + f] = u;
         part += abs2(u);
     }
-    const R tot = block_sum_256(part, sh_re);
+    const R tot = block_sum_256(part, sh);
     if (threadIdx.x == 0) s_nrm = sqrt(tot > R(1) ? tot : R(1));
     __syncthreads();
     const R nrm = s_nrm;

@@ -22,7 +22,7 @@ __global__ void __launch_bounds__(256) gershgorin_batched_kernel(const T* __rest
     for (long j = threadIdx.x; j < n; j += 256) {
         R acc = 0;
         for (long i = 0; i < n; ++i) acc += absval(a[i * n + j]);
-        best = (acc > best || acc != acc) ? acc : best;
+        best = max_np(acc, best);
     }
     const R m = block_max_256(best, sh);
     if (threadIdx.x == 0) out[blockIdx.x] = m;
@@ -77,15 +77,9 @@ int normalize_diff_api(dcp_handle* h, const T* U, const T* ref, T* out, int64_t 
                        (long)F, strict, ref, (long)F, out, (long)F, rowmax, (T*)nullptr, (T*)nullptr,
                        (T*)nullptr);
     DCP_HIP_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((final_max_kernel<T>), dim3(1), dim3(256), 0, h->stream, (const T*)rowmax, (long)K,
-                       md);
+    launch_final_max<T>(h->stream, rowmax, (long)K, md);
     DCP_HIP_OK(h, hipGetLastError());
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, 64, &hostv));
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, md, sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    *maxdiff = (double)(*reinterpret_cast<T*>(hostv));
-    return DCP_OK;
+    return read_scalar(h, md, maxdiff);
 }
 
 // ---- batched inverse (math_utils/linalg.py:9-38) ---------------------------------------------------------

@@ -10,6 +10,7 @@
 #include "gemm_mfma_bf16x6.hpp"
 #include "gemm_mfma_f32.hpp"
 #include "gemm_mfma_f64.hpp"
+#include "reduce.hpp"
 #include "scalar.hpp"
 
 namespace dcp {
@@ -802,9 +803,11 @@ struct EpiMuDen {
 
 // Split-K numerator: out = cur * max(sum_s slab_s, 0) / max(acc, 1e-15).  acc is the NEGATIVE part (x.G);
 // the positive part (Y.D^T) arrives as S ordered split-K partials, summed here in the fixed order
-// 0..S-1 (as mu_quotient_slabs_kernel does).  With few rows per GPU the Y.D^T product splits its
+// 0..S-1 (slab_sum, as mu_quotient_slabs_kernel does).  With few rows per GPU the Y.D^T product splits its
 // reduction; the quotient then rides on the x.G product (16-byte epilogue) instead of a pass of its own.
-template <class T>
+// PEN: the L1/L2 penalty on the codes, out = cur * max(sum slabs, 0) / max(acc + l1 + l2 cur, 1e-15); without it
+// l1 and l2 are not read.
+template <class T, bool PEN>
 struct EpiMuDenSlabs {
     static constexpr bool kVec4 = std::is_same<T, float>::value;
     const T* cur;
@@ -815,11 +818,12 @@ struct EpiMuDenSlabs {
     int S;
     T* out;
     long ld_out;
+    T l1 = T(0), l2 = T(0);
     __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const long o = (long)r * ld_slab + c;
-        T nu = slabs[o];
-        for (int s = 1; s < S; ++s) nu = nu + slabs[(long)s * slab_stride + o];
-        out[(long)r * ld_out + c] = cur[(long)r * ld_cur + c] * max_np(nu, T(0)) / max_np(v, T(1.0e-15));
+        const T nu = slab_sum(slabs, slab_stride, S, (long)r * ld_slab + c);
+        const T x = cur[(long)r * ld_cur + c];
+        if constexpr (PEN) v = v + l1 + l2 * x;
+        out[(long)r * ld_out + c] = x * max_np(nu, T(0)) / max_np(v, T(1.0e-15));
     }
     bool vec_ok() const {
         return al16_ptr(cur) && al16_ptr(slabs) && al16_ptr(out) && (ld_cur % 4) == 0 && (ld_slab % 4) == 0 &&
@@ -827,47 +831,16 @@ struct EpiMuDenSlabs {
     }
     __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
         if constexpr (std::is_same<T, float>::value) {
-            const long o = (long)r * ld_slab + c0;
-            f32x4 nu = *reinterpret_cast<const f32x4*>(slabs + o);
-            for (int s = 1; s < S; ++s) {
-                const f32x4 p = *reinterpret_cast<const f32x4*>(slabs + (long)s * slab_stride + o);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) nu[e] = nu[e] + p[e];
-            }
+            const f32x4 nu = slab_sum(reinterpret_cast<const f32x4*>(slabs + (long)r * ld_slab + c0), slab_stride / 4, S, 0L);
             const f32x4 x = *reinterpret_cast<const f32x4*>(cur + (long)r * ld_cur + c0);
             f32x4 q;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) q[e] = x[e] * max_np(nu[e], 0.0f) / max_np(v[e], 1.0e-15f);
-            *reinterpret_cast<f32x4*>(out + (long)r * ld_out + c0) = q;
-        }
-    }
-};
-
-// EpiMuDenSlabs with the L1/L2 penalty on the codes: out = cur * max(sum slabs, 0) / max(acc + l1 + l2 cur, 1e-15).
-template <class T>
-struct EpiMuDenSlabsPen : EpiMuDenSlabs<T> {
-    T l1, l2;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const long o = (long)r * this->ld_slab + c;
-        T nu = this->slabs[o];
-        for (int s = 1; s < this->S; ++s) nu = nu + this->slabs[(long)s * this->slab_stride + o];
-        const T x = this->cur[(long)r * this->ld_cur + c];
-        this->out[(long)r * this->ld_out + c] = x * max_np(nu, T(0)) / max_np(v + l1 + l2 * x, T(1.0e-15));
-    }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        if constexpr (std::is_same<T, float>::value) {
-            const long o = (long)r * this->ld_slab + c0;
-            f32x4 nu = *reinterpret_cast<const f32x4*>(this->slabs + o);
-            for (int s = 1; s < this->S; ++s) {
-                const f32x4 p = *reinterpret_cast<const f32x4*>(this->slabs + (long)s * this->slab_stride + o);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) nu[e] = nu[e] + p[e];
+            for (int e = 0; e < 4; ++e) {
+                float d = v[e];
+                if constexpr (PEN) d = d + l1 + l2 * x[e];
+                q[e] = x[e] * max_np(nu[e], 0.0f) / max_np(d, 1.0e-15f);
             }
-            const f32x4 x = *reinterpret_cast<const f32x4*>(this->cur + (long)r * this->ld_cur + c0);
-            f32x4 q;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) q[e] = x[e] * max_np(nu[e], 0.0f) / max_np(v[e] + l1 + l2 * x[e], 1.0e-15f);
-            *reinterpret_cast<f32x4*>(this->out + (long)r * this->ld_out + c0) = q;
+            *reinterpret_cast<f32x4*>(out + (long)r * ld_out + c0) = q;
         }
     }
 };
@@ -1073,7 +1046,7 @@ __device__ __forceinline__ double beta_divergence_elem(double beta, double y, do
     return (pow(y, beta) + (beta - 1.0) * pow(v, beta) - beta * y * pow(v, beta - 1.0)) / (beta * (beta - 1.0));
 }
 
-// out = M o d_beta(Y | acc + 1e-15), an entry with M == 0 contributing exactly 0 (reduced by sum_partial_kernel)
+// out = M o d_beta(Y | acc + 1e-15), an entry with M == 0 contributing exactly 0 (reduced by reduce_partial_kernel: SumOp over MapValue)
 template <class T>
 struct EpiBetaDivergence {
     const T* y;
@@ -1091,7 +1064,7 @@ struct EpiBetaDivergence {
     }
 };
 
-// Residual: out = (y - acc) [* mask]   (parity metric; reduced by sumsq_partial_kernel)
+// Residual: out = (y - acc) [* mask]   (parity metric; reduced by reduce_partial_kernel: SumOp over MapAbs2)
 template <class T>
 struct EpiResidual {
     const T* y;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/decomp_hip.h"
+#include "scalar.hpp"
 
 struct dcp_handle {
     int device = 0;
@@ -286,14 +287,38 @@ inline int wait_pinned_word(dcp_handle* h, const W* word, W sentinel, W* out = n
     return DCP_OK;
 }
 
-// Sum of n doubles in device memory (per-workgroup partials, added in order): copied to `pinned`, one stream
-// synchronisation.
-inline int read_partial_sum(dcp_handle* h, const double* part_dev, int n, double* pinned, double* sum) {
-    DCP_HIP_OK(h, hipMemcpyAsync(pinned, part_dev, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+// pinned[0 .. n) <- dev[0 .. n) once h->stream has run: one copy on the stream, one stream synchronisation
+template <class W>
+inline int read_words(dcp_handle* h, const W* dev, int n, W* pinned) {
+    DCP_HIP_OK(h, hipMemcpyAsync(pinned, dev, sizeof(W) * n, hipMemcpyDeviceToHost, h->stream));
     DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
+    return DCP_OK;
+}
+
+// *out <- the device scalar *dev through `pinned`, or through the start of the handle's pinned scratch
+template <class W, class O>
+inline int read_scalar(dcp_handle* h, const W* dev, O* out, W* pinned = nullptr) {
+    void* hostv = pinned;
+    if (pinned == nullptr) DCP_TRY(host_scratch(h, 64, &hostv));
+    DCP_TRY(read_words(h, dev, 1, static_cast<W*>(hostv)));
+    *out = (O)*static_cast<W*>(hostv);
+    return DCP_OK;
+}
+
+// Sum / maximum (NaN wins, as np.max) of n doubles in device memory -- per-workgroup partials, taken in order --
+// through `pinned`
+inline int read_partial_sum(dcp_handle* h, const double* part_dev, int n, double* pinned, double* sum) {
+    DCP_TRY(read_words(h, part_dev, n, pinned));
     double acc = 0.0;
     for (int i = 0; i < n; ++i) acc += pinned[i];
     *sum = acc;
+    return DCP_OK;
+}
+inline int read_partial_max(dcp_handle* h, const double* part_dev, int n, double* pinned, double* max) {
+    DCP_TRY(read_words(h, part_dev, n, pinned));
+    double m = 0.0;
+    for (int i = 0; i < n; ++i) m = max_np(pinned[i], m);
+    *max = m;
     return DCP_OK;
 }
 

@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(256) ksvd_count_kernel(const T* __restrict__ X
     for (int r = tid; r < nr; r += 256) m = rowcnt[r] > m ? rowcnt[r] : m;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        const int w = __shfl_down(m, o, 64);
+        const int w = lane_down(m, o);
         m = w > m ? w : m;
     }
     if (lane == 0 && m > 0) atomicMax(&meta[0], m);
@@ -190,7 +190,7 @@ __global__ void __launch_bounds__(256) ksvd_pass1_kernel(const T* __restrict__ R
     if (tile == 0 && wave == 0) {
         R a = 0;
         for (int e = lane; e < n; e += 64) a += abs2(s_gc[e]);
-        a = omp_wave_sum(a);
+        a = wave_sum_all(a);
         if (lane == 0) gpart[chunk] = a;
     }
     const long j = ((long)tile * 64 + lane) * V;
@@ -257,6 +257,8 @@ __global__ void __launch_bounds__(256) ksvd_finish_kernel(const T* __restrict__ 
     }
     uu = block_sum_256(uu, sh);
     dq = block_sum_256(dq, sh);
+    // (not block_sum_256_parts: handing it du's parts changes which product of mul(dj, conj(u)) the compiler fuses
+    // for complex64, and with it the bits of u . d^H)
     const R re = block_sum_256(real_part(du), sh);
     R im = 0;
     if constexpr (scalar_traits<T>::is_complex) im = block_sum_256(du.im, sh);
@@ -273,7 +275,7 @@ template <class S>
 __device__ __forceinline__ S ksvd_lane_sum(const S* __restrict__ a, int n, int lane) {
     S s = zero_of<S>();
     for (int t = lane; t < n; t += 64) s = add(s, a[t]);
-    return omp_wave_sum(s);
+    return wave_sum_all(s);
 }
 
 // ---- pass 2: d' = u / |u| (d where !(|u| > 0));  g' = R[i, :] d'^H + g (d . d'^H);  R[i, :] += g d - g' d';
@@ -320,7 +322,7 @@ __global__ void __launch_bounds__(256) ksvd_pass2_kernel(T* __restrict__ Rm, T* 
         }
         if (use_lds) *reinterpret_cast<P*>(slice + j) = rv;
     }
-    const T gn = fmadd(omp_wave_sum(acc), g, dd);
+    const T gn = fmadd(wave_sum_all(acc), g, dd);
     const T mgn = sub(zero_of<T>(), gn);
 #pragma unroll 4
     for (long j = (long)lane * V; j < F; j += 64 * V) {
@@ -344,21 +346,6 @@ __global__ void __launch_bounds__(256) ksvd_pass2_kernel(T* __restrict__ Rm, T* 
         for (int q = 0; q < V; ++q) o.v[q] = keep_d ? ov.v[q] : ksvd_div(uv.v[q], nrm);
         *reinterpret_cast<P*>(D + (long)k * F + j) = o;
     }
-}
-
-// part[b] = max |a - b| over this workgroup's grid-stride share (NaN wins, as np.max), as double
-template <class T>
-__global__ void __launch_bounds__(256) ksvd_maxdiff_kernel(const T* __restrict__ a, const T* __restrict__ b, long n,
-                                                           double* __restrict__ part) {
-    typedef real_t<T> R;
-    __shared__ R sh[4];
-    R m = 0;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
-        const R v = absval(sub(a[i], b[i]));
-        m = (v > m || v != v) ? v : m;
-    }
-    const R r = block_max_256(m, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = (double)r;
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------
@@ -465,8 +452,9 @@ inline int ksvd_sweep(dcp_handle* h, const T* Y, T* X, T* D, int N, int F, int K
     const bool vec = ksvd_vec<T>() > 1 && ((size_t)F * sizeof(T)) % 16 == 0 && al16_ptr(D);
     if (vec) DCP_TRY((ksvd_atoms<T, ksvd_vec<T>()>(h, X, D, N, F, K, cnt, w)));
     else DCP_TRY((ksvd_atoms<T, 1>(h, X, D, N, F, K, cnt, w)));
-    hipLaunchKernelGGL((ksvd_maxdiff_kernel<T>), dim3(grid_for((long)K * F, kKsvdMdParts)), dim3(256), 0, st,
-                       (const T*)D, (const T*)w.Dold, (long)K * F, w.mdpart);
+    // mdpart[b] = max |D - Dold| over workgroup b's share (NaN wins, as np.max), as double
+    hipLaunchKernelGGL((reduce_partial_kernel<MaxOp, MapAbsDiff<T>, double>), dim3(grid_for((long)K * F, kKsvdMdParts)),
+                       dim3(256), 0, st, MapAbsDiff<T>{D, w.Dold}, (long)K * F, w.mdpart);
     DCP_LAUNCH_OK(h, hipGetLastError());
     return DCP_OK;
 }
@@ -488,14 +476,7 @@ inline int ksvd_read_counts(dcp_handle* h, const int* meta, int K, const int* it
 inline int ksvd_read_maxdiff(dcp_handle* h, const double* mdpart, long n, double* maxdiff_out) {
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, kKsvdMdParts * sizeof(double), &hostv));
-    double* hd = reinterpret_cast<double*>(hostv);
-    const int parts = grid_for(n, kKsvdMdParts);
-    DCP_HIP_OK(h, hipMemcpyAsync(hd, mdpart, parts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    double m = 0.0;
-    for (int i = 0; i < parts; ++i) m = (hd[i] > m || hd[i] != hd[i]) ? hd[i] : m;
-    *maxdiff_out = m;
-    return DCP_OK;
+    return read_partial_max(h, mdpart, grid_for(n, kKsvdMdParts), reinterpret_cast<double*>(hostv), maxdiff_out);
 }
 
 inline int ksvd_check_sizes(dcp_handle* h, int64_t N, int64_t F, int64_t K) {

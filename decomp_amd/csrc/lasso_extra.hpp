@@ -217,14 +217,7 @@ __global__ void __launch_bounds__(256) admm_mask_system_kernel(const T* __restri
         TW acc = zero_of<TW>();
         for (long f = lane; f < F; f += 64)
             acc = madd(acc, to_work(scale(ai[f], m[f])), to_work(conj_of(aj[f])));
-        if constexpr (scalar_traits<T>::is_complex) {
-            for (int o = 32; o > 0; o >>= 1) {
-                acc.re += __shfl_xor(acc.re, o, 64);
-                acc.im += __shfl_xor(acc.im, o, 64);
-            }
-        } else {
-            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-        }
+        acc = wave_sum_all(acc);
         if (lane == 0) out[e] = (i == j) ? add_real(acc, rho) : acc;
     }
 }

@@ -408,7 +408,7 @@ __global__ void __launch_bounds__(256) gershgorin_finish_kernel(const R* __restr
         }
         for (; s < stripes; ++s) a0 += partial[(long)s * K + j];
         const R acc = (a0 + a1) + (a2 + a3);
-        best = (acc > best || acc != acc) ? acc : best;
+        best = max_np(acc, best);
     }
     R m = block_max_256(best, sh);
     if (threadIdx.x == 0) {
@@ -423,16 +423,6 @@ __global__ void __launch_bounds__(256) scale_vec_kernel(const R* __restrict__ v,
                                                         R* __restrict__ out) {
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L)
         out[i] = v[i] / divisor;
-}
-
-// sum of a real vector -> out[0]   (one workgroup; sum(mask) for 1-D masks)
-template <class R>
-__global__ void __launch_bounds__(256) vec_sum_kernel(const R* __restrict__ v, long n, R* __restrict__ out) {
-    __shared__ R sh[4];
-    R acc = 0;
-    for (long i = threadIdx.x; i < n; i += 256) acc += v[i];
-    R t = block_sum_256(acc, sh);
-    if (threadIdx.x == 0) out[0] = t;
 }
 
 // Coordinate-descent sweeps in Gram form.  One wave per row; lane l holds columns l + 64m of the
@@ -502,13 +492,7 @@ __global__ void __launch_bounds__(256) cd_gram_kernel(T* __restrict__ X, T* __re
                 }
                 const int kk = __ffsll((long long)mask) - 1;     // first moving coordinate
                 if (check && lane >= cursor && lane < kk && !((R(0) - tl[m]) < R(0))) viol = true;
-                T dk;
-                if constexpr (scalar_traits<T>::is_complex) {
-                    dk.re = __shfl(d.re, kk, 64);
-                    dk.im = __shfl(d.im, kk, 64);
-                } else {
-                    dk = __shfl(d, kk, 64);
-                }
+                const T dk = lane_get(d, kk);
                 if (lane == kk) {
                     x[m] = xn;
                     if (check && !((absval(d) - tl[m]) < R(0))) viol = true;
@@ -591,13 +575,7 @@ __global__ void __launch_bounds__(256) cd_gram_wide_kernel(T* __restrict__ X, T*
                 }
                 const int kk = __ffsll((long long)mask) - 1;
                 if (check && lane >= cursor && lane < kk && !((R(0) - tl) < R(0))) viol = true;
-                T dk;
-                if constexpr (scalar_traits<T>::is_complex) {
-                    dk.re = __shfl(d.re, kk, 64);
-                    dk.im = __shfl(d.im, kk, 64);
-                } else {
-                    dk = __shfl(d, kk, 64);
-                }
+                const T dk = lane_get(d, kk);
                 if (lane == kk) {
                     x = xn;
                     if (check && !((absval(d) - tl) < R(0))) viol = true;
@@ -645,7 +623,7 @@ __global__ void __launch_bounds__(256) cd_mask_kernel(T* __restrict__ X, T* __re
                                                       int nsweeps, int check_last,
                                                       int* __restrict__ flag) {
     typedef real_t<T> R;
-    __shared__ R sh_re[4], sh_im[4];
+    __shared__ R sh[4];
     __shared__ T s_d;
     const long row = blockIdx.x;
     T* r = Rres + row * F;
@@ -659,15 +637,10 @@ __global__ void __launch_bounds__(256) cd_mask_kernel(T* __restrict__ X, T* __re
             for (long f = threadIdx.x; f < F; f += 256) {
                 const T t = mul(r[f], conj_of(ak[f]));
                 pre += real_part(t);
-                if constexpr (scalar_traits<T>::is_complex) pim += t.im;
+                pim += imag_part(t);
             }
-            const R tre = block_sum_256(pre, sh_re);
-            R tim = 0;
-            if constexpr (scalar_traits<T>::is_complex) tim = block_sum_256(pim, sh_im);
+            const T dot = block_sum_256_parts<T>(pre, pim, sh);
             if (threadIdx.x == 0) {
-                T dot;
-                if constexpr (scalar_traits<T>::is_complex) { dot.re = tre; dot.im = tim; }
-                else dot = tre;
                 const T xk = X[row * K + k];
                 const T z = add(dot, scale(xk, akk[k]));
                 const T xn = prox_apply<PROX>(z, alphak[k] * rowscale[row]);
@@ -786,8 +759,7 @@ inline int gram_kk(dcp_handle* h, const T* P, const T* Q, int K, int F, LassoWs<
     plan_splits<FORM_NT>(g, 512, kMaxSplits);
     if ((size_t)g.ksplits * K * K > w.slab_count) return fail(h, DCP_ERR_INTERNAL, "lasso slab plan");
     DCP_LAUNCH_OK(h, (gemm<FORM_NT>(h->stream, g, EpiSlab<T>{w.slabs, K, (long)K * K})));
-    hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, h->stream,
-                       w.slabs, (long)K * K, g.ksplits, (long)K * K, out);
+    launch_reduce_slabs_scalar<T>(h->stream, w.slabs, (long)K * K, g.ksplits, (long)K * K, out);
     DCP_LAUNCH_OK(h, hipGetLastError());
     return DCP_OK;
 }
@@ -828,10 +800,7 @@ inline int lasso_settle_deferred(dcp_handle* h) {
 
 template <class T>
 inline int read_flag(dcp_handle* h, int* flag_dev, int* host_flag, bool* violated) {
-    DCP_HIP_OK(h, hipMemcpyAsync(host_flag, flag_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    *violated = (*host_flag != 0);
-    return DCP_OK;
+    return read_scalar(h, (const int*)flag_dev, violated, host_flag);
 }
 
 // scal[0] = 1 / L, scal[2] = L for L = max_j sum_i |M[i, j]|  (eigen.py:20)
@@ -892,7 +861,8 @@ inline int lasso_solve(dcp_handle* h, const T* Y, const real_t<T>* mask, int mas
                            (long)N, (long)F, 0L, w.Ym);
         DCP_LAUNCH_OK(h, hipGetLastError());
         Yuse = w.Ym;
-        hipLaunchKernelGGL((vec_sum_kernel<R>), dim3(1), dim3(256), 0, st, mask, (long)F, w.scal + 1);
+        hipLaunchKernelGGL((reduce_vector_kernel<SumOp, R, FinStore<R>>), dim3(1), dim3(256), 0, st, mask, (long)F,
+                           FinStore<R>{w.scal + 1});   // sum(mask)
         DCP_LAUNCH_OK(h, hipGetLastError());
     } else if (mask_ndim == 2) {
         hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for((long)N * F)), dim3(256), 0, st, Y, mask,
@@ -951,10 +921,10 @@ inline int lasso_solve(dcp_handle* h, const T* Y, const real_t<T>* mask, int mas
         DCP_TRY(gram_kk<T>(h, w.An, w.An, K, F, w, w.AAt));
         have_gram = true;
         DCP_TRY(gershgorin_bound<T>(h, w.AAt, K, w));
-        R* host_l = reinterpret_cast<R*>(reinterpret_cast<char*>(hostv) + 16);
-        DCP_HIP_OK(h, hipMemcpyAsync(host_l, w.scal + 2, sizeof(R), hipMemcpyDeviceToHost, st));
-        DCP_HIP_OK(h, hipStreamSynchronize(st));
-        const R ratio = (R)K / host_l[0];
+        R bound = 0;
+        DCP_TRY(read_scalar(h, (const R*)(w.scal + 2), &bound,
+                            reinterpret_cast<R*>(reinterpret_cast<char*>(hostv) + 16)));
+        const R ratio = (R)K / bound;
         pcd_p = (ratio == ratio && ratio < R(2147483647)) ? (int)ratio : 0;
         if (pcd_p <= 1) {
             if (mask_ndim == 2)

@@ -236,8 +236,9 @@ int nmf_gauss_logp_api(dcp_handle* h, const T* Y, const T* mask, const T* X, con
     GemmArgs<T> a;
     a.A = X; a.lda = K; a.B = D; a.ldb = F; a.M = (int)N; a.N = (int)F; a.K = (int)K;
     DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiResidual<T>{Y, F, nullptr, 0, w.tmp, F})));   // d = y - x D
-    hipLaunchKernelGGL((gauss_logp_partial_kernel<T>), dim3(w.blocks), dim3(256), 0, h->stream, (const T*)w.tmp,
-                       mask, (long)N * F, 1.0 / scale, log(scale) + 3.14159265358979323846 * 0.5, w.part);
+    hipLaunchKernelGGL((reduce_partial_kernel<SumOp, MapGaussLogp<T>, double>), dim3(w.blocks), dim3(256), 0, h->stream,
+                       MapGaussLogp<T>{w.tmp, mask, 1.0 / scale, log(scale) + 3.14159265358979323846 * 0.5},
+                       (long)N * F, w.part);
     DCP_LAUNCH_OK(h, hipGetLastError());
     return w.sum(h, out);
 }
@@ -309,15 +310,9 @@ int nmf_apply_api(dcp_handle* h, const T* D, const T* P, const T* Q, double alph
                        (const T*)wu.U, (long)F, (long)F, 1, D, (long)F, D_new, (long)F, wu.rowmax,
                        (T*)nullptr, (T*)nullptr, (T*)nullptr);
     DCP_HIP_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((final_max_kernel<T>), dim3(1), dim3(256), 0, h->stream, (const T*)wu.rowmax,
-                       (long)K, md);
+    launch_final_max<T>(h->stream, wu.rowmax, (long)K, md);
     DCP_HIP_OK(h, hipGetLastError());
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, 64, &hostv));
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, md, sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    *maxdiff = (double)(*reinterpret_cast<T*>(hostv));
-    return DCP_OK;
+    return read_scalar(h, md, maxdiff);
 }
 
 template <class T>

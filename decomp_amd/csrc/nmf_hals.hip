@@ -43,8 +43,7 @@ int hals_x_side(dcp_handle* h, const T* Y, const T* Xc, T* Xn, const T* Dc, cons
             launch_reduce_slabs_affine<T>(st, w.slabs, (long)K * K, g.ksplits, (long)K * K, T(0), (long)K, T(pen.l2),
                                           w.G);
         else
-            hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, st, w.slabs,
-                               (long)K * K, g.ksplits, (long)K * K, w.G);
+            launch_reduce_slabs_scalar<T>(st, w.slabs, (long)K * K, g.ksplits, (long)K * K, w.G);
         DCP_LAUNCH_OK(h, hipGetLastError());
     }
     {   // C = Y D^T, then the x sweep

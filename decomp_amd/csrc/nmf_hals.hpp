@@ -270,7 +270,7 @@ inline hipError_t launch_nn_cd_sweep(hipStream_t st, const T* V_in, T* V_out, lo
 // ---- the normalisation of one HALS iteration ----------------------------------------------------
 // n_k = ||U_k||_2.  n_k > 0: D_new[k] = U_k / n_k, nrm[k] = n_k;  n_k = 0: D_new[k] = U_k (= 0), nrm[k] = 1.
 // max|ref - D_new| goes to *gmax (zero on entry; *gmax_zero is cleared for the next iteration) and, by the
-// last-arriving workgroup, to the pinned host word the loop polls -- the protocol of row_normalize_kernel.
+// last-arriving workgroup, to the pinned host word the loop polls (publish_max).
 template <class T>
 __global__ void __launch_bounds__(256) hals_normalize_kernel(const T* __restrict__ U, long F,
                                                              const T* __restrict__ ref, T* __restrict__ out,
@@ -297,21 +297,13 @@ __global__ void __launch_bounds__(256) hals_normalize_kernel(const T* __restrict
     for (long j = threadIdx.x; j < F; j += 256) {
         const T o = scale ? u[j] / n : u[j];
         const T d = fabs(ref[row * F + j] - o);
-        md = (d > md || d != d) ? d : md;
+        md = max_np(d, md);
         out[row * F + j] = o;
     }
     const T m = block_max_256(md, sh);
     if (threadIdx.x == 0) {
-        unsigned int inc = 1u;
-        const T old = atomic_max_nonneg_ret(gmax, m);
-        asm volatile("; the arrival is counted behind the max" : "+v"(inc) : "v"(old));
         if (gmax_zero != nullptr && row == 0) *gmax_zero = T(0);
-        if (ticket != nullptr && host_out != nullptr) {
-            if (atomicAdd(ticket, inc) == gridDim.x - 1u) {
-                *host_out = atomic_read_nonneg(gmax);
-                atomicExch(ticket, 0u);
-            }
-        }
+        publish_max(m, gmax, ticket, host_out, true);
     }
 }
 

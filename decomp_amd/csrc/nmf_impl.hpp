@@ -162,8 +162,7 @@ inline int column_sums(dcp_handle* h, const T* a, long ld, long rows, long cols,
     hipLaunchKernelGGL((colsum_partial_kernel<T>), grid, dim3(256), 0, h->stream, a, ld, rows,
                        cols, rows_per, part);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for(cols, 64)), dim3(256), 0, h->stream,
-                       part, cols, stripes, cols, out);
+    launch_reduce_slabs_scalar<T>(h->stream, part, cols, stripes, cols, out, 64);
     DCP_LAUNCH_OK(h, hipGetLastError());
     return DCP_OK;
 }
@@ -235,12 +234,13 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
                     return fail(h, DCP_ERR_INTERNAL, "nmf stacked x-update slab plan mismatch");
                 DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, sg, EpiSlab<T>{w.slabs, K, (long)2 * N * K})));
                 if (pen.on())
-                    hipLaunchKernelGGL((mu_quotient_stacked_pen_kernel<T>), dim3(grid_for((long)N * K)), dim3(256),
+                    hipLaunchKernelGGL((mu_quotient_stacked_kernel<T, true>), dim3(grid_for((long)N * K)), dim3(256),
                                        0, st, Xin, (const T*)w.slabs, (long)2 * N * K, sg.ksplits, (long)N * K, l1,
                                        l2, Xout);
                 else
-                    hipLaunchKernelGGL((mu_quotient_stacked_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0,
-                                       st, Xin, (const T*)w.slabs, (long)2 * N * K, sg.ksplits, (long)N * K, Xout);
+                    hipLaunchKernelGGL((mu_quotient_stacked_kernel<T, false>), dim3(grid_for((long)N * K)), dim3(256),
+                                       0, st, Xin, (const T*)w.slabs, (long)2 * N * K, sg.ksplits, (long)N * K, l1,
+                                       l2, Xout);
                 DCP_LAUNCH_OK(h, hipGetLastError());
                 done = true;
             }
@@ -269,8 +269,7 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
             if (!std::is_same<T, float>::value) g.tile = TILE_SMALL_DEEP;   // float64: 64 x 64 tiles (see f64_tier)
             plan_splits<FORM_NT>(g, 512, kMaxSplits, 16);   // tiny output: 256-deep splits (measured best)
             DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, g, EpiSlab<T>{w.slabs, K, (long)K * K})));
-            hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0,
-                               st, w.slabs, (long)K * K, g.ksplits, (long)K * K, w.G);
+            launch_reduce_slabs_scalar<T>(st, w.slabs, (long)K * K, g.ksplits, (long)K * K, w.G);
             DCP_LAUNCH_OK(h, hipGetLastError());
         }
         if (!split_gram) {   // Q = x G
@@ -336,20 +335,21 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
             if (split_gram) {
                 GemmArgs<T> q;   // x_new = x * max(sum slabs, 0) / max(x G, eps)
                 q.A = Xin; q.lda = K; q.B = w.G; q.ldb = K; q.M = N; q.N = K; q.K = K;
-                const EpiMuDenSlabs<T> den{Xin, K, w.slabs, K, (long)N * K, pg.ksplits, Xout, K};
                 if (pen.on())
-                    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, q, EpiMuDenSlabsPen<T>{den, l1, l2})));
+                    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, q, EpiMuDenSlabs<T, true>{Xin, K, w.slabs, K, (long)N * K,
+                                                                                   pg.ksplits, Xout, K, l1, l2})));
                 else
-                    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, q, den)));
+                    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, q, EpiMuDenSlabs<T, false>{Xin, K, w.slabs, K, (long)N * K,
+                                                                                    pg.ksplits, Xout, K})));
             } else {
                 if (pen.on())
-                    hipLaunchKernelGGL((mu_quotient_slabs_pen_kernel<T>), dim3(grid_for((long)N * K)), dim3(256),
+                    hipLaunchKernelGGL((mu_quotient_slabs_kernel<T, true>), dim3(grid_for((long)N * K)), dim3(256),
                                        0, st, Xin, (const T*)w.slabs, (long)N * K, pg.ksplits, xden,
                                        (long)ld_xden, (long)N, (long)K, l1, l2, Xout);
                 else
-                    hipLaunchKernelGGL((mu_quotient_slabs_kernel<T>), dim3(grid_for((long)N * K)), dim3(256),
+                    hipLaunchKernelGGL((mu_quotient_slabs_kernel<T, false>), dim3(grid_for((long)N * K)), dim3(256),
                                        0, st, Xin, (const T*)w.slabs, (long)N * K, pg.ksplits, xden,
-                                       (long)ld_xden, (long)N, (long)K, Xout);
+                                       (long)ld_xden, (long)N, (long)K, l1, l2, Xout);
                 DCP_LAUNCH_OK(h, hipGetLastError());
             }
         }
@@ -425,8 +425,7 @@ inline int nmf_grad_x(dcp_handle* h, const T* Ypre, const T* mask, const T* X, c
         g.A = D; g.lda = F; g.B = D; g.ldb = F; g.M = K; g.N = K; g.K = F;
         plan_splits<FORM_NT>(g, 512, kMaxSplits, 16);
         DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, g, EpiSlab<T>{w.slabs, K, (long)K * K})));
-        hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, st, w.slabs,
-                           (long)K * K, g.ksplits, (long)K * K, w.G);
+        launch_reduce_slabs_scalar<T>(st, w.slabs, (long)K * K, g.ksplits, (long)K * K, w.G);
         DCP_LAUNCH_OK(h, hipGetLastError());
         GemmArgs<T> q;
         q.A = X; q.lda = K; q.B = w.G; q.ldb = K; q.M = N; q.N = K; q.K = K;
@@ -514,8 +513,7 @@ inline int nmf_update(dcp_handle* h, const T* stats, const T* D, T* D_new, int64
                        1, D, (long)F, D_new, (long)F, w.rowmax, (T*)nullptr, (T*)nullptr,
                        (T*)nullptr);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((final_max_kernel<T>), dim3(1), dim3(256), 0, st, w.rowmax, (long)K,
-                       maxdiff_dev);
+    launch_final_max<T>(st, w.rowmax, (long)K, maxdiff_dev);
     DCP_LAUNCH_OK(h, hipGetLastError());
     return DCP_OK;
 }
@@ -527,8 +525,8 @@ inline int nmf_residual(dcp_handle* h, const T* Y, const T* mask, const T* X, co
     GemmArgs<T> a;
     a.A = X; a.lda = K; a.B = D; a.ldb = F; a.M = (int)N; a.N = (int)F; a.K = (int)K;
     DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiResidual<T>{Y, F, mask, F, tmpNF, F})));
-    hipLaunchKernelGGL((sumsq_partial_kernel<T>), dim3(nblocks), dim3(256), 0, h->stream, tmpNF,
-                       (long)N * F, partial_dev);
+    hipLaunchKernelGGL((reduce_partial_kernel<SumOp, MapAbs2<T>, double>), dim3(nblocks), dim3(256), 0, h->stream,
+                       MapAbs2<T>{tmpNF}, (long)N * F, partial_dev);
     DCP_LAUNCH_OK(h, hipGetLastError());
     return DCP_OK;
 }
@@ -542,8 +540,8 @@ inline int nmf_beta_divergence(dcp_handle* h, const T* Y, const T* mask, const T
     GemmArgs<T> a;
     a.A = X; a.lda = K; a.B = D; a.ldb = F; a.M = (int)N; a.N = (int)F; a.K = (int)K;
     DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiBetaDivergence<T>{Y, F, mask, F, beta, tmpNF, F})));
-    hipLaunchKernelGGL((sum_partial_kernel<T>), dim3(nblocks), dim3(256), 0, h->stream, (const T*)tmpNF,
-                       (long)N * F, partial_dev);
+    hipLaunchKernelGGL((reduce_partial_kernel<SumOp, MapValue<T>, double>), dim3(nblocks), dim3(256), 0, h->stream,
+                       MapValue<T>{tmpNF}, (long)N * F, partial_dev);
     DCP_LAUNCH_OK(h, hipGetLastError());
     return DCP_OK;
 }
@@ -574,15 +572,13 @@ inline int nmf_mask_prepare(dcp_handle* h, const T* Y, const T* mask, int64_t N,
     DCP_TRY(nmf_premask<T>(h, Y, mask, N, F, Ym, &Ypre));
     *binary = 0;
     if (!std::is_same<T, float>::value || bits == nullptr) return DCP_OK;
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, 64, &hostv));
     DCP_HIP_OK(h, hipMemsetAsync(flag_dev, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL((mask_rowbits_kernel<T>), dim3(grid_for(((N + 31) / 32) * F)), dim3(256), 0,
                        h->stream, mask, (long)N, (long)F, bits, flag_dev);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, flag_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    *binary = (*reinterpret_cast<int*>(hostv) == 0) ? 1 : 0;
+    int not_binary = 0;
+    DCP_TRY(read_scalar(h, (const int*)flag_dev, &not_binary));
+    *binary = (not_binary == 0) ? 1 : 0;
     return DCP_OK;
 }
 

@@ -52,33 +52,6 @@ template <class R> DCP_HD R omp_eps_dep();
 template <> DCP_HD float  omp_eps_dep<float>()  { return 4.8828125e-4f; }              // 4096 * 2^-23 = 2^-11
 template <> DCP_HD double omp_eps_dep<double>() { return 9.094947017729282e-13; }      // 4096 * 2^-52 = 2^-40
 
-// ---- cross-lane helpers -------------------------------------------------------------------------
-__device__ __forceinline__ float  omp_xor(float v, int m)  { return __shfl_xor(v, m, 64); }
-__device__ __forceinline__ double omp_xor(double v, int m) { return __shfl_xor(v, m, 64); }
-template <class R>
-__device__ __forceinline__ cx<R> omp_xor(cx<R> v, int m) { return cx<R>{omp_xor(v.re, m), omp_xor(v.im, m)}; }
-
-// v of lane l in every lane; l is wave-uniform (v_readlane_b32)
-__device__ __forceinline__ float omp_lane(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ double omp_lane(double v, int l) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-template <class R>
-__device__ __forceinline__ cx<R> omp_lane(cx<R> v, int l) { return cx<R>{omp_lane(v.re, l), omp_lane(v.im, l)}; }
-
-// the sum over the 64 lanes, the same bits in every lane (a + b == b + a at every butterfly step)
-template <class T>
-__device__ __forceinline__ T omp_wave_sum(T v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = add(v, omp_xor(v, m));
-    return v;
-}
-
 // v where keep, else +0, by a bit mask (a select of a loaded value may be sunk into a branch around the load)
 __device__ __forceinline__ float omp_keep(float v, bool keep) { return __int_as_float(__float_as_int(v) & -(int)keep); }
 __device__ __forceinline__ double omp_keep(double v, bool keep) {
@@ -214,8 +187,8 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
             }
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) {
-                const R oc = omp_xor(bc, m);
-                const int ok = __shfl_xor(bk, m, 64);
+                const R oc = lane_xor(bc, m);
+                const int ok = lane_xor(bk, m);
                 const bool take = oc > bc || (oc == bc && ok < bk);
                 bc = take ? oc : bc;
                 bk = take ? ok : bk;
@@ -229,7 +202,7 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
             T w = zero_of<T>();
             R wn2 = R(0);
             for (int m = 0; m < n; ++m) {
-                const T wm = omp_lane(scale(b, dinv), m);
+                const T wm = lane_bcast(scale(b, dinv), m);
                 wn2 += abs2(wm);
                 const T lcol = omp_keep(L[lc * ld + m], lane > m && lane < n);   // column m: odd stride, no conflict
                 b = fmsub(b, lcol, wm);
@@ -241,7 +214,7 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
             const R ldiag = sqrt(d), rdiag = R(1) / ldiag;
             {
                 const T wc = conj_of(w);
-                const T zn_part = omp_wave_sum(omp_keep(mul(wc, z), lane < n));   // sum_{m<n} L[n][m] z_m
+                const T zn_part = wave_sum_all(omp_keep(mul(wc, z), lane < n));   // sum_{m<n} L[n][m] z_m
                 const T zn = scale(sub(conj_of(a0k), zn_part), rdiag);
                 if (lane < n) L[n * ld + lane] = wc;
                 if (lane == n) {
@@ -257,7 +230,7 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
             T t = omp_keep(z, lane <= n);
             T v = zero_of<T>();
             for (int m = n; m >= 0; --m) {
-                const T vm = omp_lane(scale(t, dinv), m);
+                const T vm = lane_bcast(scale(t, dinv), m);
                 const T lrow = omp_keep(L[m * ld + lc], lane < m);   // row m: contiguous
                 t = fmsub(t, conj_of(lrow), vm);
                 if (lane == m) v = vm;
@@ -266,7 +239,7 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
             if (lane <= n) xs[lane] = x;   // (the scoring loop's reads of xs lie before the barrier above)
             ++n;
             __syncthreads();
-            if (use_tol) r2 = yn2 - real_part(omp_wave_sum(omp_keep(mul(x, conj_of(a0sel)), lane < n)));
+            if (use_tol) r2 = yn2 - real_part(wave_sum_all(omp_keep(mul(x, conj_of(a0sel)), lane < n)));
         }
 
         // ---- the row of X, zeros off the support ----
@@ -382,14 +355,7 @@ inline int omp_solve(dcp_handle* h, const T* Y, const T* A, T* X, int N, int F, 
 }
 
 // *it_out = the device word, after the stream has run
-inline int omp_read_it(dcp_handle* h, const int* it_dev, int* it_out) {
-    void* hostv = nullptr;
-    DCP_TRY(host_scratch(h, 64, &hostv));
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, it_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
-    *it_out = *reinterpret_cast<int*>(hostv);
-    return DCP_OK;
-}
+inline int omp_read_it(dcp_handle* h, const int* it_dev, int* it_out) { return read_scalar(h, it_dev, it_out); }
 
 template <class T>
 inline int omp_api(dcp_handle* h, const T* Y, const T* A, T* X, int64_t N, int64_t F, int64_t K, int n_nonzero,

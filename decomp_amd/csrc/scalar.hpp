@@ -115,5 +115,8 @@ DCP_HD double max_np(double a, double floor_) { return (a > floor_ || a != a) ? 
 DCP_HD float  real_part(float a)  { return a; }
 DCP_HD double real_part(double a) { return a; }
 template <class R> DCP_HD R real_part(cx<R> a) { return a.re; }
+DCP_HD float  imag_part(float)  { return 0.0f; }
+DCP_HD double imag_part(double) { return 0.0; }
+template <class R> DCP_HD R imag_part(cx<R> a) { return a.im; }
 
 }  // namespace dcp

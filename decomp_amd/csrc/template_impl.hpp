@@ -343,15 +343,18 @@ __global__ void __launch_bounds__(256) tm_gram_fill_kernel(TmGeom g, long lo, lo
 
 // scal[0] = 1 / max(v) (+ jitter on the max: scal[1] = max + jitter)   (one workgroup, fixed order)
 template <class R>
-__global__ void __launch_bounds__(256) tm_max_kernel(const R* __restrict__ v, long n, R jitter, R* __restrict__ scal) {
-    __shared__ R sh[4];
-    R best = 0;
-    for (long i = threadIdx.x; i < n; i += 256) best = (v[i] > best || v[i] != v[i]) ? v[i] : best;
-    const R m = block_max_256(best, sh);
-    if (threadIdx.x == 0) {
+struct FinInvMax {
+    R jitter;
+    R* scal;
+    __device__ __forceinline__ void operator()(R m) const {
         scal[0] = R(1) / (m + jitter);
         scal[1] = m + jitter;
     }
+};
+template <class R>
+inline void launch_tm_max(hipStream_t st, const R* v, long n, R jitter, R* scal) {
+    hipLaunchKernelGGL((reduce_vector_kernel<MaxOp, R, FinInvMax<R>>), dim3(1), dim3(256), 0, st, v, n,
+                       FinInvMax<R>{jitter, scal});
 }
 
 // ---- dictionary statistics ----------------------------------------------------------------------
@@ -461,18 +464,13 @@ __global__ void __launch_bounds__(256) tm_dupdate_rows_kernel(const T* __restric
     for (long i = threadIdx.x; i < n; i += 256) {
         ca += absval(XXt[i * n + j]);
         const T p = mul(XXt[j * n + i], D[i]);
-        if constexpr (scalar_traits<T>::is_complex) { re += p.re; im += p.im; }
-        else re += p;
+        re += real_part(p);
+        im += imag_part(p);
     }
     const R tca = block_sum_256(ca, sh);
-    const R tre = block_sum_256(re, sh);
-    R tim = 0;
-    if constexpr (scalar_traits<T>::is_complex) tim = block_sum_256(im, sh);
+    const T dot = block_sum_256_parts<T>(re, im, sh);
     if (threadIdx.x == 0) {
         colabs[j] = tca;
-        T dot;
-        if constexpr (scalar_traits<T>::is_complex) dot = T{tre, tim};
-        else dot = tre;
         step[j] = sub(yX[j], dot);
     }
 }
@@ -617,7 +615,7 @@ inline int tm_lasso_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmG
             DCP_LAUNCH_OK(h, hipGetLastError());
         }
     }
-    hipLaunchKernelGGL((tm_max_kernel<R>), dim3(1), dim3(256), 0, st, (const R*)colsum, TC, R(0), scal);
+    launch_tm_max<R>(st, colsum, TC, R(0), scal);
     DCP_LAUNCH_OK(h, hipGetLastError());
 
     const bool mom = method != DCP_LASSO_ISTA;
@@ -746,7 +744,7 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
     hipLaunchKernelGGL((tm_dupdate_rows_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)XXt, (const T*)yX,
                        (const T*)D, TS, colabs, step);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((tm_max_kernel<R>), dim3(1), dim3(256), 0, st, (const R*)colabs, TS, R(1.0e-15), scal);
+    launch_tm_max<R>(st, colabs, TS, R(1.0e-15), scal);
     DCP_LAUNCH_OK(h, hipGetLastError());
     hipLaunchKernelGGL((tm_dupdate_apply_kernel<T>), dim3(tm_grid(TS)), dim3(256), 0, st, (const T*)D,
                        (const T*)step, (const R*)scal, TS, U);
@@ -757,7 +755,7 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
                        g.S, Dn, g.S, rowmax);
     DCP_LAUNCH_OK(h, hipGetLastError());
     DCP_HIP_OK(h, hipMemcpyAsync(D, Dn, (size_t)TS * sizeof(T), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL((tm_max_kernel<R>), dim3(1), dim3(256), 0, st, (const R*)rowmax, g.T, R(0), scal + 2);
+    launch_tm_max<R>(st, rowmax, g.T, R(0), scal + 2);
     DCP_LAUNCH_OK(h, hipGetLastError());
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, 64, &hostv));

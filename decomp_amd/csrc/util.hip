@@ -39,14 +39,13 @@ int count_negative_api(dcp_handle* h, const T* x, int64_t n, int64_t* count) {
     DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { a.take(part, blocks); }));
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, sizeof(unsigned long long) * blocks, &hostv));
-    hipLaunchKernelGGL((count_negative_kernel<T>), dim3(blocks), dim3(256), 0, h->stream, x,
-                       (long)n, part);
+    hipLaunchKernelGGL((reduce_partial_kernel<SumOp, MapNegative<T>, unsigned long long>), dim3(blocks), dim3(256), 0,
+                       h->stream, MapNegative<T>{x}, (long)n, part);
     DCP_HIP_OK(h, hipGetLastError());
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, part, sizeof(unsigned long long) * blocks,
-                                 hipMemcpyDeviceToHost, h->stream));
-    DCP_HIP_OK(h, hipStreamSynchronize(h->stream));
+    unsigned long long* host = reinterpret_cast<unsigned long long*>(hostv);
+    DCP_TRY(read_words(h, (const unsigned long long*)part, blocks, host));
     unsigned long long tot = 0;
-    for (int i = 0; i < blocks; ++i) tot += reinterpret_cast<unsigned long long*>(hostv)[i];
+    for (int i = 0; i < blocks; ++i) tot += host[i];
     *count = (int64_t)tot;
     return DCP_OK;
 }
@@ -226,8 +225,7 @@ int gemm_api(dcp_handle* h, int form, const T* A, const T* B, T* C, int64_t M, i
         else if (form == FORM_NN) e = gemm_hook_launch<FORM_NN>(h->stream, a, tile, epi);
         else e = gemm_hook_launch<FORM_TN>(h->stream, a, tile, epi);
         if (e != hipSuccess) return fail(h, DCP_ERR_HIP, hipGetErrorString(e));
-        hipLaunchKernelGGL((reduce_slabs_kernel<T>), dim3(grid_for(M * N)), dim3(256), 0, h->stream,
-                           slabs, (long)(M * N), a.ksplits, (long)(M * N), C);
+        launch_reduce_slabs_scalar<T>(h->stream, slabs, (long)(M * N), a.ksplits, (long)(M * N), C);
         DCP_HIP_OK(h, hipGetLastError());
     } else {
         if (ext_floats) {
@@ -577,8 +575,7 @@ int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B,
         EpiSlab<float> epi{slabs, (long)N, (long)M * N};
         e = (form == FORM_NT) ? gemm_bf16x6<FORM_NT>(h->stream, a, epi) : gemm_bf16x6<FORM_TN>(h->stream, a, epi);
         if (e != hipSuccess) return fail(h, DCP_ERR_HIP, hipGetErrorString(e));
-        hipLaunchKernelGGL((reduce_slabs_kernel<float>), dim3(grid_for(M * N)), dim3(256), 0, h->stream, slabs,
-                           (long)(M * N), a.ksplits, (long)(M * N), C);
+        launch_reduce_slabs_scalar<float>(h->stream, slabs, (long)(M * N), a.ksplits, (long)(M * N), C);
         DCP_HIP_OK(h, hipGetLastError());
     } else {
         EpiStore<float> epi{C, (long)N};

@@ -311,7 +311,8 @@ def _apply_inputs(K, F, dt, seed):
 @pytest.mark.parametrize('F', APPLY_F)
 def test_apply_against_float64(F, K):
     """Normalise path: row_normalize_kernel keeps rows of F <= 4096 in registers, and strides over longer ones;
-    final_max_kernel reduces K rows.  D_new against l2_strict(rule) from the same inputs: the rule costs a few u
+    reduce_vector_kernel (MaxOp) reduces K rows.  D_new against l2_strict(rule) from the same inputs: the rule costs a
+    few u
     per entry (relative to D (|1 - alpha| + alpha |P| / q) where it cancels), the norm P(F) + 2u, the division u.
     max|dD| must equal np.max(np.abs(D - D_new)) exactly; a row whose rule output is all zero gives NaN there and
     in max|dD|, as the reference's U / sqrt(0) does."""
