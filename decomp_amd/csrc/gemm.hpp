@@ -785,6 +785,39 @@ struct EpiMuNumPen : EpiMuNum<T> {
     }
 };
 
+// EpiMuNum / EpiMuNumPen whose denominator cur . gram is formed by the product's own workgroup (the denominator
+// tail of the 256 x 256 split-bf16 NT kernel, gemm_mfma_bf16x6.hpp) and never stored:
+//   out = cur * max(acc, 0) / max(den, 1e-15),   den = (cur . gram)[r, c]  (+ l1 + l2 cur with PEN)
+// The quotient is EpiMuNum::vec4's expression, so out is bitwise what the two-kernel path gives.
+template <bool PEN>
+struct EpiMuGramDen {
+    static constexpr bool kVec4 = true;
+    static constexpr bool kDenTail = true;
+    const float* cur;
+    long ld_cur;
+    const float* gram;   // [depth, depth]
+    long ld_gram;
+    int depth;
+    float* out;
+    long ld_out;
+    float l1 = 0.0f, l2 = 0.0f;
+    bool vec_ok() const {
+        return al16_ptr(cur) && al16_ptr(gram) && al16_ptr(out) && (ld_cur % 4) == 0 && (ld_gram % 4) == 0 &&
+               (ld_out % 4) == 0;
+    }
+    __device__ __forceinline__ void quot4(int r, int c0, f32x4 v, f32x4 d) const {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(cur + (long)r * ld_cur + c0);
+        const float a1 = l1, a2 = l2;
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (PEN) o[e] = x[e] * max_np(v[e], 0.0f) / max_np(d[e] + a1 + a2 * x[e], 1.0e-15f);
+            else o[e] = x[e] * max_np(v[e], 0.0f) / max_np(d[e], 1.0e-15f);
+        }
+        *reinterpret_cast<f32x4*>(out + (long)r * ld_out + c0) = o;
+    }
+};
+
 // out = cur * max(num, 0) / max(acc, 1e-15): acc is the NEGATIVE gradient part.
 template <class T>
 struct EpiMuDen {

@@ -48,6 +48,11 @@
 //     each plane's granule with one ds_write_b64; the fragment is read back transposed with two
 //     ds_read_b64_tr_b16 (k 8h..8h+3 and 8h+4..8h+7).  A 32-lane half of one such read takes 4 k rows
 //     x 8 granules; the XOR puts them on 32 distinct bank pairs (conflict free).
+//
+// Denominator tail (256 x 256 NT tile, epilogue functors with kDenTail: the NMF x update): after the K loop the
+// workgroup forms its own tile of x.G on the fp32 MFMA, through the freed LDS ring and in the exact order of the
+// stand-alone fp32 product, and applies the MU quotient to the accumulators; x.G is never stored.  Described at
+// x6_den_tail() below.  The K loop, its ring and its barriers are the same code for every functor.
 #pragma once
 #include "gemm_mfma_f32.hpp"
 #include <type_traits>
@@ -152,6 +157,154 @@ __device__ __forceinline__ x6_bf16x8 x6_frag(const char* plane, int off) {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(plane + off));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(plane + off + 4 * ROWS * 2));
     return __builtin_bit_cast(x6_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// ---- fused denominator tail (256 x 256 NT tile, functors with `static constexpr bool kDenTail = true`) ----
+// The NMF x update needs  x_new = x o max(Y.D^T, 0) / max(x.G, eps).  With such a functor the workgroup, after its
+// bf16x6 K loop has left num = Y.D^T in the accumulators, forms its own 256 x 256 tile of den = x.G on the fp32
+// MFMA and applies the quotient; den never reaches memory.  The functor carries
+//     const float* cur; long ld_cur      x (left operand of x.G and the quotient's multiplicand)
+//     const float* gram; long ld_gram    G, [depth, >= n0 + 256] row-major
+//     int depth                          reduction depth of x.G (the atom count), a multiple of 16
+//     void quot4(int row, int col0, f32x4 num, f32x4 den) const
+// Bits: every element of den starts at 0 and takes v_mfma_f32_32x32x2_f32 over K blocks of 16 in ascending
+// order, inside a block c = 0, 1 then s = 0 .. 3, the lane halves h supplying k = 8c + 4h + s: the sequence of
+// gemm_mfma_kernel<TileCfg<256, 256, 16, 64, 64, 1>, KMAJOR, XMAJOR> (its PIPE == 0 loop, panel_frag), so den is
+// bitwise the stand-alone product's.  Nothing assumes G symmetric.
+// Registers: num holds 64 of the wave's 128; den is formed in two passes of 32 x 64 per wave (32 registers), pass i
+// over the wave's i-th 32-row block, i.e. 128 of the tile's 256 rows per pass, and the quotient of those rows runs
+// at the end of their pass.
+// LDS: the ring of the K loop is free after one barrier.  A stage is one 16-deep K block of one pass: the x panel
+// [128 rows][16 k] (8 KiB, 16-byte chunks XOR-swizzled as the fp32 core's KMAJOR image) and the G panel
+// [16 k][256 columns] (16 KiB), in a ring of three 24 KiB buffers with the K loop's barrier argument: during stage
+// t a wave issues the 8 MFMAs of c = 0, stores stage t + 2 (in registers since stage t - 1), reads its c = 1
+// fragments, passes the barrier, issues the loads of stage t + 3 and then the 8 MFMAs of c = 1.  The stage index
+// runs through both passes, so pass 1's first panels are loaded and stored before pass 0's quotient and x_new
+// drains under pass 1's MFMAs.  Loads past the last stage re-read it into a buffer nobody reads (no branches).
+// Each x element is staged once, G once per pass (it stays in L2).
+template <class E, class = void>
+struct epi_den_tail { static constexpr bool value = false; };
+template <class E>
+struct epi_den_tail<E, decltype((void)E::kDenTail)> { static constexpr bool value = E::kDenTail; };
+
+typedef float x6_f32x2 __attribute__((ext_vector_type(2)));
+
+// float offset of 16-byte chunk q (4 k) of row r in the tail's x panel
+__device__ __forceinline__ int x6_den_xoff(int r, int q) { return r * 16 + ((q ^ ((r >> 2) & 3)) << 2); }
+
+template <class Epi>
+__device__ __forceinline__ void x6_den_tail(f32x16 (&num)[2][2], const Epi& epi, char* smem, int m0, int n0, int tid) {
+    constexpr int XS = 128 * 16 * 4;     // x panel of one stage, bytes
+    constexpr int GS = 16 * 256 * 4;     // G panel
+    constexpr int DBUF = XS + GS;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 2, wn = wave & 3;
+    const int l31 = lane & 31, h = lane >> 5;
+    const int nkd = epi.depth >> 4;      // K blocks per pass; stages 0 .. 2 nkd - 1
+
+    // staging: a thread moves 8 bytes of the x panel (row pr = 32 wm' + r: tile row 64 wm' + 32 pass + r) and 16
+    // bytes of the G panel (a wave moves one k row of it)
+    const int pr = tid >> 3, k2 = tid & 7;
+    const float* xsrc = epi.cur + (long)(m0 + (pr >> 5) * 64 + (pr & 31)) * epi.ld_cur + 2 * k2;
+    const int xdst = (x6_den_xoff(pr, k2 >> 1) + 2 * (k2 & 1)) * 4;
+    const int gk = tid >> 6, gc = tid & 63;
+    const float* gsrc = epi.gram + (long)gk * epi.ld_gram + (n0 + 4 * gc);
+    const int gdst = XS + (gk * 256 + 4 * gc) * 4;
+    int lp = 0, lk = 0;                  // pass and K block of the next stage to load (stops at the last one)
+    auto gload = [&](x6_f32x2& rx, f32x4& rg) {
+        rx = *reinterpret_cast<const x6_f32x2*>(xsrc + (long)(32 * lp) * epi.ld_cur + 16 * lk);
+        rg = *reinterpret_cast<const f32x4*>(gsrc + (long)(16 * lk) * epi.ld_gram);
+        if (lk + 1 < nkd) {
+            ++lk;
+        } else if (lp == 0) {
+            lp = 1;
+            lk = 0;
+        }
+    };
+    auto lstore = [&](int buf, const x6_f32x2& rx, const f32x4& rg) {
+        *reinterpret_cast<x6_f32x2*>(smem + buf + xdst) = rx;
+        *reinterpret_cast<f32x4*>(smem + buf + gdst) = rg;
+    };
+
+    x6_f32x2 rx;
+    f32x4 rg;
+    int b0 = 0, b1 = DBUF, b2 = 2 * DBUF;   // byte offsets of the buffers of stages t, t + 1, t + 2
+    {
+        x6_f32x2 rx0, rx1;
+        f32x4 rg0, rg1;
+        gload(rx0, rg0);
+        gload(rx1, rg1);
+        gload(rx, rg);
+        __syncthreads();   // every wave has left the K loop: the ring is free
+        lstore(b0, rx0, rg0);
+        lstore(b1, rx1, rg1);
+        __syncthreads();
+    }
+
+    // fragment addresses inside a stage buffer: x row 32 wm + l31, chunk 2c + h; G rows 8c + 4h + s, the lane's column
+    const int xfrag0 = x6_den_xoff(wm * 32 + l31, h) * 4, xfrag1 = x6_den_xoff(wm * 32 + l31, 2 + h) * 4;
+    const int gfrag = XS + ((4 * h) * 256 + wn * 64 + l31) * 4;
+    const int tq = l31 & 3, col0 = l31 & ~3;
+
+    auto pass = [&](auto i_tag) {
+        constexpr int i = decltype(i_tag)::value;
+        f32x16 den[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) den[j][r] = 0.0f;
+        for (int kb = 0; kb < nkd; ++kb) {
+            const char* s = smem + b0;
+            auto frags = [&](int xoff, int c, f32x4& fa, f32x4 (&fb)[2]) {
+                fa = *reinterpret_cast<const f32x4*>(s + xoff);
+                const float* g = reinterpret_cast<const float*>(s + gfrag) + c * 8 * 256;
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int st = 0; st < 4; ++st) fb[j][st] = g[st * 256 + j * 32];
+            };
+            auto mfmas = [&](const f32x4& fa, const f32x4 (&fb)[2]) {
+#pragma unroll
+                for (int st = 0; st < 4; ++st)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        den[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[st], fb[j][st], den[j], 0, 0, 0);
+            };
+            f32x4 fa, fb[2];
+            frags(xfrag0, 0, fa, fb);
+            mfmas(fa, fb);
+            __builtin_amdgcn_sched_barrier(0);
+            lstore(b2, rx, rg);
+            f32x4 ga, gb[2];
+            frags(xfrag1, 1, ga, gb);
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+            __builtin_amdgcn_sched_barrier(0);
+            gload(rx, rg);
+            mfmas(ga, gb);
+            __builtin_amdgcn_sched_barrier(0);
+            const int t0 = b0;
+            b0 = b1;
+            b1 = b2;
+            b2 = t0;
+        }
+        // quotient of this pass's 128 rows: 4 x 4 transposes inside the lane quads, 16 bytes per lane
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 a, d;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    a[e] = num[i][j][4 * g + e];
+                    d[e] = den[j][4 * g + e];
+                }
+                epi.quot4(m0 + wm * 64 + i * 32 + 8 * g + 4 * h + tq, n0 + wn * 64 + j * 32 + col0,
+                          quad_transpose(a, tq), quad_transpose(d, tq));
+            }
+    };
+    pass(std::integral_constant<int, 0>{});
+    pass(std::integral_constant<int, 1>{});
 }
 
 template <class Cfg, int ALAY, int BLAY, class Epi>
@@ -350,7 +503,12 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
 
     // ---- epilogue: the 32x32x16 bf16 MFMA has the C layout of the fp32 one:
     //      col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----
-    if constexpr (epi_vec4<Epi>::value) {
+    if constexpr (epi_den_tail<Epi>::value) {
+        // acc is the quotient's numerator; the denominator is formed here (x6_den_tail), unsplit products only
+        static_assert(BM == 256 && BN == 256 && NT == 1024 && STAGES == 3 && ALAY == KMAJOR && BLAY == KMAJOR,
+                      "the denominator tail is laid out for the 256 x 256 NT tile");
+        x6_den_tail(acc, epi, x6_smem, m0, n0, tid);
+    } else if constexpr (epi_vec4<Epi>::value) {
         // functors with a 16-byte form always use it here (x6_epi_ok): the per-element form of a loading
         // epilogue (EpiMuNum) would be compiled beside it and spill at four waves per SIMD
         const int tq = l31 & 3, col0 = (l31 & ~3);
@@ -406,6 +564,12 @@ inline bool x6_eligible(const GemmProblem& p) {
 template <class Cfg, int ALAY, int BLAY, class Epi>
 inline hipError_t launch_gemm_bf16x6(hipStream_t stream, GemmProblem p, const Epi& epi) {
     if (!x6_eligible<Cfg>(p) || !x6_epi_ok(epi)) return hipErrorInvalidValue;
+    if constexpr (epi_den_tail<Epi>::value) {
+        // the tail takes the whole numerator: one split, one B segment; whole 16-deep K blocks of x.G.  The tail's
+        // clamped loads would work from one K block per pass upward; 48 keeps the three stages of its prologue
+        // distinct, which is all that has been tested (the NMF dispatch only sends multiples of 256)
+        if (p.ksplits > 1 || p.B2 != nullptr || epi.depth < 48 || (epi.depth % 16) != 0) return hipErrorInvalidValue;
+    }
     if (p.B2 == nullptr) p.n_b1 = p.N;
     p.m_a1 = p.M;
     p.tiles_m1 = p.tiles_m = p.M / Cfg::BM;

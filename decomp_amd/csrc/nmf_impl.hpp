@@ -261,6 +261,19 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
     GemmArgs<T> pg_probe;
     const bool split_gram = gram && std::is_same<T, float>::value && Xout != Xin &&
                             nmf_xupdate_splits<T>(s.N, s.F, s.K, pg_probe) > 1;
+    // Enough 256 x 256 tiles for an unsplit Y.D^T on the split-bf16 core (float32, out of place): that launch
+    // forms x.G itself after its K loop, on the fp32 MFMA and in the stand-alone product's order, and applies the
+    // quotient (EpiMuGramDen); Q is neither written nor read.  Not in place: a workgroup reads whole rows of x
+    // while the workgroups of the other column tiles write them.
+    bool fused_den = false;
+    if constexpr (std::is_same<T, float>::value) {
+        if (gram && h->f32_product_mode == 0 && Xout != Xin) {
+            GemmArgs<T> fg;
+            fg.A = Ypre; fg.lda = F; fg.B = D; fg.ldb = F;
+            fused_den = nmf_xupdate_splits<T>(s.N, s.F, s.K, fg) <= 1 && x6_tier<FORM_NT>(fg) == X6_HUGE &&
+                        EpiMuGramDen<false>{Xin, K, w.G, K, K, Xout, K}.vec_ok();
+        }
+    }
     if (gram) {
         {   // G = D D^T  (split over F, partial slabs summed in order)
             ProfScope ps(h, DCP_PROF_GRAM);
@@ -272,7 +285,7 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
             launch_reduce_slabs_scalar<T>(st, w.slabs, (long)K * K, g.ksplits, (long)K * K, w.G);
             DCP_LAUNCH_OK(h, hipGetLastError());
         }
-        if (!split_gram) {   // Q = x G
+        if (!split_gram && !fused_den) {   // Q = x G
             ProfScope ps(h, DCP_PROF_XNEG);
             GemmArgs<T> q;
             q.A = Xin; q.lda = K; q.B = w.G; q.ldb = K; q.M = N; q.N = K; q.K = K;
@@ -318,7 +331,17 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
         GemmArgs<T> pg;
         pg.A = xnum_A; pg.lda = F; pg.B = D; pg.ldb = F; pg.M = N; pg.N = K; pg.K = F;
         const int psplits = nmf_xupdate_splits<T>(s.N, s.F, s.K, pg);
-        if (psplits <= 1) {
+        if (fused_den) {
+            if constexpr (std::is_same<T, float>::value) {
+                const GemmProblem fp = x6_problem<FORM_NT>(pg);
+                if (pen.on())
+                    DCP_LAUNCH_OK(h, (launch_gemm_bf16x6<X6Huge, KMAJOR, KMAJOR>(
+                                         st, fp, EpiMuGramDen<true>{Xin, K, w.G, K, K, Xout, K, l1, l2})));
+                else
+                    DCP_LAUNCH_OK(h, (launch_gemm_bf16x6<X6Huge, KMAJOR, KMAJOR>(
+                                         st, fp, EpiMuGramDen<false>{Xin, K, w.G, K, K, Xout, K})));
+            }
+        } else if (psplits <= 1) {
             // enough row tiles to fill the chip: quotient fused into the GEMM epilogue
             pg.ksplits = 1;
             const EpiMuNum<T> num{Xin, K, xden, ld_xden, Xout, K};
