@@ -150,6 +150,8 @@ SIGNATURES = {
     'dcp_inv_c64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
     'dcp_inv_c128': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
     'dcp_debug_tn_plain': (_c_int, [_c_int]),
+    'dcp_debug_gemm_route': (_c_int, [_c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int,
+                                      _c_int, _c_vp]),
     'dcp_gemm_bf16x6_f32': (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int]),
     'dcp_set_f32_product_mode': (_c_int, [_c_vp, _c_int]),
     'dcp_calib_read_f32': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp]),

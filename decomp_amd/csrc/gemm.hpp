@@ -1,8 +1,9 @@
-// One GEMM front end for every dtype: float and complex64 go to the fp32 MFMA core
-// (gemm_mfma_f32.hpp), double and complex128 to the fp64 MFMA core (gemm_mfma_f64.hpp) when the
-// output is at least 128 x 128; what is left (thin fp64 / complex128 outputs, complex products
-// without an extended-operand scratch) runs on the generic LDS-tiled VALU core (gemm_generic.hpp).  Epilogue functors (below) fuse the per-element update rules
-// of the solvers into the GEMM that produces their last operand.
+// One GEMM front end for every dtype.  gemm_route() decides once, on the host, which core runs a
+// product (fp32 MFMA, gemm_mfma_f32.hpp; fp64 MFMA, gemm_mfma_f64.hpp; generic LDS-tiled VALU,
+// gemm_generic.hpp), under which real image a complex product runs, the dimensions the core sees
+// and the tile that is launched.  gemm() launches what the route says, plan_splits() counts tiles
+// by it.  Epilogue functors (below) fuse the per-element update rules of the solvers into the GEMM
+// that produces their last operand.
 #pragma once
 #include <type_traits>
 
@@ -138,12 +139,6 @@ struct CplxNnEpi {    // kernel epilogue mode 3
     __device__ __forceinline__ void operator()(int, int, R, int) const {}
 };
 
-// complex64 NN products whose left operand is the smaller one take the planar-rows form
-template <int FORM>
-inline bool cplx_planar_a(int M, int N, bool conjA, bool conjB, const void* ext_ws) {
-    return FORM == FORM_NN && !conjA && !conjB && ext_ws != nullptr && M < N;
-}
-
 template <int FORM>
 inline bool cplx_on_mfma(bool conjA, bool conjB, const void* ext_ws) {
     if (FORM == FORM_TN) return conjA && !conjB;
@@ -175,14 +170,6 @@ typedef TileCfg<64, 64, 64, 32, 32, 1> CfgSmallDeep;   // 64 KiB LDS: latency-bo
 enum Tier { TIER_SMALL = 0, TIER_LARGE = 1, TIER_HUGE = 2, TIER_FLAT = 3, TIER_MID = 4, TIER_SMALL_DEEP = 5, TIER_TALL = 6, TIER_HUGE_DEEP = 7 };
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
-
-inline void tier_dims(int tier, int& bm, int& bn) {
-    if (tier == TIER_HUGE || tier == TIER_HUGE_DEEP) { bm = CfgHuge::BM; bn = CfgHuge::BN; }
-    else if (tier == TIER_LARGE || tier == TIER_MID) { bm = CfgLarge::BM; bn = CfgLarge::BN; }
-    else if (tier == TIER_FLAT) { bm = CfgFlat::BM; bn = CfgFlat::BN; }
-    else if (tier == TIER_TALL) { bm = CfgTall::BM; bn = CfgTall::BN; }
-    else { bm = 64; bn = 64; }
-}
 
 // The tile tier the float path uses for this problem (split-K planning needs it before the
 // launch): the largest tile that still gives the chip enough workgroups, counting the splits
@@ -259,65 +246,178 @@ inline int f64_tier(int M, int N, int tile_sel, int K = 1 << 30) {
     if (M > 32 && N > 32) return F64_SQ64;   // (33..64) x (33..64 or 65..127 handled above): small square outputs
     return F64_GENERIC;
 }
-inline bool f64_tier_dims(int tier, int& bm, int& bn) {
-    switch (tier) {
-        case F64_128: bm = 128; bn = 128; return true;
-        case F64_TALL64: bm = 128; bn = 64; return true;
-        case F64_TALL32: bm = 128; bn = 32; return true;
-        case F64_FLAT64: bm = 64; bn = 128; return true;
-        case F64_FLAT32: bm = 32; bn = 128; return true;
-        case F64_SQ64: bm = 64; bn = 64; return true;
-        default: return false;
+
+// A/B knob of the pair schedule (TileCfg PIPE = 3): -1 = not yet read, 0 = pair schedule, 1 = plain schedule.
+// Read ONCE from DCP_TN_PLAIN; dcp_debug_tn_plain() (test hook) overrides it so that one process can run both.
+inline std::atomic<int>& tn_plain_flag() {
+    static std::atomic<int> flag{-1};
+    return flag;
+}
+inline bool tn_plain_schedule() {
+    int v = tn_plain_flag().load(std::memory_order_relaxed);
+    if (v < 0) {
+        v = getenv("DCP_TN_PLAIN") != nullptr ? 1 : 0;
+        tn_plain_flag().store(v, std::memory_order_relaxed);
+    }
+    return v != 0;
+}
+
+// ------------------------------------------------------------------ the route ----
+// Every decision of the front end about one product, made once by gemm_route(): pure host arithmetic (no HIP call;
+// the only global state read is tn_plain_schedule()).  gemm() launches by it, plan_splits() counts tiles by it, the
+// solvers and the test hooks ask it instead of guessing.
+enum GemmCore { CORE_F32 = 0, CORE_F64 = 1, CORE_GENERIC = 2 };
+// real image of a complex product = the kernels' epilogue mode (see CplxColEpi / CplxTnEpi / CplxNnEpi)
+enum CplxImage { IMG_NONE = 0, IMG_EXT_B = 1, IMG_TN_VIEWS = 2, IMG_ROWS_A = 3 };
+// launched fp32 tiles: a Tier, or one of the two pair-schedule tiles
+enum { TIER_LARGE_X = 8, TIER_HUGE_DEEP_X = 9 };
+
+struct TileDims { int id, BM, BN, BK, WM, WN, PIPE; };
+template <class Cfg>
+constexpr TileDims tile_of(int id, int pipe = 0) { return {id, Cfg::BM, Cfg::BN, Cfg::BK, Cfg::WM, Cfg::WN, pipe}; }
+
+struct GemmRoute {
+    int core = CORE_GENERIC;
+    // A thin complex128 product keeps its image here although the generic core builds none: callers that re-use
+    // or size by the image (lasso's ext_ready, the dcp_gemm_* hook) asked by shape alone before: kept.
+    int image = IMG_NONE;
+    int img_rows = 0, img_cols = 0;   // the complex matrix that is imaged (B for EXT_B, A for ROWS_A)
+    int M = 0, N = 0, K = 0, n1 = 0;  // the product as the launched core sees it; n1: columns of the first B segment
+    int klen = 0, ksplits = 1;        // as the launched core receives them
+    // PLANNING: the picked tier (a Tier on the fp32 core, an F64Tier otherwise) and what plan_splits counts by.  Where
+    // `tile` differs, plan and launch differed before the route; ksplits, so the bits, hangs on the plan: kept.
+    int tier = -1;
+    int plan_M = 0, plan_N = 0, plan_n1 = 0, plan_bm = 64, plan_bn = 64;
+    int kunit = 1;   // K blocks of 16 per K block of the planned tile (splits are whole tile blocks)
+    // LAUNCH: the tile that runs (id: a Tier or TIER_*_X on the fp32 core, an F64Tier on the fp64 core)
+    TileDims tile = {-1, 64, 64, 16, 0, 0, 0};   // (the generic core's)
+    void plan_by(TileDims t) { plan_bm = t.BM; plan_bn = t.BN; }
+};
+
+inline TileDims f32_tile(int id) {
+    switch (id) {
+        case TIER_SMALL: return tile_of<CfgSmall>(id);
+        case TIER_SMALL_DEEP: return tile_of<CfgSmallDeep>(id);
+        case TIER_LARGE_X: return tile_of<CfgLargeX>(id, CfgLargeX::PIPE);
+        case TIER_MID: return tile_of<CfgMid>(id);
+        case TIER_HUGE: return tile_of<CfgHuge>(id);
+        case TIER_HUGE_DEEP: return tile_of<CfgHugeDeep>(id);
+        case TIER_HUGE_DEEP_X: return tile_of<CfgHugeDeepX>(id, CfgHugeDeepX::PIPE);
+        case TIER_FLAT: return tile_of<CfgFlat>(id);
+        case TIER_TALL: return tile_of<CfgTall>(id);
+        default: return tile_of<CfgLarge>(TIER_LARGE);
+    }
+}
+inline TileDims f64_tile(int id) {
+    switch (id) {
+        case F64_TALL64: return tile_of<F64Tall64>(id);
+        case F64_TALL32: return tile_of<F64Tall32>(id);
+        case F64_FLAT64: return tile_of<F64Flat64>(id);
+        case F64_FLAT32: return tile_of<F64Flat32>(id);
+        case F64_SQ64: return tile_of<F64Sq64>(id);
+        default: return tile_of<F64Tile>(F64_128);
     }
 }
 
-template <int AL, int BL, class Epi>
-inline hipError_t launch_f64_tier(int tier, hipStream_t stream, const GemmProblemD& p, const Epi& epi) {
-    if (tier == F64_TALL64) return launch_gemm_mfma_f64_cfg<F64Tall64, AL, BL, Epi>(stream, p, epi);
-    if (tier == F64_TALL32) return launch_gemm_mfma_f64_cfg<F64Tall32, AL, BL, Epi>(stream, p, epi);
-    if (tier == F64_FLAT64) return launch_gemm_mfma_f64_cfg<F64Flat64, AL, BL, Epi>(stream, p, epi);
-    if (tier == F64_FLAT32) return launch_gemm_mfma_f64_cfg<F64Flat32, AL, BL, Epi>(stream, p, epi);
-    if (tier == F64_SQ64) return launch_gemm_mfma_f64_cfg<F64Sq64, AL, BL, Epi>(stream, p, epi);
-    return launch_gemm_mfma_f64<AL, BL, Epi>(stream, p, epi);
+template <int FORM, class T>
+inline GemmRoute gemm_route(const GemmArgs<T>& a) {
+    constexpr bool f32 = std::is_same<real_t<T>, float>::value;
+    GemmRoute r;
+    r.M = r.plan_M = a.M; r.N = r.plan_N = a.N; r.K = a.K;
+    r.n1 = r.plan_n1 = a.B2 != nullptr ? a.n_b1 : a.N;
+    r.klen = a.klen; r.ksplits = a.ksplits;
+    if constexpr (scalar_traits<T>::is_complex) {
+        if (!cplx_on_mfma<FORM>(a.conjA, a.conjB, a.ext_ws)) return r;
+        bool rows = FORM == FORM_NN && a.M < a.N;   // the left operand is the smaller one: planar rows of A
+        int t_ext = F64_GENERIC;
+        if constexpr (!f32) {   // (complex128 asks f64_tier without K, float64 below with it)
+            const int t_rows = f64_tier(2 * a.M, 2 * a.N, a.tile);
+            rows = rows && t_rows != F64_GENERIC;
+            t_ext = f64_tier(FORM == FORM_TN ? 2 * a.M : a.M, 2 * a.N, a.tile);
+            r.tier = rows ? t_rows : t_ext;
+        }
+        r.image = FORM == FORM_TN ? IMG_TN_VIEWS : rows ? IMG_ROWS_A : IMG_EXT_B;
+        if (!f32 && r.tier == F64_GENERIC) return r;
+        // the real-extended product: N doubles; M under the TN views and rows(A), K under ext(B)
+        r.plan_N = 2 * a.N;
+        r.plan_n1 *= 2;
+        if (r.image != IMG_EXT_B) r.plan_M = 2 * a.M;
+        if constexpr (!f32) {
+            r.plan_by(f64_tile(r.tier));
+            // PLAN AND LAUNCH DISAGREE (kept): the plan counts tiles of the rows(A) product, but the launch asks
+            // the ext(B) tier first and runs a thin output (30 x 50 NN) on the generic core, as the caller gave it
+            if (t_ext == F64_GENERIC) return r;
+            r.core = CORE_F64;
+            r.tile = f64_tile(r.tier);
+        }
+        r.M = r.plan_M; r.N = r.plan_N;
+        if (r.image == IMG_EXT_B) r.K = 2 * a.K;
+        // the ext(B) and rows(A) launches take B as ONE segment (a second one is counted by the plan and then
+        // dropped: kept), and an un-split reduction leaves its length to the launcher
+        r.n1 = r.plan_n1;
+        if (r.image != IMG_TN_VIEWS) {
+            r.n1 = r.N;
+            if (a.ksplits <= 1) r.klen = 0;
+            const bool ext = r.image == IMG_EXT_B;
+            r.img_rows = !ext ? a.M : FORM == FORM_NT ? a.N : a.K;
+            r.img_cols = (!ext || FORM == FORM_NT) ? a.K : a.N;
+        }
+        if constexpr (f32) {
+            r.core = CORE_F32;
+            r.tier = pick_tier<FORM>(r.M, r.N, r.K, a.tile, a.split_planned);   // (real32 = false: kept)
+            r.plan_by(f32_tile(r.tier));
+            // PLAN AND LAUNCH DISAGREE (kept): complex64 launches fewer tiles than it plans by.  The 32-wide and
+            // deep 64 x 64 tiers collapse to 64 x 64 (rows(A) keeps the deep one); TN runs nothing above 128 x 128,
+            // rows(A) neither, ext(B) keeps 256 x 256 and the 8-wave tile (whose 64-deep K blocks the plan's
+            // kunit = 1 ignores)
+            const int t = r.tier;
+            const bool small = t == TIER_SMALL || t == TIER_FLAT || t == TIER_TALL ||
+                               (t == TIER_SMALL_DEEP && r.image != IMG_ROWS_A);
+            if (small) r.tile = f32_tile(TIER_SMALL);
+            else if (t == TIER_SMALL_DEEP || (r.image == IMG_EXT_B && (t == TIER_HUGE || t == TIER_MID))) r.tile = f32_tile(t);
+            else r.tile = f32_tile((r.image == IMG_TN_VIEWS && !tn_plain_schedule()) ? TIER_LARGE_X : TIER_LARGE);
+        }
+    } else if constexpr (f32) {
+        r.core = CORE_F32;
+        r.tier = pick_tier<FORM>(a.M, a.N, a.K, a.tile, a.split_planned, true);
+        r.plan_by(f32_tile(r.tier));
+        if (r.tier == TIER_HUGE_DEEP) r.kunit = CfgHugeDeep::BK / 16;
+        if (r.tier == TIER_MID) r.kunit = CfgMid::BK / 16;
+        int t = r.tier;
+        if (t == TIER_SMALL && a.tile == TILE_AUTO) {
+            // at most one workgroup per CU: occupancy is moot and the product is a chain of
+            // load -> LDS -> MFMA round trips, one per K block; 64-deep blocks make 4x fewer of them
+            // (small problems: Y.D^T 2048 x 32 x 512 31 -> 10 us).  Same summation order.
+            const long wgs = (long)ceil_div(a.M, 64) * ceil_div(a.N, 64) * (a.ksplits > 1 ? a.ksplits : 1);
+            const int depth = a.ksplits > 1 ? a.klen : a.K;
+            if (wgs <= 256 && depth >= 256 && depth % 64 == 0 && a.K % 64 == 0) t = TIER_SMALL_DEEP;
+        }
+        // reduction over samples, both panels row-contiguous: the pair schedule (DCP_TN_PLAIN=1: A/B knob)
+        if (FORM == FORM_TN && !tn_plain_schedule()) {
+            if (t == TIER_HUGE_DEEP) t = TIER_HUGE_DEEP_X;
+            if (t == TIER_LARGE) t = TIER_LARGE_X;
+        }
+        r.tile = f32_tile(t);
+    } else {
+        r.tier = f64_tier(a.M, a.N, a.tile, a.K);
+        if (r.tier != F64_GENERIC) {
+            r.core = CORE_F64;
+            r.plan_by(r.tile = f64_tile(r.tier));
+        }
+    }
+    return r;
 }
 
 // Choose split-K so that the grid reaches ~target workgroups, each split a multiple
 // of 16 deep (the MFMA K block).  Returns the number of splits; sets a.klen.
 template <int FORM, class T>
 inline int plan_splits(GemmArgs<T>& a, int target_wgs, int max_splits, int min_blocks = 32) {
-    int bm = 64, bn = 64;
     a.split_planned = true;
-    // problem dims as the MFMA core sees them (complex64: real-extended)
-    int Mx = a.M, Nx = a.N, Kx = a.K, n1 = a.B2 != nullptr ? a.n_b1 : a.N;
-    bool mfma = std::is_same<T, float>::value;
-    if (std::is_same<T, c64>::value && cplx_on_mfma<FORM>(a.conjA, a.conjB, a.ext_ws)) {
-        mfma = true;
-        Nx *= 2; n1 *= 2;
-        if (FORM == FORM_TN || cplx_planar_a<FORM>(a.M, a.N, a.conjA, a.conjB, a.ext_ws)) Mx *= 2;
-        else Kx *= 2;
-    }
-    int kunit = 1;   // K blocks of 16 per K block of the tile that will run (splits are whole tile blocks)
-    if (mfma) {
-        const int tier = pick_tier<FORM>(Mx, Nx, Kx, a.tile, true, std::is_same<T, float>::value);
-        tier_dims(tier, bm, bn);
-        if (std::is_same<T, float>::value) {
-            if (tier == TIER_HUGE_DEEP) kunit = CfgHugeDeep::BK / 16;
-            if (tier == TIER_MID) kunit = CfgMid::BK / 16;
-        }
-    }
+    // the product, the planned tile and the K granularity as the route has them (r.tier, not r.tile: see GemmRoute)
+    const GemmRoute r = gemm_route<FORM>(a);
+    const bool mfma = r.core == CORE_F32;
+    const int Mx = r.plan_M, Nx = r.plan_N, Kx = r.K, n1 = r.plan_n1, bm = r.plan_bm, bn = r.plan_bn, kunit = r.kunit;
     if (mfma && FORM == FORM_TN && bm == CfgHuge::BM && target_wgs > 256) target_wgs = 256;   // one 16-wave tile per CU
-    if (std::is_same<T, double>::value) (void)f64_tier_dims(f64_tier(a.M, a.N, a.tile, a.K), bm, bn);
-    if (std::is_same<T, c128>::value && cplx_on_mfma<FORM>(a.conjA, a.conjB, a.ext_ws)) {
-        const int Me = (FORM == FORM_TN) ? 2 * a.M : a.M;
-        int tbm = 0, tbn = 0;
-        const bool planar = cplx_planar_a<FORM>(a.M, a.N, a.conjA, a.conjB, a.ext_ws) &&
-                            f64_tier(2 * a.M, 2 * a.N, a.tile) != F64_GENERIC;
-        if (f64_tier_dims(f64_tier(planar ? 2 * a.M : Me, 2 * a.N, a.tile), tbm, tbn)) {   // fp64 MFMA core
-            Mx = planar ? 2 * a.M : Me; Nx = 2 * a.N; n1 *= 2;
-            if (FORM != FORM_TN && !planar) Kx *= 2;
-            bm = tbm; bn = tbn;
-        }
-    }
     const long tiles = (long)ceil_div(Mx, bm) * (ceil_div(n1, bn) + ceil_div(Nx - n1, bn));
     const long kblocks = ceil_div(Kx > 0 ? Kx : 1, 16);   // (real-extended depth for complex64)
     // splits allowed by the reduction depth: keep every split at least 512 deep (32 K blocks)
@@ -375,214 +475,128 @@ inline int plan_deep_nt(GemmArgs<T>& a, int max_s) {
     return a.ksplits;
 }
 
-// A/B knob of the pair schedule (TileCfg PIPE = 3): -1 = not yet read, 0 = pair schedule, 1 = plain schedule.
-// Read ONCE from DCP_TN_PLAIN; dcp_debug_tn_plain() (test hook) overrides it so that one process can run both.
-inline std::atomic<int>& tn_plain_flag() {
-    static std::atomic<int> flag{-1};
-    return flag;
+// The kernel-argument struct of the MFMA core a route names (GemmProblem / GemmProblemD), filled from the caller's
+// arguments and the route.  Complex operands enter as real views (two reals per element) unless the route puts an
+// image in their place: `image` is what launch_cplx_image() returned.
+template <int FORM, class T>
+inline auto fill_problem(const GemmArgs<T>& a, const GemmRoute& r, const real_t<T>* image = nullptr) {
+    typedef real_t<T> R;
+    constexpr int w = scalar_traits<T>::is_complex ? 2 : 1;
+    typename std::conditional<std::is_same<R, float>::value, GemmProblem, GemmProblemD>::type p;
+    p.A = reinterpret_cast<const R*>(a.A); p.lda = w * a.lda;
+    p.B = reinterpret_cast<const R*>(a.B); p.ldb = w * a.ldb;
+    p.B2 = reinterpret_cast<const R*>(a.B2); p.ldb2 = w * a.ldb2;
+    if constexpr (std::is_same<T, float>::value) { p.A2 = a.A2; p.lda2 = a.lda2; p.m_a1 = a.m_a1; }
+    if (r.image == IMG_ROWS_A) { p.A = image; p.lda = a.A_rows != nullptr ? a.lda_rows : r.img_cols; }
+    if (r.image == IMG_EXT_B) { p.B = image; p.ldb = 2 * r.img_cols; }
+    if (r.image == IMG_ROWS_A || r.image == IMG_EXT_B) { p.B2 = nullptr; p.ldb2 = 0; }
+    p.M = r.M; p.N = r.N; p.K = r.K; p.n_b1 = r.n1;
+    p.ksplits = r.ksplits; p.klen = r.klen;
+    p.tiles_m = p.tiles_n = 0;
+    // NT walks n tiles first (they share the A row panel); TN/NN walk m first.
+    p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
+    return p;
 }
-inline bool tn_plain_schedule() {
-    int v = tn_plain_flag().load(std::memory_order_relaxed);
-    if (v < 0) {
-        v = getenv("DCP_TN_PLAIN") != nullptr ? 1 : 0;
-        tn_plain_flag().store(v, std::memory_order_relaxed);
+template <int FORM, class T>
+inline auto fill_problem(const GemmArgs<T>& a) {
+    return fill_problem<FORM>(a, gemm_route<FORM>(a));
+}
+
+// Builds the real image the route asks for in the caller's scratch (ext(B): [2 rows, 2 cols] reals; rows(A):
+// [2M, K] reals, 2MK <= 4KN) and returns it; the caller's own rows(A), or an ext(B) it declared ready, is taken
+// as it is.  Null when the product needs none.
+template <class T>
+inline const real_t<T>* launch_cplx_image(hipStream_t stream, const GemmArgs<T>& a, const GemmRoute& r) {
+    typedef real_t<T> R;
+    if (r.image != IMG_ROWS_A && r.image != IMG_EXT_B) return nullptr;
+    if (r.image == IMG_ROWS_A && a.A_rows != nullptr) return a.A_rows;
+    long g = ((long)r.img_rows * r.img_cols + 255) / 256;
+    g = g > 4096 ? 4096 : g < 1 ? 1 : g;
+    if (r.image == IMG_ROWS_A)
+        hipLaunchKernelGGL((cplx_rows_kernel<R>), dim3((unsigned)g), dim3(256), 0, stream, a.A, (long)r.img_rows,
+                           (long)r.img_cols, a.lda, a.ext_ws);
+    else if (!a.ext_ready)
+        hipLaunchKernelGGL((cplx_ext_kernel<R>), dim3((unsigned)g), dim3(256), 0, stream, a.B, (long)r.img_rows,
+                           (long)r.img_cols, a.ldb, a.ext_ws);
+    return a.ext_ws;
+}
+
+// The one switch over the launched tile, per core.  The `if constexpr` guards name the tiles a form / image can
+// be routed to (gemm_route), so that no other kernel is instantiated.
+template <int FORM, int IMAGE, class Epi>
+inline hipError_t launch_tile(const GemmRoute& r, hipStream_t stream, const GemmProblem& p, const Epi& epi) {
+    constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
+    constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
+    constexpr bool real = IMAGE == IMG_NONE, pair = FORM == FORM_TN, deep64 = real || IMAGE == IMG_ROWS_A;
+    constexpr bool big = FORM != FORM_TN && (real || IMAGE == IMG_EXT_B);
+    switch (r.tile.id) {
+        case TIER_SMALL: return launch_gemm_mfma<CfgSmall, AL, BL, Epi>(stream, p, epi);
+        case TIER_LARGE: return launch_gemm_mfma<CfgLarge, AL, BL, Epi>(stream, p, epi);
+        case TIER_SMALL_DEEP:
+            if constexpr (deep64) return launch_gemm_mfma<CfgSmallDeep, AL, BL, Epi>(stream, p, epi); else break;
+        case TIER_LARGE_X:
+            if constexpr (pair) return launch_gemm_mfma<CfgLargeX, AL, BL, Epi>(stream, p, epi); else break;
+        case TIER_HUGE_DEEP_X:
+            if constexpr (pair && real) return launch_gemm_mfma<CfgHugeDeepX, AL, BL, Epi>(stream, p, epi); else break;
+        case TIER_HUGE_DEEP:
+            if constexpr (real) return launch_gemm_mfma<CfgHugeDeep, AL, BL, Epi>(stream, p, epi); else break;
+        case TIER_FLAT:
+            if constexpr (real) return launch_gemm_mfma<CfgFlat, AL, BL, Epi>(stream, p, epi); else break;
+        case TIER_TALL:
+            if constexpr (real) return launch_gemm_mfma<CfgTall, AL, BL, Epi>(stream, p, epi); else break;
+        case TIER_HUGE:
+            if constexpr (big) return launch_gemm_mfma<CfgHuge, AL, BL, Epi>(stream, p, epi); else break;
+        case TIER_MID:
+            if constexpr (big) return launch_gemm_mfma<CfgMid, AL, BL, Epi>(stream, p, epi); else break;
     }
-    return v != 0;
+    return hipErrorInvalidValue;   // (a tile the route never names for this form / image)
+}
+template <int FORM, int IMAGE, class Epi>
+inline hipError_t launch_tile(const GemmRoute& r, hipStream_t stream, const GemmProblemD& p, const Epi& epi) {
+    constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
+    constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
+    switch (r.tile.id) {
+        case F64_TALL64: return launch_gemm_mfma_f64_cfg<F64Tall64, AL, BL, Epi>(stream, p, epi);
+        case F64_TALL32: return launch_gemm_mfma_f64_cfg<F64Tall32, AL, BL, Epi>(stream, p, epi);
+        case F64_FLAT64: return launch_gemm_mfma_f64_cfg<F64Flat64, AL, BL, Epi>(stream, p, epi);
+        case F64_FLAT32: return launch_gemm_mfma_f64_cfg<F64Flat32, AL, BL, Epi>(stream, p, epi);
+        case F64_SQ64: return launch_gemm_mfma_f64_cfg<F64Sq64, AL, BL, Epi>(stream, p, epi);
+        default: return launch_gemm_mfma_f64<AL, BL, Epi>(stream, p, epi);
+    }
 }
 
 template <int FORM, class T, class Epi>
+inline hipError_t launch_generic(hipStream_t stream, const GemmArgs<T>& a, const GemmRoute& r, const Epi& epi) {
+    GenericProblem<T> p;
+    p.A = a.A; p.B = a.B; p.B2 = a.B2; p.n_b1 = a.n_b1;
+    if (FORM == FORM_TN) { p.sAm = 1; p.sAk = a.lda; } else { p.sAm = a.lda; p.sAk = 1; }
+    if (FORM == FORM_NT) { p.sBk = 1; p.sBn = a.ldb; p.sB2k = 1; p.sB2n = a.ldb2; }
+    else { p.sBk = a.ldb; p.sBn = 1; p.sB2k = a.ldb2; p.sB2n = 1; }
+    p.M = r.M; p.N = r.N; p.K = r.K;
+    p.ksplits = r.ksplits; p.klen = r.klen;
+    p.tiles_m = p.tiles_n = 0;
+    constexpr bool cplx = scalar_traits<T>::is_complex;
+    return launch_gemm_generic<T, Epi>(stream, p, cplx && a.conjA, cplx && a.conjB, epi);
+}
+
+// Take the route, build the image it asks for, launch its tile: every branch here tests a field of the route.
+template <int FORM, class T, class Epi>
 inline hipError_t gemm(hipStream_t stream, const GemmArgs<T>& a, const Epi& epi) {
-    if constexpr (std::is_same<T, float>::value) {
-        GemmProblem p;
-        p.A = a.A; p.lda = a.lda; p.B = a.B; p.ldb = a.ldb;
-        p.B2 = a.B2; p.ldb2 = a.ldb2; p.n_b1 = a.n_b1;
-        p.A2 = a.A2; p.lda2 = a.lda2; p.m_a1 = a.m_a1;
-        p.M = a.M; p.N = a.N; p.K = a.K;
-        p.ksplits = a.ksplits; p.klen = a.klen;
-        p.tiles_m = p.tiles_n = 0;
-        // NT walks n tiles first (they share the A row panel); TN/NN walk m first.
-        p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
-        constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
-        constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
-        int tier = pick_tier<FORM>(a.M, a.N, a.K, a.tile, a.split_planned, true);
-        if (tier == TIER_SMALL && a.tile == TILE_AUTO) {
-            // at most one workgroup per CU: occupancy is moot and the product is a chain of
-            // load -> LDS -> MFMA round trips, one per K block; 64-deep blocks make 4x fewer of them
-            // (small problems: Y.D^T 2048 x 32 x 512 31 -> 10 us).  Same summation order.
-            const long wgs = (long)ceil_div(a.M, 64) * ceil_div(a.N, 64) * (a.ksplits > 1 ? a.ksplits : 1);
-            const int depth = a.ksplits > 1 ? a.klen : a.K;
-            if (wgs <= 256 && depth >= 256 && depth % 64 == 0 && a.K % 64 == 0) tier = TIER_SMALL_DEEP;
-        }
-        if (tier == TIER_SMALL) return launch_gemm_mfma<CfgSmall, AL, BL, Epi>(stream, p, epi);
-        if (tier == TIER_SMALL_DEEP) return launch_gemm_mfma<CfgSmallDeep, AL, BL, Epi>(stream, p, epi);
-        if constexpr (FORM == FORM_TN && (epi_mode<Epi>::value == 0)) {
-            // reduction over samples, both panels row-contiguous: the pair schedule (DCP_TN_PLAIN=1: A/B knob)
-            if (!tn_plain_schedule()) {
-                if (tier == TIER_HUGE_DEEP) return launch_gemm_mfma<CfgHugeDeepX, AL, BL, Epi>(stream, p, epi);
-                if (tier == TIER_LARGE) return launch_gemm_mfma<CfgLargeX, AL, BL, Epi>(stream, p, epi);
-            }
-        }
-        if (tier == TIER_HUGE_DEEP) return launch_gemm_mfma<CfgHugeDeep, AL, BL, Epi>(stream, p, epi);
-        if (tier == TIER_FLAT) return launch_gemm_mfma<CfgFlat, AL, BL, Epi>(stream, p, epi);
-        if (tier == TIER_TALL) return launch_gemm_mfma<CfgTall, AL, BL, Epi>(stream, p, epi);
-        if constexpr (FORM != FORM_TN) {
-            if (tier == TIER_HUGE) return launch_gemm_mfma<CfgHuge, AL, BL, Epi>(stream, p, epi);
-            if (tier == TIER_MID) return launch_gemm_mfma<CfgMid, AL, BL, Epi>(stream, p, epi);
-        }
-        return launch_gemm_mfma<CfgLarge, AL, BL, Epi>(stream, p, epi);
+    typedef real_t<T> R;
+    const GemmRoute r = gemm_route<FORM>(a);
+    if constexpr (!std::is_same<T, float>::value) {   // (float32 is never routed to the generic core)
+        if (r.core == CORE_GENERIC) return launch_generic<FORM>(stream, a, r, epi);
+    }
+    if constexpr (!scalar_traits<T>::is_complex) {
+        return launch_tile<FORM, IMG_NONE>(r, stream, fill_problem<FORM>(a, r), epi);
     } else {
-        if constexpr (std::is_same<T, c64>::value) {
-            if (cplx_on_mfma<FORM>(a.conjA, a.conjB, a.ext_ws)) {
-                GemmProblem p;
-                const float* Ar = reinterpret_cast<const float*>(a.A);
-                p.A = Ar; p.lda = 2 * a.lda;
-                p.B2 = nullptr; p.ldb2 = 0; p.n_b1 = 2 * a.N;
-                p.ksplits = a.ksplits; p.klen = a.klen;
-                p.tiles_m = p.tiles_n = 0;
-                p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
-                constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
-                constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
-                if constexpr (FORM == FORM_TN) {
-                    p.B = reinterpret_cast<const float*>(a.B); p.ldb = 2 * a.ldb;
-                    if (a.B2 != nullptr) {
-                        p.B2 = reinterpret_cast<const float*>(a.B2); p.ldb2 = 2 * a.ldb2;
-                        p.n_b1 = 2 * a.n_b1;
-                    }
-                    p.M = 2 * a.M; p.N = 2 * a.N; p.K = a.K;
-                    CplxTnEpi<Epi> ce{epi};
-                    const int tier = pick_tier<FORM>(p.M, p.N, p.K, a.tile, a.split_planned);
-                    if (tier == TIER_SMALL || tier == TIER_SMALL_DEEP || tier == TIER_FLAT || tier == TIER_TALL)
-                        return launch_gemm_mfma<CfgSmall, AL, BL>(stream, p, ce);
-                    if (!tn_plain_schedule()) return launch_gemm_mfma<CfgLargeX, AL, BL>(stream, p, ce);
-                    return launch_gemm_mfma<CfgLarge, AL, BL>(stream, p, ce);
-                } else if (cplx_planar_a<FORM>(a.M, a.N, a.conjA, a.conjB, a.ext_ws)) {
-                    // rows(A): [2M, K] real image in the caller's scratch (2MK <= 4KN reals); B as it lies
-                    if (a.A_rows != nullptr) {
-                        p.A = a.A_rows; p.lda = a.lda_rows;
-                    } else {
-                        long g = ((long)a.M * a.K + 255) / 256;
-                        if (g > 4096) g = 4096;
-                        if (g < 1) g = 1;
-                        hipLaunchKernelGGL((cplx_rows_kernel<float>), dim3((unsigned)g), dim3(256), 0, stream, a.A,
-                                           (long)a.M, (long)a.K, a.lda, a.ext_ws);
-                        p.A = a.ext_ws; p.lda = a.K;
-                    }
-                    p.B = reinterpret_cast<const float*>(a.B); p.ldb = 2 * a.ldb;
-                    p.M = 2 * a.M; p.N = 2 * a.N; p.K = a.K;
-                    if (a.ksplits <= 1) p.klen = 0;
-                    CplxNnEpi<Epi> ce{epi};
-                    const int tier = pick_tier<FORM>(p.M, p.N, p.K, a.tile, a.split_planned);
-                    if (tier == TIER_SMALL_DEEP) return launch_gemm_mfma<CfgSmallDeep, AL, BL>(stream, p, ce);
-                    if (tier == TIER_SMALL || tier == TIER_FLAT || tier == TIER_TALL)
-                        return launch_gemm_mfma<CfgSmall, AL, BL>(stream, p, ce);
-                    return launch_gemm_mfma<CfgLarge, AL, BL>(stream, p, ce);
-                } else {
-                    // ext(B): [2 rows(B), 2 cols(B)] real image in the caller's scratch
-                    const long rowsB = (FORM == FORM_NT) ? a.N : a.K;
-                    const long colsB = (FORM == FORM_NT) ? a.K : a.N;
-                    long g = (rowsB * colsB + 255) / 256;
-                    if (g > 4096) g = 4096;
-                    if (g < 1) g = 1;
-                    if (!a.ext_ready)
-                        hipLaunchKernelGGL((cplx_ext_kernel<float>), dim3((unsigned)g), dim3(256), 0, stream, a.B,
-                                           rowsB, colsB, a.ldb, a.ext_ws);
-                    p.B = a.ext_ws; p.ldb = 2 * colsB;
-                    p.M = a.M; p.N = 2 * a.N; p.K = 2 * a.K;
-                    if (a.ksplits <= 1) p.klen = 0;
-                    CplxColEpi<Epi> ce{epi};
-                    const int tier = pick_tier<FORM>(p.M, p.N, p.K, a.tile, a.split_planned);
-                    if (tier == TIER_SMALL || tier == TIER_SMALL_DEEP || tier == TIER_FLAT || tier == TIER_TALL)
-                        return launch_gemm_mfma<CfgSmall, AL, BL>(stream, p, ce);
-                    if (tier == TIER_HUGE) return launch_gemm_mfma<CfgHuge, AL, BL>(stream, p, ce);
-                    if (tier == TIER_MID) return launch_gemm_mfma<CfgMid, AL, BL>(stream, p, ce);
-                    return launch_gemm_mfma<CfgLarge, AL, BL>(stream, p, ce);
-                }
-            }
+        const auto p = fill_problem<FORM>(a, r, launch_cplx_image(stream, a, r));
+        if constexpr (FORM == FORM_TN) {
+            return launch_tile<FORM, IMG_TN_VIEWS>(r, stream, p, CplxTnEpi<Epi, R>{epi});
+        } else {
+            if (r.image == IMG_ROWS_A) return launch_tile<FORM, IMG_ROWS_A>(r, stream, p, CplxNnEpi<Epi, R>{epi});
+            return launch_tile<FORM, IMG_EXT_B>(r, stream, p, CplxColEpi<Epi, R>{epi});
         }
-        if constexpr (std::is_same<T, c128>::value) {
-            const int Me = (FORM == FORM_TN) ? 2 * a.M : a.M;
-            const int t128 = f64_tier(Me, 2 * a.N, a.tile);
-            if (cplx_on_mfma<FORM>(a.conjA, a.conjB, a.ext_ws) && t128 != F64_GENERIC) {
-                // complex128 on the fp64 MFMA core: same real-extended formulation as complex64
-                GemmProblemD p;
-                p.A = reinterpret_cast<const double*>(a.A); p.lda = 2 * a.lda;
-                p.B2 = nullptr; p.ldb2 = 0; p.n_b1 = 2 * a.N;
-                p.ksplits = a.ksplits; p.klen = a.klen;
-                p.tiles_m = p.tiles_n = 0;
-                p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
-                constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
-                constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
-                if constexpr (FORM == FORM_TN) {
-                    p.B = reinterpret_cast<const double*>(a.B); p.ldb = 2 * a.ldb;
-                    if (a.B2 != nullptr) {
-                        p.B2 = reinterpret_cast<const double*>(a.B2); p.ldb2 = 2 * a.ldb2;
-                        p.n_b1 = 2 * a.n_b1;
-                    }
-                    p.M = 2 * a.M; p.N = 2 * a.N; p.K = a.K;
-                    CplxTnEpi<Epi, double> ce{epi};
-                    return launch_f64_tier<AL, BL>(t128, stream, p, ce);
-                } else if (cplx_planar_a<FORM>(a.M, a.N, a.conjA, a.conjB, a.ext_ws) &&
-                           f64_tier(2 * a.M, 2 * a.N, a.tile) != F64_GENERIC) {
-                    // planar rows of A against B's own memory, as for complex64 (mode 3)
-                    if (a.A_rows != nullptr) {
-                        p.A = a.A_rows; p.lda = a.lda_rows;
-                    } else {
-                        long g = ((long)a.M * a.K + 255) / 256;
-                        if (g > 4096) g = 4096;
-                        if (g < 1) g = 1;
-                        hipLaunchKernelGGL((cplx_rows_kernel<double>), dim3((unsigned)g), dim3(256), 0, stream, a.A,
-                                           (long)a.M, (long)a.K, a.lda, a.ext_ws);
-                        p.A = a.ext_ws; p.lda = a.K;
-                    }
-                    p.B = reinterpret_cast<const double*>(a.B); p.ldb = 2 * a.ldb;
-                    p.M = 2 * a.M; p.N = 2 * a.N; p.K = a.K;
-                    if (a.ksplits <= 1) p.klen = 0;
-                    CplxNnEpi<Epi, double> ce{epi};
-                    return launch_f64_tier<AL, BL>(f64_tier(p.M, p.N, a.tile), stream, p, ce);
-                } else {
-                    const long rowsB = (FORM == FORM_NT) ? a.N : a.K;
-                    const long colsB = (FORM == FORM_NT) ? a.K : a.N;
-                    long g = (rowsB * colsB + 255) / 256;
-                    if (g > 4096) g = 4096;
-                    if (g < 1) g = 1;
-                    if (!a.ext_ready)
-                        hipLaunchKernelGGL((cplx_ext_kernel<double>), dim3((unsigned)g), dim3(256), 0, stream, a.B,
-                                           rowsB, colsB, a.ldb, a.ext_ws);
-                    p.B = a.ext_ws; p.ldb = 2 * colsB;
-                    p.M = a.M; p.N = 2 * a.N; p.K = 2 * a.K;
-                    if (a.ksplits <= 1) p.klen = 0;
-                    CplxColEpi<Epi, double> ce{epi};
-                    return launch_f64_tier<AL, BL>(t128, stream, p, ce);
-                }
-            }
-        }
-        if constexpr (std::is_same<T, double>::value) {
-            const int t64 = f64_tier(a.M, a.N, a.tile, a.K);
-            if (t64 != F64_GENERIC) {
-                GemmProblemD p;
-                p.A = a.A; p.lda = a.lda; p.B = a.B; p.ldb = a.ldb;
-                p.B2 = a.B2; p.ldb2 = a.ldb2; p.n_b1 = a.n_b1;
-                p.M = a.M; p.N = a.N; p.K = a.K;
-                p.ksplits = a.ksplits; p.klen = a.klen;
-                p.tiles_m = p.tiles_n = 0;
-                p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
-                constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
-                constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
-                return launch_f64_tier<AL, BL>(t64, stream, p, epi);
-            }
-        }
-        GenericProblem<T> p;
-        p.A = a.A; p.B = a.B; p.B2 = a.B2; p.n_b1 = a.n_b1;
-        if (FORM == FORM_TN) { p.sAm = 1; p.sAk = a.lda; } else { p.sAm = a.lda; p.sAk = 1; }
-        if (FORM == FORM_NT) { p.sBk = 1; p.sBn = a.ldb; p.sB2k = 1; p.sB2n = a.ldb2; }
-        else { p.sBk = a.ldb; p.sBn = 1; p.sB2k = a.ldb2; p.sB2n = 1; }
-        p.M = a.M; p.N = a.N; p.K = a.K;
-        p.ksplits = a.ksplits; p.klen = a.klen;
-        p.tiles_m = p.tiles_n = 0;
-        if constexpr (scalar_traits<T>::is_complex)
-            return launch_gemm_generic<T, Epi>(stream, p, a.conjA, a.conjB, epi);
-        else
-            return launch_gemm_generic<T, Epi>(stream, p, false, false, epi);
     }
 }
 
@@ -594,19 +608,6 @@ inline hipError_t gemm(hipStream_t stream, const GemmArgs<T>& a, const Epi& epi)
 // hipErrorInvalidValue (callers check x6_tier first).
 enum { X6_NONE = -1, X6_LARGE = 0, X6_HUGE = 1 };
 constexpr int kX6HugeTnMinK = 1024;
-
-template <int FORM>
-inline GemmProblem x6_problem(const GemmArgs<float>& a) {
-    GemmProblem p;
-    p.A = a.A; p.lda = a.lda; p.B = a.B; p.ldb = a.ldb;
-    p.B2 = a.B2; p.ldb2 = a.ldb2; p.n_b1 = a.n_b1;
-    p.A2 = a.A2; p.lda2 = a.lda2; p.m_a1 = a.m_a1;
-    p.M = a.M; p.N = a.N; p.K = a.K;
-    p.ksplits = a.ksplits; p.klen = a.klen;
-    p.tiles_m = p.tiles_n = 0;
-    p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
-    return p;
-}
 
 // TN on 256 x 256 by shape alone (no pointers): whole tiles in both B segments (columns < n1, >= n1) and deep
 // enough splits
@@ -645,7 +646,7 @@ template <int FORM>
 inline int x6_tier(const GemmArgs<float>& a) {
     if (FORM == FORM_NN) return X6_NONE;
     const int tier = pick_tier<FORM>(a.M, a.N, a.K, a.tile, a.split_planned, true);
-    const GemmProblem p = x6_problem<FORM>(a);
+    const GemmProblem p = fill_problem<FORM>(a);
     if (FORM == FORM_NT && tier == TIER_HUGE && x6_eligible<X6Huge>(p)) return X6_HUGE;
     if (FORM == FORM_TN && tier == TIER_LARGE && x6_huge_tn_shape(a, a.B2 != nullptr ? a.n_b1 : a.N, a.ksplits > 1 ? a.klen : a.K) &&
         x6_eligible<X6Huge>(p))
@@ -664,8 +665,8 @@ inline hipError_t gemm_bf16x6(hipStream_t stream, const GemmArgs<float>& a, cons
         return hipErrorInvalidValue;
     } else {
         const int t = x6_tier<FORM>(a);
-        if (t == X6_HUGE) return launch_gemm_bf16x6<X6Huge, AL, BL, Epi>(stream, x6_problem<FORM>(a), epi);
-        if (t == X6_LARGE) return launch_gemm_bf16x6<X6Large, AL, BL, Epi>(stream, x6_problem<FORM>(a), epi);
+        if (t == X6_HUGE) return launch_gemm_bf16x6<X6Huge, AL, BL, Epi>(stream, fill_problem<FORM>(a), epi);
+        if (t == X6_LARGE) return launch_gemm_bf16x6<X6Large, AL, BL, Epi>(stream, fill_problem<FORM>(a), epi);
         return hipErrorInvalidValue;
     }
 }

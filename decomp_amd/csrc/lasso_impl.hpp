@@ -1251,7 +1251,7 @@ inline int lasso_solve(dcp_handle* h, const T* Y, const real_t<T>* mask, int mas
                 // complex: the extended image of A A^H (ext2 holds nothing else during the loop) is built by
                 // the first iteration and reused by the others (a product with fewer samples than atoms takes
                 // the planar-rows form instead, which images V and ignores this flag)
-                a.ext_ready = i > 0 && !cplx_planar_a<FORM_NN>(N, K, false, false, w.ext2);
+                a.ext_ready = i > 0 && gemm_route<FORM_NN>(a).image != IMG_ROWS_A;
                 // float32, >= 512 atoms, at least one 128 x 128 tile per two CUs: the 8-wave 128 x 128 x 64 tile
                 // (8192 x 512 x 512: 45 us against 50 us on the 64 x 64 tile for the bare product; dictionary step
                 // 1.64 -> 1.62 ms).  complex64 measured slower on it and keeps the automatic choice.

@@ -86,7 +86,12 @@ inline int nmf_xupdate_splits(int64_t N, int64_t F, int64_t K, GemmArgs<T>& pg) 
     pg.M = (int)N; pg.N = (int)K; pg.K = (int)F;
     pg.tile = TILE_AUTO;
     int bm = 64, bn = 64;
-    if (std::is_same<T, float>::value) tier_dims(pick_tier<FORM_NT>(pg.M, pg.N, pg.K, TILE_AUTO, true), bm, bn);
+    if (std::is_same<T, float>::value) {   // the tile a split plan would count by (float64 counts 64 x 64 here: kept)
+        GemmArgs<T> planned = pg;
+        planned.split_planned = true;
+        const GemmRoute r = gemm_route<FORM_NT>(planned);
+        bm = r.plan_bm; bn = r.plan_bn;
+    }
     const long tiles = (long)ceil_div(N, bm) * ceil_div(K, bn);
     const long enough = (bm == 256) ? 192 : 512;
     if (tiles >= enough || F < 1024) {
@@ -333,7 +338,7 @@ inline int nmf_stats(dcp_handle* h, const T* Ypre, const T* mask, const T* Xin, 
         const int psplits = nmf_xupdate_splits<T>(s.N, s.F, s.K, pg);
         if (fused_den) {
             if constexpr (std::is_same<T, float>::value) {
-                const GemmProblem fp = x6_problem<FORM_NT>(pg);
+                const GemmProblem fp = fill_problem<FORM_NT>(pg);
                 if (pen.on())
                     DCP_LAUNCH_OK(h, (launch_gemm_bf16x6<X6Huge, KMAJOR, KMAJOR>(
                                          st, fp, EpiMuGramDen<true>{Xin, K, w.G, K, K, Xout, K, l1, l2})));

@@ -93,15 +93,9 @@ typedef TileCfg<32, 128, 32, 32, 32, 2> CfgFlat32s;     // 34: 4 waves of 32x32,
 
 template <class Cfg, int FORM, class Epi>
 hipError_t hook_cfg(hipStream_t st, const GemmArgs<float>& a, const Epi& epi) {
-    GemmProblem p;
-    p.A = a.A; p.lda = a.lda; p.B = a.B; p.ldb = a.ldb;
-    p.B2 = nullptr; p.ldb2 = 0; p.n_b1 = a.N;
-    p.M = a.M; p.N = a.N; p.K = a.K; p.ksplits = a.ksplits; p.klen = a.klen;
-    p.tiles_m = p.tiles_n = 0;
-    p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
     constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
     constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
-    return launch_gemm_mfma<Cfg, AL, BL, Epi>(st, p, epi);
+    return launch_gemm_mfma<Cfg, AL, BL, Epi>(st, fill_problem<FORM>(a), epi);
 }
 
 // fp64 tile experiments (test hook only): codes 3..6
@@ -113,13 +107,7 @@ typedef F64Cfg<128, 128, 32, 64, 2> F64Thin;     // 6: 8 waves of 32 x 64, two w
 template <int FORM, class Epi>
 hipError_t gemm_hook_launch_f64(hipStream_t st, const GemmArgs<double>& a, int tile, const Epi& epi) {
     if (tile >= 3 && tile <= 6) {
-        GemmProblemD p;
-        p.A = a.A; p.lda = a.lda; p.B = a.B; p.ldb = a.ldb;
-        p.B2 = nullptr; p.ldb2 = 0; p.n_b1 = a.N;
-        p.M = a.M; p.N = a.N; p.K = a.K;
-        p.ksplits = a.ksplits; p.klen = a.klen;
-        p.tiles_m = p.tiles_n = 0;
-        p.mt_fast = (FORM == FORM_NT) ? 0 : 1;
+        const GemmProblemD p = fill_problem<FORM>(a);
         constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR;
         constexpr int BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
         if (tile == 3) return launch_gemm_mfma_f64_cfg<F64Big, AL, BL, Epi>(st, p, epi);
@@ -210,9 +198,9 @@ int gemm_api(dcp_handle* h, int form, const T* A, const T* B, T* C, int64_t M, i
         }));
         if (ext_floats) {
             a.ext_ws = ext;
-            bool planar = form == FORM_NN && cplx_planar_a<FORM_NN>(a.M, a.N, a.conjA, a.conjB, a.ext_ws);
-            if (std::is_same<T, c128>::value) planar = planar && f64_tier(2 * a.M, 2 * a.N, a.tile) != F64_GENERIC;
-            if (form != FORM_TN && !planar) {   // the MFMA core splits the real-extended reduction (2K)
+            const int image = form == FORM_NT ? gemm_route<FORM_NT>(a).image
+                            : form == FORM_NN ? gemm_route<FORM_NN>(a).image : gemm_route<FORM_TN>(a).image;
+            if (image == IMG_EXT_B) {   // the MFMA core splits the real-extended reduction (2K)
                 const long kb2 = (2 * K + 15) / 16;
                 long s2 = ksplits > kb2 ? kb2 : ksplits;
                 a.klen = (int)(((kb2 + s2 - 1) / s2) * 16);
@@ -239,6 +227,36 @@ int gemm_api(dcp_handle* h, int form, const T* A, const T* B, T* C, int64_t M, i
         if (e != hipSuccess) return fail(h, DCP_ERR_HIP, hipGetErrorString(e));
     }
     return DCP_OK;
+}
+
+// dcp_debug_gemm_route for one dtype: dummy aligned operands, conjugations as gemm_api sets them
+template <class T>
+void debug_route(int form, int64_t M, int64_t N, int64_t K, int64_t n_b1, int tile, int flags, int target_wgs,
+                 int max_splits, int min_blocks, int32_t* out) {
+    GemmArgs<T> a;
+    a.A = reinterpret_cast<const T*>(0x10000); a.B = reinterpret_cast<const T*>(0x20000);
+    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.tile = tile;
+    a.lda = (form == FORM_TN) ? M : K;
+    a.ldb = (form == FORM_NT) ? K : N;
+    if (n_b1 > 0) { a.B2 = reinterpret_cast<const T*>(0x30000); a.ldb2 = a.ldb; a.n_b1 = (int)n_b1; }
+    if (flags & 2) { a.A2 = reinterpret_cast<const T*>(0x50000); a.lda2 = a.lda; a.m_a1 = (int)(M / 2); }
+    if constexpr (scalar_traits<T>::is_complex) {
+        a.conjB = (form == FORM_NT);
+        a.conjA = (form == FORM_TN);
+        if (flags & 1) a.ext_ws = reinterpret_cast<real_t<T>*>(0x40000);
+    }
+    GemmRoute r;
+    auto go = [&](auto f) {
+        if (target_wgs > 0) plan_splits<decltype(f)::value>(a, target_wgs, max_splits, min_blocks);
+        r = gemm_route<decltype(f)::value>(a);
+    };
+    if (form == FORM_NT) go(std::integral_constant<int, FORM_NT>{});
+    else if (form == FORM_NN) go(std::integral_constant<int, FORM_NN>{});
+    else go(std::integral_constant<int, FORM_TN>{});
+    const TileDims& t = r.tile;   // (the generic core builds no image: see GemmRoute::image)
+    const int32_t v[13] = {r.core, r.core == CORE_GENERIC ? IMG_NONE : r.image, t.BM, t.BN, t.BK, t.WM, t.WN, t.PIPE,
+                           r.M, r.N, r.K, r.klen, r.ksplits};
+    for (int i = 0; i < 13; ++i) out[i] = v[i];
 }
 
 // PMC calibration aid (MI355X_MICROARCH.md, HBM section: "calibrate on a known byte count in your
@@ -400,6 +418,17 @@ int dcp_debug_tn_plain(int on) {
     const int prev = dcp::tn_plain_schedule() ? 1 : 0;
     if (on >= 0) dcp::tn_plain_flag().store(on ? 1 : 0, std::memory_order_relaxed);
     return prev;
+}
+
+int dcp_debug_gemm_route(int dtype, int form, int64_t M, int64_t N, int64_t K, int64_t n_b1, int tile, int flags,
+                         int target_wgs, int max_splits, int min_blocks, int32_t* out) {
+    if (!out || dtype < 0 || dtype > 3 || form < 0 || form > 2 || M <= 0 || N <= 0 || K <= 0 || n_b1 < 0 || n_b1 >= N)
+        return DCP_ERR_INVALID;
+    if (dtype == 0) debug_route<float>(form, M, N, K, n_b1, tile, flags, target_wgs, max_splits, min_blocks, out);
+    else if (dtype == 1) debug_route<double>(form, M, N, K, n_b1, tile, flags, target_wgs, max_splits, min_blocks, out);
+    else if (dtype == 2) debug_route<c64>(form, M, N, K, n_b1, tile, flags, target_wgs, max_splits, min_blocks, out);
+    else debug_route<c128>(form, M, N, K, n_b1, tile, flags, target_wgs, max_splits, min_blocks, out);
+    return DCP_OK;
 }
 
 int dcp_calib_read_f32(dcp_handle* h, const float* p, int64_t rows, int64_t cols, int pattern,

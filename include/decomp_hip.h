@@ -195,6 +195,17 @@ int dcp_set_f32_product_mode(dcp_handle* h, int mode);
  * LDS waits of the pair schedule is caught. */
 int dcp_debug_tn_plain(int on);
 
+/* Test hook (not a reference interface): how the GEMM front end routes one product.  Pure host arithmetic, no
+ * handle and no GPU.  dtype: 0 = float32, 1 = float64, 2 = complex64, 3 = complex128; form, tile and the
+ * conjugations as dcp_gemm_*; n_b1 > 0: B in two column segments, the first n_b1 wide; flags: bit 0 = an
+ * extended-operand scratch is present (complex), bit 1 = a second row segment of A is present.  target_wgs > 0
+ * plans the split-K first (plan_splits(target_wgs, max_splits, min_blocks)); 0 routes one un-planned split.
+ * out[13] = core (0 fp32 MFMA, 1 fp64 MFMA, 2 generic), complex image (0 none, 1 ext(B), 2 TN views, 3 rows(A)),
+ * the launched tile BM, BN, BK, WM, WN, PIPE, the product as the core sees it M, N, K, and klen, ksplits as the
+ * core receives them. */
+int dcp_debug_gemm_route(int dtype, int form, int64_t M, int64_t N, int64_t K, int64_t n_b1, int tile, int flags,
+                         int target_wgs, int max_splits, int min_blocks, int32_t* out);
+
 /* PMC calibration aid (not a reference interface): reads p[rows, cols] exactly once with the
  * global-load shape of the GEMM panel loaders (pattern 0: 16 rows x 64 B per wave instruction;
  * pattern 1: 512-B row segments), so that rocprofv3 FETCH_SIZE can be compared with a known

@@ -118,7 +118,10 @@ def test_c64_on_mfma(form):
     for (M, N, K, ks) in [(256, 256, 128, 1), (128, 64, 512, 4), (101, 20, 3, 1), (37, 65, 129, 3),
                           (512, 128, 256, 1), (64, 96, 1000, 7), (5, 3, 10, 1),
                           # left operand the smaller one: A B takes the planar-rows form (no image of B)
-                          (32, 1024, 512, 1), (31, 333, 130, 1), (64, 2048, 64, 1), (16, 512, 2048, 4)]:
+                          (32, 1024, 512, 1), (31, 333, 130, 1), (64, 2048, 64, 1), (16, 512, 2048, 4),
+                          # <= 16 atoms, A^H B: the smallest shape whose split plan counts 32 x 128 tiles where the
+                          # launch runs 64 x 64 ones
+                          (3, 200, 999, 4)]:
         if form == 0:
             A, B = _cplx(rng, M, K), _cplx(rng, N, K)
             ref = A.astype(np.complex128) @ B.astype(np.complex128).conj().T
@@ -147,7 +150,10 @@ def test_c128_on_mfma(form):
     def cplx(*s):
         return rng.randn(*s) + 1j * rng.randn(*s)
     for (M, N, K, ks) in [(256, 256, 128, 1), (128, 64, 512, 4), (130, 70, 35, 1), (64, 96, 1000, 7),
-                          (512, 128, 256, 1), (300, 129, 77, 3)]:
+                          (512, 128, 256, 1), (300, 129, 77, 3),
+                          # A B: the split plan counts tiles of the planar-rows product, the launch takes the thin
+                          # output to the generic core
+                          (30, 50, 1000, 3)]:
         if form == 0:
             A, B = cplx(M, K), cplx(N, K)
             ref = A @ B.conj().T
