@@ -91,6 +91,10 @@ SIGNATURES = {
     'dcp_omp_gram_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
     'dcp_omp_gram_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
     'dcp_omp_gram_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
+    'dcp_omp_mask_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_omp_mask_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_omp_mask_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_omp_mask_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_int)]),
     'dcp_ksvd_sweep_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
     'dcp_ksvd_sweep_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
     'dcp_ksvd_sweep_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),

@@ -5,6 +5,9 @@
 next to the L1 family of ``decomp_amd.lasso``.  Shapes, dtypes and the NumPy / torch convention are those of
 ``lasso.solve``.  Everything after validation runs in libdecomp_hip.so (``dcp_omp_*``: both products on the GEMM
 cores, then the greedy kernel of decomp_amd/csrc/omp.hpp, which also states the algorithm).
+
+With ``mask`` every row is coded on its observed samples only (``dcp_omp_mask_*``, decomp_amd/csrc/omp_mask.hpp):
+the same greedy algorithm with every inner product weighted by the mask.
 """
 import ctypes
 import math
@@ -47,19 +50,31 @@ def check_tol(tol, what='tol'):
     return float(tol)
 
 
-def solve(y, A, n_nonzero_coefs=None, tol=None):
+def solve(y, A, n_nonzero_coefs=None, tol=None, mask=None):
     """
     Greedy solution of  argmin_x |y - xA|^2  s.t. |x|_0 <= n_nonzero_coefs  for every row of y.
 
     y: [..., n_channels], A: [n_features, n_channels]; float or complex, both of one dtype.
     n_nonzero_coefs: at most this many atoms per row (<= 64 real, <= 32 complex).
     tol: stop a row once |y - xA|^2 <= tol.  With tol alone the sparsity is min(n_features, n_channels, cap).
+    mask: real, non-negative weights m of the samples, y's shape or [n_channels]; None: the unweighted problem.
+        With a mask the objective is  sum_f m_f |y_f - (xA)_f|^2  (and tol bounds that weighted residual): a sample
+        with m_f = 0 is missing, an atom is scored by its observed part only, and a row without any observed
+        sample gets x = 0.  The weights enter LINEARLY (m, not m^2): the convention of the 2-D masks of
+        ``lasso.solve`` and of ``nmf.solve(method='em-hals')``; for 0 / 1 masks it coincides with the 1-D
+        convention of ``lasso.solve``.  The mask is cast to the real dtype of y.
     Returns (it, x): x [..., n_features] with zeros off the support, it the largest number of atoms any row took.
     """
-    kind = get_array_module(y, A)
+    kind = get_array_module(y, A, mask)
     assertion.assert_dtypes(y=y, A=A)
+    assertion.assert_dtypes(mask=mask, dtypes='f')
+    assertion.assert_nonnegative_host_or_device(mask)
     assertion.assert_ndim('A', A, ndim=2)
     assertion.assert_shapes('y', y, 'A', A, axes=[-1])
+    if mask is not None and len(mask.shape) == 1:
+        assertion.assert_shapes('y', y, 'mask', mask, axes=[-1])
+    else:
+        assertion.assert_shapes('y', y, 'mask', mask)
     if n_nonzero_coefs is None and tol is None:
         raise ValueError('Either n_nonzero_coefs or tol must be given.')
     K, F = int(A.shape[0]), int(A.shape[1])
@@ -81,8 +96,21 @@ def solve(y, A, n_nonzero_coefs=None, tol=None):
     it = ctypes.c_int(0)
     if N > 0:
         lib, h = _arrays.lib_handle(yd)
-        name = 'dcp_omp_' + _arrays.suffix(yd)
-        rc = getattr(lib, name)(h, _arrays.ptr(y2), _arrays.ptr(Ad), _arrays.ptr(xd), N, F, K, s, tol_c,
-                                ctypes.byref(it))
+        if mask is None:
+            name = 'dcp_omp_' + _arrays.suffix(yd)
+            rc = getattr(lib, name)(h, _arrays.ptr(y2), _arrays.ptr(Ad), _arrays.ptr(xd), N, F, K, s, tol_c,
+                                    ctypes.byref(it))
+        else:
+            md = _arrays.to_device(mask, dev)
+            rdt = torch.float64 if yd.dtype in (torch.float64, torch.complex128) else torch.float32
+            if md.dtype != rdt:
+                md = md.to(rdt)
+            mask_ndim = 1 if md.dim() == 1 else 2
+            if mask_ndim == 2:
+                md = md.reshape(N, F)
+            md = md.contiguous()
+            name = 'dcp_omp_mask_' + _arrays.suffix(yd)
+            rc = getattr(lib, name)(h, _arrays.ptr(y2), _arrays.ptr(md), mask_ndim, _arrays.ptr(Ad), _arrays.ptr(xd),
+                                    N, F, K, s, tol_c, 0, ctypes.byref(it))
         _hip.check(h, rc, name)
     return it.value, _arrays.to_caller(xd.reshape(batch_shape + (K,)), kind)

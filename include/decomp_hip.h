@@ -555,6 +555,35 @@ int dcp_omp_gram_c64(dcp_handle* h, const void* alpha0, const void* G, const flo
 int dcp_omp_gram_c128(dcp_handle* h, const void* alpha0, const void* G, const double* ynorm2, void* X,
                       int64_t N, int64_t K, int n_nonzero, double tol, int* it_out);
 
+/* ---- masked orthogonal matching pursuit (not in the reference; csrc/omp_mask.hpp) ------------- */
+/* argmin_x sum_f m_f |y_f - (x A)_f|^2  s.t.  |x|_0 <= n_nonzero  for every row of Y[N,F], A[K,F], with non-negative
+ * weights M in the real type: [F] (mask_ndim 1, shared by all rows) or [N,F] (mask_ndim 2, a row of its own for every
+ * row of Y), as in dcp_lasso_*.  The weights enter linearly (m, not m^2).  The algorithm is that of dcp_omp_* with
+ * every inner product weighted, <u, v>_m = sum_f m_f u_f conj(v_f): the residual stop is sum m |r|^2 <= tol, the
+ * selection score |<r, a_k>_m| / n_k with n_k^2 = sum_f m_f |a_kf|^2 of THAT row (an atom whose observed part vanishes
+ * in a row is never selected there; a row whose weights are all zero gets x = 0 and takes no step), the pivot test
+ * d <= 4096 eps n_k*^2.  n_nonzero, tol, the sizes, X, *it_out and the error codes are those of dcp_omp_*; mask_ndim
+ * other than 1 or 2, a negative rows_per_pass or a null M: DCP_ERR_INVALID.
+ *   mask_ndim 1 : Y and A are scaled by sqrt(m) into workspace and dcp_omp_* runs on them.
+ *   mask_ndim 2 : the residual form, in passes of rows_per_pass rows (0: the library chooses the fewest equal passes
+ *                 whose per-row workspace -- the packed Cholesky factor, alpha, the weighted norms and the residual
+ *                 image -- stays within 1 GiB).  Per pass the weighted squared norms M (|A|^2)^T, then n_nonzero
+ *                 times: alpha = (m o r) A^H on the GEMM cores and one step kernel (selection, the weighted dot
+ *                 products of the pivot, the factor's new row, both substitutions, r rebuilt from y).  No host round
+ *                 trip between the steps.
+ * Bitwise reproducible; the rows are independent, so the result does not depend on rows_per_pass as long as the
+ * products of every pass take the same GEMM tile.  Synchronises the stream before returning.  With dcp_profile_*
+ * on, the products of the steps are timed under DCP_PROF_GRAM, the step kernels under DCP_PROF_XUPDATE and the rest
+ * under DCP_PROF_MISC. */
+int dcp_omp_mask_f32(dcp_handle* h, const float* Y, const float* M, int mask_ndim, const float* A, float* X,
+                     int64_t N, int64_t F, int64_t K, int n_nonzero, double tol, int rows_per_pass, int* it_out);
+int dcp_omp_mask_f64(dcp_handle* h, const double* Y, const double* M, int mask_ndim, const double* A, double* X,
+                     int64_t N, int64_t F, int64_t K, int n_nonzero, double tol, int rows_per_pass, int* it_out);
+int dcp_omp_mask_c64(dcp_handle* h, const void* Y, const float* M, int mask_ndim, const void* A, void* X,
+                     int64_t N, int64_t F, int64_t K, int n_nonzero, double tol, int rows_per_pass, int* it_out);
+int dcp_omp_mask_c128(dcp_handle* h, const void* Y, const double* M, int mask_ndim, const void* A, void* X,
+                      int64_t N, int64_t F, int64_t K, int n_nonzero, double tol, int rows_per_pass, int* it_out);
+
 /* ---- approximate K-SVD (not in the reference; csrc/ksvd.hpp) ---------------------------------- */
 /* min |Y - X D|^2  s.t.  |x_i|_0 <= s, |d_k| = 1  for Y[N,F], X[N,K], D[K,F] (Rubinstein, Zibulevsky & Elad 2008).
  * The atom sweep, on R = Y - X D formed once on the GEMM cores: for k = 0 .. K-1 in order, with I the rows where
