@@ -33,6 +33,9 @@
 //           once.  Rows too long for the slice (F sizeof(T) > kKsvdLdsBytes) are read a second time instead.  The
 //           waves also write D[k] = d', a slice each.
 // Each atom makes two reads and one write of its support rows of R: 3 sum_k |I_k| F sizeof(T) bytes per sweep.
+//
+// The sweep for data with holes (every inner product weighted per row, and its own monotonicity argument) is
+// ksvd_mask.hpp; it shares the lists, ksvd_sweep_begin / ksvd_sweep_end and the workspace of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -403,16 +406,28 @@ inline int ksvd_count(dcp_handle* h, const T* X, int N, int K, KsvdWs<T>& w) {
     return DCP_OK;
 }
 
+// pass 2's workgroup: the row kept in LDS where it fits (use_lds), as many waves (4, 2 or 1) as slices fit
+struct KsvdPass2Shape {
+    int use_lds, waves;
+    size_t lds;
+};
+template <class T>
+inline KsvdPass2Shape ksvd_pass2_shape(int F) {
+    const size_t row_bytes = (size_t)F * sizeof(T);
+    const int use_lds = row_bytes <= (size_t)kKsvdLdsBytes;
+    int waves = 4;
+    while (use_lds && waves > 1 && waves * row_bytes > (size_t)kKsvdLdsBytes) waves >>= 1;
+    return KsvdPass2Shape{use_lds, waves, use_lds ? waves * row_bytes : 0};
+}
+
 template <class T, int V>
 inline int ksvd_atoms(dcp_handle* h, T* X, T* D, int N, int F, int K, const int* cnt, KsvdWs<T>& w) {
     hipStream_t st = h->stream;
     const long ntiles = ((long)F + 64L * V - 1) / (64L * V);
     const int nparts = (int)(((long)F + 255) / 256);
-    const size_t row_bytes = (size_t)F * sizeof(T);
-    const int use_lds = row_bytes <= (size_t)kKsvdLdsBytes;
-    int waves = 4;
-    while (use_lds && waves > 1 && waves * row_bytes > (size_t)kKsvdLdsBytes) waves >>= 1;
-    const size_t lds = use_lds ? waves * row_bytes : 0;
+    const KsvdPass2Shape p2 = ksvd_pass2_shape<T>(F);
+    const int use_lds = p2.use_lds, waves = p2.waves;
+    const size_t lds = p2.lds;
     for (int k = 0; k < K; ++k) {
         if (cnt[k] == 0) continue;
         const long nchunks = ((long)cnt[k] + kKsvdChunk - 1) / kKsvdChunk;
@@ -432,10 +447,9 @@ inline int ksvd_atoms(dcp_handle* h, T* X, T* D, int N, int F, int K, const int*
     return DCP_OK;
 }
 
-// Steps 2 and 3 on X whose counts (cnt [K], host) ksvd_count produced: the lists, R = Y - X D, the K atoms, then
-// max|D_new - D_old| into w.mdpart.  Enqueues only, from this one call: no host round trip between atoms.
+// What every sweep does before atom 0: the lists (on the counts of ksvd_count), the copy of D, R = Y - X D.
 template <class T>
-inline int ksvd_sweep(dcp_handle* h, const T* Y, T* X, T* D, int N, int F, int K, const int* cnt, KsvdWs<T>& w) {
+inline int ksvd_sweep_begin(dcp_handle* h, const T* Y, T* X, T* D, int N, int F, int K, KsvdWs<T>& w) {
     hipStream_t st = h->stream;
     const int nb = (N + kKsvdRowBlock - 1) / kKsvdRowBlock;
     hipLaunchKernelGGL((ksvd_fill_kernel<T>), dim3(nb), dim3(256), 0, st, (const T*)X, N, K,
@@ -448,15 +462,28 @@ inline int ksvd_sweep(dcp_handle* h, const T* Y, T* X, T* D, int N, int F, int K
         a.ext_ws = w.ext;
         DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a, EpiSubFrom<T>{Y, (long)F, w.R, (long)F})));
     }
+    return DCP_OK;
+}
+
+// ... and after atom K - 1: mdpart[b] = max |D - Dold| over workgroup b's share (NaN wins, as np.max), as double
+template <class T>
+inline int ksvd_sweep_end(dcp_handle* h, const T* D, int F, int K, KsvdWs<T>& w) {
+    hipLaunchKernelGGL((reduce_partial_kernel<MaxOp, MapAbsDiff<T>, double>), dim3(grid_for((long)K * F, kKsvdMdParts)),
+                       dim3(256), 0, h->stream, MapAbsDiff<T>{D, w.Dold}, (long)K * F, w.mdpart);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
+// Steps 2 and 3 on X whose counts (cnt [K], host) ksvd_count produced: the lists, R = Y - X D, the K atoms, then
+// max|D_new - D_old| into w.mdpart.  Enqueues only, from this one call: no host round trip between atoms.
+template <class T>
+inline int ksvd_sweep(dcp_handle* h, const T* Y, T* X, T* D, int N, int F, int K, const int* cnt, KsvdWs<T>& w) {
+    DCP_TRY(ksvd_sweep_begin<T>(h, Y, X, D, N, F, K, w));
     // 16-byte accesses where every row of R, D and the partials starts on a 16-byte boundary
     const bool vec = ksvd_vec<T>() > 1 && ((size_t)F * sizeof(T)) % 16 == 0 && al16_ptr(D);
     if (vec) DCP_TRY((ksvd_atoms<T, ksvd_vec<T>()>(h, X, D, N, F, K, cnt, w)));
     else DCP_TRY((ksvd_atoms<T, 1>(h, X, D, N, F, K, cnt, w)));
-    // mdpart[b] = max |D - Dold| over workgroup b's share (NaN wins, as np.max), as double
-    hipLaunchKernelGGL((reduce_partial_kernel<MaxOp, MapAbsDiff<T>, double>), dim3(grid_for((long)K * F, kKsvdMdParts)),
-                       dim3(256), 0, st, MapAbsDiff<T>{D, w.Dold}, (long)K * F, w.mdpart);
-    DCP_LAUNCH_OK(h, hipGetLastError());
-    return DCP_OK;
+    return ksvd_sweep_end<T>(h, D, F, K, w);
 }
 
 // host <- the largest row count, the column counts and (it_dev given) OMP's step count: one synchronisation

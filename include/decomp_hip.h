@@ -614,6 +614,44 @@ int dcp_ksvd_step_c64(dcp_handle* h, const void* Y, void* X, void* D, int64_t N,
 int dcp_ksvd_step_c128(dcp_handle* h, const void* Y, void* X, void* D, int64_t N, int64_t F, int64_t K,
                        int n_nonzero, double coef_tol, double* maxdiff_out, int* it_out);
 
+/* ---- masked approximate K-SVD (not in the reference; csrc/ksvd_mask.hpp) ------------------------ */
+/* min sum_if M_if |Y_if - (X D)_if|^2  s.t.  |x_i|_0 <= s, |d_k| = 1: dcp_ksvd_* for data with holes.  M: non-negative
+ * weights in the real type, [F] (mask_ndim 1) or [N,F] (mask_ndim 2), entering linearly, as in dcp_omp_mask_*.  Y must
+ * be finite at hidden entries (M = 0) too; its values there do not influence the result.  The atom sweep, on
+ * R = Y - X D formed once: for k = 0 .. K-1 in order, I the rows where X[i,k] != 0, g = X[I,k], d = D[k], m_i = M[i,:]:
+ *   c_f = sum_I m_if |g_i|^2;  n_f = sum_I m_if conj(g_i) R_if + c_f d_f;  u_f = n_f / c_f (d_f where !(c_f > 0));
+ *   d' = u / |u| (d where !(|u| > 0));  q_i = sum_f m_if |d'_f|^2;
+ *   g'_i = (sum_f m_if R_if conj(d'_f) + g_i sum_f m_if d_f conj(d'_f)) / q_i (0 where !(q_i > 0));
+ *   R[I,:] += g d - g' d';  X[I,k] = g';  D[k] = d'.
+ * u minimises the weighted objective over the atom for fixed g, the normalisation leaves it unchanged and g' minimises
+ * it over the coefficients for d', so the sweep never increases it.  With M = 1 this is the sweep of dcp_ksvd_sweep_*
+ * up to rounding.  A 1-D mask and its [N,F] broadcast give the same bits.  Bitwise reproducible; both families
+ * synchronise the stream before returning.  *maxdiff_out, row_nnz_max, n_nonzero, coef_tol and *it_out are those of
+ * dcp_ksvd_*; rows_per_pass and the coder are those of dcp_omp_mask_* (coef_tol bounds the weighted residual).
+ * A null pointer, sizes outside [1, 2^31-1], mask_ndim other than 1 or 2, a negative rows_per_pass, a NaN coef_tol, a
+ * sparsity beyond the cap or K, row_nnz_max outside [1, K] or below a row's count: DCP_ERR_INVALID with a message,
+ * before anything is written. */
+int dcp_ksvd_mask_sweep_f32(dcp_handle* h, const float* Y, const float* M, int mask_ndim, float* X, float* D,
+                            int64_t N, int64_t F, int64_t K, int row_nnz_max, double* maxdiff_out);
+int dcp_ksvd_mask_sweep_f64(dcp_handle* h, const double* Y, const double* M, int mask_ndim, double* X, double* D,
+                            int64_t N, int64_t F, int64_t K, int row_nnz_max, double* maxdiff_out);
+int dcp_ksvd_mask_sweep_c64(dcp_handle* h, const void* Y, const float* M, int mask_ndim, void* X, void* D,
+                            int64_t N, int64_t F, int64_t K, int row_nnz_max, double* maxdiff_out);
+int dcp_ksvd_mask_sweep_c128(dcp_handle* h, const void* Y, const double* M, int mask_ndim, void* X, void* D,
+                             int64_t N, int64_t F, int64_t K, int row_nnz_max, double* maxdiff_out);
+int dcp_ksvd_mask_step_f32(dcp_handle* h, const float* Y, const float* M, int mask_ndim, float* X, float* D,
+                           int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                           double* maxdiff_out, int* it_out);
+int dcp_ksvd_mask_step_f64(dcp_handle* h, const double* Y, const double* M, int mask_ndim, double* X, double* D,
+                           int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                           double* maxdiff_out, int* it_out);
+int dcp_ksvd_mask_step_c64(dcp_handle* h, const void* Y, const float* M, int mask_ndim, void* X, void* D,
+                           int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                           double* maxdiff_out, int* it_out);
+int dcp_ksvd_mask_step_c128(dcp_handle* h, const void* Y, const double* M, int mask_ndim, void* X, void* D,
+                            int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                            double* maxdiff_out, int* it_out);
+
 /* ---- row movers of the minibatch containers (decomp/utils/data.py:124-156, 214-313) ------ */
 /* gather : out[i, :] = in[index[i], :]      scatter: out[index[i], :] = in[i, :]      i < rows
  * Rows are row_bytes long (any dtype); index: int64 in DEVICE memory.  `in` / `out` may be
