@@ -84,6 +84,20 @@ def to_device(a, device=None, copy=False):
     return torch.from_numpy(arr).to('cuda:%d' % dev)
 
 
+def mask_to_device(mask, yd, N, F):
+    """(md, mask_ndim) for the library: the mask on yd's device in yd's real dtype, contiguous, [F] (mask_ndim 1)
+    or reshaped to [N, F] (mask_ndim 2); (None, 0) without a mask."""
+    if mask is None:
+        return None, 0
+    md = to_device(mask, yd.device.index)
+    rdt = torch.float64 if yd.dtype in (torch.float64, torch.complex128) else torch.float32
+    if md.dtype != rdt:
+        md = md.to(rdt)
+    if md.dim() == 1:
+        return md.contiguous(), 1
+    return md.reshape(N, F).contiguous(), 2
+
+
 def to_caller(t, kind):
     """Back to the caller's array kind."""
     if t is None:

@@ -34,12 +34,16 @@
 //           waves also write D[k] = d', a slice each.
 // Each atom makes two reads and one write of its support rows of R: 3 sum_k |I_k| F sizeof(T) bytes per sweep.
 //
-// The sweep for data with holes (every inner product weighted per row, and its own monotonicity argument) is
-// ksvd_mask.hpp; it shares the lists, ksvd_sweep_begin / ksvd_sweep_end and the workspace of this file.
+// The sweep for data with holes (every inner product weighted per row, and its own monotonicity argument) is stated
+// in ksvd_mask.hpp, which holds its three kernels.  The host path below is one for both: the atom loop launches the
+// three kernels of this file or those three, and the coder of a step is OmpCoder (omp_mask.hpp) for mask = none, 1-D
+// or 2-D.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "omp.hpp"
+#include <cstdint>
+
+#include "omp_mask.hpp"
 
 namespace dcp {
 
@@ -65,6 +69,13 @@ template <class T>
 __device__ __forceinline__ T ksvd_div(T a, real_t<T> s) {   // a true division, as the reference's u / |u|
     if constexpr (scalar_traits<T>::is_complex) return T{a.re / s, a.im / s};
     else return a / s;
+}
+
+// one element of the new atom: d' = u / |u|, or d where !(|u| > 0)
+template <class T, int V>
+__device__ __forceinline__ T ksvd_new_atom(bool keep_d, const KsvdPack<T, V>& d, const KsvdPack<T, V>& u, int q,
+                                           real_t<T> nrm) {
+    return keep_d ? d.v[q] : ksvd_div(u.v[q], nrm);
 }
 
 // ---- the support lists ---------------------------------------------------------------------------
@@ -320,7 +331,7 @@ __global__ void __launch_bounds__(256) ksvd_pass2_kernel(T* __restrict__ Rm, T* 
         const P ov = *reinterpret_cast<const P*>(d + j);
 #pragma unroll
         for (int q = 0; q < V; ++q) {
-            const T dn = keep_d ? ov.v[q] : ksvd_div(uv.v[q], nrm);
+            const T dn = ksvd_new_atom(keep_d, ov, uv, q, nrm);
             acc = fmadd(acc, rv.v[q], conj_of(dn));
         }
         if (use_lds) *reinterpret_cast<P*>(slice + j) = rv;
@@ -335,7 +346,7 @@ __global__ void __launch_bounds__(256) ksvd_pass2_kernel(T* __restrict__ Rm, T* 
         P o;
 #pragma unroll
         for (int q = 0; q < V; ++q) {
-            const T dn = keep_d ? ov.v[q] : ksvd_div(uv.v[q], nrm);
+            const T dn = ksvd_new_atom(keep_d, ov, uv, q, nrm);
             o.v[q] = fmadd(fmadd(rv.v[q], g, ov.v[q]), mgn, dn);
         }
         *reinterpret_cast<P*>(r + j) = o;
@@ -346,10 +357,17 @@ __global__ void __launch_bounds__(256) ksvd_pass2_kernel(T* __restrict__ Rm, T* 
         const P ov = *reinterpret_cast<const P*>(d + j);
         P o;
 #pragma unroll
-        for (int q = 0; q < V; ++q) o.v[q] = keep_d ? ov.v[q] : ksvd_div(uv.v[q], nrm);
+        for (int q = 0; q < V; ++q) o.v[q] = ksvd_new_atom(keep_d, ov, uv, q, nrm);
         *reinterpret_cast<P*>(D + (long)k * F + j) = o;
     }
 }
+
+}  // namespace dcp
+
+// ---- the three kernels of the weighted sweep: they use the pieces above, the host path below launches them -----
+#include "ksvd_mask.hpp"
+
+namespace dcp {
 
 // ---- workspace ------------------------------------------------------------------------------------------------
 template <class T>
@@ -357,8 +375,9 @@ struct KsvdWs {
     T* R = nullptr;              // [N, F] the maintained residual
     T* Dold = nullptr;           // [K, F] D at the start of the sweep
     T* part = nullptr;           // [ceil(N / kKsvdChunk), F] pass-1 partials
+    real_t<T>* cpart = nullptr;  // the same shape, masked calls only: pass-1 partials of c
     T* ubuf = nullptr;           // [F] u of the atom in flight
-    real_t<T>* gpart = nullptr;  // [ceil(N / kKsvdChunk)] |g|^2 per chunk
+    real_t<T>* gpart = nullptr;  // [ceil(N / kKsvdChunk)] |g|^2 per chunk (unmasked; so are udd and dsq)
     real_t<T>* usq = nullptr;    // [ceil(F / 256)] |u|^2, d . u^H and |d|^2 per finish tile
     T* udd = nullptr;
     real_t<T>* dsq = nullptr;
@@ -372,7 +391,7 @@ struct KsvdWs {
 };
 
 template <class T>
-inline void ksvd_layout(WsLayout& a, KsvdWs<T>& w, int64_t N, int64_t F, int64_t K, int64_t s) {
+inline void ksvd_layout(WsLayout& a, KsvdWs<T>& w, int64_t N, int64_t F, int64_t K, int64_t s, bool masked) {
     a.take(w.R, (size_t)N * F);
     a.take(w.Dold, (size_t)K * F);
     a.take(w.part, (size_t)((N + kKsvdChunk - 1) / kKsvdChunk) * F);
@@ -388,6 +407,7 @@ inline void ksvd_layout(WsLayout& a, KsvdWs<T>& w, int64_t N, int64_t F, int64_t
     a.take(w.meta, (size_t)K + 4);
     a.take(w.mdpart, (size_t)kKsvdMdParts);
     if (scalar_traits<T>::is_complex) a.take(w.ext, (size_t)4 * K * F);
+    if (masked) a.take(w.cpart, (size_t)((N + kKsvdChunk - 1) / kKsvdChunk) * F);
 }
 
 // Enqueues the counting half of the list build: afterwards w.meta holds the largest row count and the column counts.
@@ -420,28 +440,46 @@ inline KsvdPass2Shape ksvd_pass2_shape(int F) {
     return KsvdPass2Shape{use_lds, waves, use_lds ? waves * row_bytes : 0};
 }
 
+// The mask of a sweep: M with a row stride of ms elements (F, or 0 for a 1-D mask); M == nullptr: no mask.
+template <class R>
+struct KsvdMask {
+    const R* M;
+    long ms;
+};
+
+// The K atoms in order, three launches each: the kernels of this file, or with a mask those of ksvd_mask.hpp.
 template <class T, int V>
-inline int ksvd_atoms(dcp_handle* h, T* X, T* D, int N, int F, int K, const int* cnt, KsvdWs<T>& w) {
+inline int ksvd_atoms(dcp_handle* h, KsvdMask<real_t<T>> m, T* X, T* D, int F, int K, const int* cnt, KsvdWs<T>& w) {
+    typedef real_t<T> R;
     hipStream_t st = h->stream;
     const long ntiles = ((long)F + 64L * V - 1) / (64L * V);
     const int nparts = (int)(((long)F + 255) / 256);
     const KsvdPass2Shape p2 = ksvd_pass2_shape<T>(F);
-    const int use_lds = p2.use_lds, waves = p2.waves;
-    const size_t lds = p2.lds;
+    const int* rows = w.rows;
+    const long long* off = w.off;
+    const T* Dold = w.Dold;
     for (int k = 0; k < K; ++k) {
         if (cnt[k] == 0) continue;
         const long nchunks = ((long)cnt[k] + kKsvdChunk - 1) / kKsvdChunk;
         if (nchunks * ntiles > 0x7fffffffL) return fail(h, DCP_ERR_INVALID, "ksvd: the pass-1 grid exceeds 2^31-1");
-        hipLaunchKernelGGL((ksvd_pass1_kernel<T, V>), dim3((unsigned)(nchunks * ntiles)), dim3(256), 0, st,
-                           (const T*)w.R, (const T*)X, (const int*)w.rows, (const long long*)w.off, k, K, (long)F,
-                           (int)ntiles, w.part, w.gpart);
-        hipLaunchKernelGGL((ksvd_finish_kernel<T>), dim3(nparts), dim3(256), 0, st, (const T*)w.part,
-                           (const real_t<T>*)w.gpart, (int)nchunks, k, (long)F, (const T*)w.Dold, w.ubuf, w.usq,
-                           w.udd, w.dsq);
-        hipLaunchKernelGGL((ksvd_pass2_kernel<T, V>), dim3((unsigned)((cnt[k] + waves - 1) / waves)),
-                           dim3(64 * waves), lds, st, w.R, X, (const int*)w.rows, (const long long*)w.off, k, K,
-                           (long)F, (const T*)w.Dold, D, (const T*)w.ubuf, (const real_t<T>*)w.usq,
-                           (const T*)w.udd, (const real_t<T>*)w.dsq, nparts, use_lds);
+        const dim3 g1((unsigned)(nchunks * ntiles)), g2((unsigned)((cnt[k] + p2.waves - 1) / p2.waves));
+        if (m.M) {
+            hipLaunchKernelGGL((ksvd_mask_pass1_kernel<T, V>), g1, dim3(256), 0, st, (const T*)w.R, m.M, m.ms,
+                               (const T*)X, rows, off, k, K, (long)F, (int)ntiles, w.part, w.cpart);
+            hipLaunchKernelGGL((ksvd_mask_finish_kernel<T>), dim3(nparts), dim3(256), 0, st, (const T*)w.part,
+                               (const R*)w.cpart, (int)nchunks, k, (long)F, Dold, w.ubuf, w.usq);
+            hipLaunchKernelGGL((ksvd_mask_pass2_kernel<T, V>), g2, dim3(64 * p2.waves), p2.lds, st, w.R, m.M, m.ms, X,
+                               rows, off, k, K, (long)F, Dold, D, (const T*)w.ubuf, (const R*)w.usq, nparts,
+                               p2.use_lds);
+        } else {
+            hipLaunchKernelGGL((ksvd_pass1_kernel<T, V>), g1, dim3(256), 0, st, (const T*)w.R, (const T*)X, rows, off,
+                               k, K, (long)F, (int)ntiles, w.part, w.gpart);
+            hipLaunchKernelGGL((ksvd_finish_kernel<T>), dim3(nparts), dim3(256), 0, st, (const T*)w.part,
+                               (const R*)w.gpart, (int)nchunks, k, (long)F, Dold, w.ubuf, w.usq, w.udd, w.dsq);
+            hipLaunchKernelGGL((ksvd_pass2_kernel<T, V>), g2, dim3(64 * p2.waves), p2.lds, st, w.R, X, rows, off, k,
+                               K, (long)F, Dold, D, (const T*)w.ubuf, (const R*)w.usq, (const T*)w.udd,
+                               (const R*)w.dsq, nparts, p2.use_lds);
+        }
         DCP_LAUNCH_OK(h, hipGetLastError());
     }
     return DCP_OK;
@@ -477,12 +515,16 @@ inline int ksvd_sweep_end(dcp_handle* h, const T* D, int F, int K, KsvdWs<T>& w)
 // Steps 2 and 3 on X whose counts (cnt [K], host) ksvd_count produced: the lists, R = Y - X D, the K atoms, then
 // max|D_new - D_old| into w.mdpart.  Enqueues only, from this one call: no host round trip between atoms.
 template <class T>
-inline int ksvd_sweep(dcp_handle* h, const T* Y, T* X, T* D, int N, int F, int K, const int* cnt, KsvdWs<T>& w) {
+inline int ksvd_sweep(dcp_handle* h, const T* Y, KsvdMask<real_t<T>> m, T* X, T* D, int N, int F, int K,
+                      const int* cnt, KsvdWs<T>& w) {
+    constexpr int V = ksvd_vec<T>();
     DCP_TRY(ksvd_sweep_begin<T>(h, Y, X, D, N, F, K, w));
-    // 16-byte accesses where every row of R, D and the partials starts on a 16-byte boundary
-    const bool vec = ksvd_vec<T>() > 1 && ((size_t)F * sizeof(T)) % 16 == 0 && al16_ptr(D);
-    if (vec) DCP_TRY((ksvd_atoms<T, ksvd_vec<T>()>(h, X, D, N, F, K, cnt, w)));
-    else DCP_TRY((ksvd_atoms<T, 1>(h, X, D, N, F, K, cnt, w)));
+    // 16-byte accesses where every row of R, D and the partials starts on a 16-byte boundary and, with a mask, every
+    // mask row is aligned for its V reals (F is then a multiple of V, so the rows are where M is)
+    const bool vec = V > 1 && ((size_t)F * sizeof(T)) % 16 == 0 && al16_ptr(D) &&
+                     (!m.M || reinterpret_cast<uintptr_t>(m.M) % (V * sizeof(real_t<T>)) == 0);
+    if (vec) DCP_TRY((ksvd_atoms<T, V>(h, m, X, D, F, K, cnt, w)));
+    else DCP_TRY((ksvd_atoms<T, 1>(h, m, X, D, F, K, cnt, w)));
     return ksvd_sweep_end<T>(h, D, F, K, w);
 }
 
@@ -506,55 +548,55 @@ inline int ksvd_read_maxdiff(dcp_handle* h, const double* mdpart, long n, double
     return read_partial_max(h, mdpart, grid_for(n, kKsvdMdParts), reinterpret_cast<double*>(hostv), maxdiff_out);
 }
 
-inline int ksvd_check_sizes(dcp_handle* h, int64_t N, int64_t F, int64_t K) {
-    if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
-    if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL)
-        return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
-    return DCP_OK;
-}
-
+// The entries.  masked false (dcp_ksvd_sweep_*, dcp_ksvd_step_*): M, mask_ndim and rows_per_pass are nullptr, 0, 0;
+// masked true (dcp_ksvd_mask_*): a null mask and mask_ndim outside {1, 2} are refused.
 template <class T>
-inline int ksvd_sweep_api(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, int64_t K, int row_nnz_max,
-                          double* maxdiff_out) {
+inline int ksvd_sweep_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, bool masked, T* X, T* D,
+                          int64_t N, int64_t F, int64_t K, int row_nnz_max, double* maxdiff_out) {
     if (!h) return DCP_ERR_INVALID;
-    if (!Y || !X || !D || !maxdiff_out) return fail(h, DCP_ERR_INVALID, "null pointer");
-    DCP_TRY(ksvd_check_sizes(h, N, F, K));
+    if (!Y || (masked && !M) || !X || !D || !maxdiff_out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (masked) DCP_TRY(omp_check_mask(h, "ksvd", mask_ndim, 0));
+    DCP_TRY(omp_check_sizes(h, N, F, K));
     if (row_nnz_max < 1 || row_nnz_max > K) return fail(h, DCP_ERR_INVALID, "ksvd: row_nnz_max must be in [1, K]");
     DCP_HIP_OK(h, hipSetDevice(h->device));
     KsvdWs<T> w;
-    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { ksvd_layout<T>(a, w, N, F, K, row_nnz_max); }));
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { ksvd_layout<T>(a, w, N, F, K, row_nnz_max, masked); }));
     DCP_TRY(ksvd_count<T>(h, X, (int)N, (int)K, w));
     int* host = nullptr;
     DCP_TRY(ksvd_read_counts(h, w.meta, (int)K, nullptr, &host));
     if (host[0] > row_nnz_max)
         return fail(h, DCP_ERR_INVALID, "ksvd: a row of X has " + std::to_string(host[0]) +
                                             " non-zeros, more than row_nnz_max = " + std::to_string(row_nnz_max));
-    DCP_TRY(ksvd_sweep<T>(h, Y, X, D, (int)N, (int)F, (int)K, host + 4, w));
+    const KsvdMask<real_t<T>> m{M, mask_ndim == 2 ? (long)F : 0L};
+    DCP_TRY(ksvd_sweep<T>(h, Y, m, X, D, (int)N, (int)F, (int)K, host + 4, w));
     return ksvd_read_maxdiff(h, w.mdpart, (long)K * F, maxdiff_out);
 }
 
+// The coder (OmpCoder: plain OMP, or the masked coder as dcp_omp_mask_* runs it), then the sweep, over one
+// workspace layout.
 template <class T>
-inline int ksvd_step_api(dcp_handle* h, const T* Y, T* X, T* D, int64_t N, int64_t F, int64_t K, int n_nonzero,
-                         double coef_tol, double* maxdiff_out, int* it_out) {
+inline int ksvd_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, bool masked, T* X, T* D,
+                         int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                         double* maxdiff_out, int* it_out) {
     if (!h) return DCP_ERR_INVALID;
-    if (!Y || !X || !D || !maxdiff_out || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
-    DCP_TRY(ksvd_check_sizes(h, N, F, K));
-    if (coef_tol != coef_tol) return fail(h, DCP_ERR_INVALID, "omp: tol is NaN");
-    DCP_TRY(omp_check_sparsity(h, K, n_nonzero, omp_cap<T>()));
+    if (!Y || (masked && !M) || !X || !D || !maxdiff_out || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (masked) DCP_TRY(omp_check_mask(h, "ksvd", mask_ndim, rows_per_pass));
+    DCP_TRY(omp_check_problem<T>(h, N, F, K, n_nonzero, coef_tol));
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    LassoWs<T> lw;
+    OmpCoder<T> coder(M, mask_ndim, rows_per_pass);
     KsvdWs<T> w;
     DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
-        omp_layout<T>(a, lw, N, F, K);
-        ksvd_layout<T>(a, w, N, F, K, n_nonzero);
+        coder.layout(a, N, F, K, n_nonzero);
+        ksvd_layout<T>(a, w, N, F, K, n_nonzero, masked);
     }));
-    DCP_TRY(omp_solve<T>(h, Y, (const T*)D, X, (int)N, (int)F, (int)K, n_nonzero, coef_tol, lw));
+    DCP_TRY(coder.solve(h, Y, (const T*)D, X, N, F, K, n_nonzero, coef_tol));
     DCP_TRY(ksvd_count<T>(h, X, (int)N, (int)K, w));
     int* host = nullptr;
-    DCP_TRY(ksvd_read_counts(h, w.meta, (int)K, lw.flag, &host));
+    DCP_TRY(ksvd_read_counts(h, w.meta, (int)K, coder.it_dev(), &host));
     *it_out = host[K + 4];
     if (host[0] > n_nonzero) return fail(h, DCP_ERR_INTERNAL, "ksvd: the coder returned a row beyond the sparsity");
-    DCP_TRY(ksvd_sweep<T>(h, Y, X, D, (int)N, (int)F, (int)K, host + 4, w));
+    const KsvdMask<real_t<T>> m{M, mask_ndim == 2 ? (long)F : 0L};
+    DCP_TRY(ksvd_sweep<T>(h, Y, m, X, D, (int)N, (int)F, (int)K, host + 4, w));
     return ksvd_read_maxdiff(h, w.mdpart, (long)K * F, maxdiff_out);
 }
 

@@ -39,13 +39,11 @@
 // 16-byte path on R and D is taken only where the mask rows are aligned for that share.
 // Each atom makes two reads and one write of its support rows of R and two reads of the same rows of M:
 // sum_k |I_k| F (3 sizeof(T) + 2 sizeof(real)) bytes per sweep.
+//
+// This file holds the three kernels only and is included by ksvd.hpp, between its own kernels (whose KsvdPack,
+// ksvd_div, ksvd_new_atom and ksvd_lane_sum these use) and the one host path that launches either set: include
+// ksvd.hpp, not this file.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "ksvd.hpp"
-#include "omp_mask.hpp"
 
 namespace dcp {
 
@@ -202,7 +200,7 @@ __global__ void __launch_bounds__(256) ksvd_mask_pass2_kernel(T* __restrict__ Rm
         const P ov = *reinterpret_cast<const P*>(d + j);
 #pragma unroll
         for (int q = 0; q < V; ++q) {
-            const T dn = keep_d ? ov.v[q] : ksvd_div(uv.v[q], nrm);
+            const T dn = ksvd_new_atom(keep_d, ov, uv, q, nrm);
             const T dc = conj_of(dn);
             sr = fmadd(sr, scale(rv.v[q], mv.v[q]), dc);
             sd = fmadd(sd, scale(ov.v[q], mv.v[q]), dc);
@@ -223,7 +221,7 @@ __global__ void __launch_bounds__(256) ksvd_mask_pass2_kernel(T* __restrict__ Rm
         P o;
 #pragma unroll
         for (int q = 0; q < V; ++q) {
-            const T dn = keep_d ? ov.v[q] : ksvd_div(uv.v[q], nrm);
+            const T dn = ksvd_new_atom(keep_d, ov, uv, q, nrm);
             o.v[q] = fmadd(fmadd(rv.v[q], g, ov.v[q]), mgn, dn);
         }
         *reinterpret_cast<P*>(r + j) = o;
@@ -234,143 +232,9 @@ __global__ void __launch_bounds__(256) ksvd_mask_pass2_kernel(T* __restrict__ Rm
         const P ov = *reinterpret_cast<const P*>(d + j);
         P o;
 #pragma unroll
-        for (int q = 0; q < V; ++q) o.v[q] = keep_d ? ov.v[q] : ksvd_div(uv.v[q], nrm);
+        for (int q = 0; q < V; ++q) o.v[q] = ksvd_new_atom(keep_d, ov, uv, q, nrm);
         *reinterpret_cast<P*>(D + (long)k * F + j) = o;
     }
-}
-
-// ---- workspace: that of ksvd.hpp (gpart, udd and dsq stay unused) and the second partial buffer ------------------
-template <class T>
-struct KsvdMaskWs {
-    KsvdWs<T> k;
-    real_t<T>* cpart = nullptr;   // [ceil(N / kKsvdChunk), F] pass-1 partials of c
-};
-
-template <class T>
-inline void ksvd_mask_layout(WsLayout& a, KsvdMaskWs<T>& w, int64_t N, int64_t F, int64_t K, int64_t s) {
-    ksvd_layout<T>(a, w.k, N, F, K, s);
-    a.take(w.cpart, (size_t)((N + kKsvdChunk - 1) / kKsvdChunk) * F);
-}
-
-template <class T, int V>
-inline int ksvd_mask_atoms(dcp_handle* h, const real_t<T>* M, long ms, T* X, T* D, int F, int K, const int* cnt,
-                           KsvdMaskWs<T>& mw) {
-    KsvdWs<T>& w = mw.k;
-    hipStream_t st = h->stream;
-    const long ntiles = ((long)F + 64L * V - 1) / (64L * V);
-    const int nparts = (int)(((long)F + 255) / 256);
-    const KsvdPass2Shape p2 = ksvd_pass2_shape<T>(F);
-    for (int k = 0; k < K; ++k) {
-        if (cnt[k] == 0) continue;
-        const long nchunks = ((long)cnt[k] + kKsvdChunk - 1) / kKsvdChunk;
-        if (nchunks * ntiles > 0x7fffffffL) return fail(h, DCP_ERR_INVALID, "ksvd: the pass-1 grid exceeds 2^31-1");
-        hipLaunchKernelGGL((ksvd_mask_pass1_kernel<T, V>), dim3((unsigned)(nchunks * ntiles)), dim3(256), 0, st,
-                           (const T*)w.R, M, ms, (const T*)X, (const int*)w.rows, (const long long*)w.off, k, K,
-                           (long)F, (int)ntiles, w.part, mw.cpart);
-        hipLaunchKernelGGL((ksvd_mask_finish_kernel<T>), dim3(nparts), dim3(256), 0, st, (const T*)w.part,
-                           (const real_t<T>*)mw.cpart, (int)nchunks, k, (long)F, (const T*)w.Dold, w.ubuf, w.usq);
-        hipLaunchKernelGGL((ksvd_mask_pass2_kernel<T, V>), dim3((unsigned)((cnt[k] + p2.waves - 1) / p2.waves)),
-                           dim3(64 * p2.waves), p2.lds, st, w.R, M, ms, X, (const int*)w.rows,
-                           (const long long*)w.off, k, K, (long)F, (const T*)w.Dold, D, (const T*)w.ubuf,
-                           (const real_t<T>*)w.usq, nparts, p2.use_lds);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-    }
-    return DCP_OK;
-}
-
-// ksvd_sweep with the weighted atoms.  Enqueues only.
-template <class T>
-inline int ksvd_mask_sweep(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, T* X, T* D, int N, int F,
-                           int K, const int* cnt, KsvdMaskWs<T>& mw) {
-    constexpr int V = ksvd_vec<T>();
-    DCP_TRY(ksvd_sweep_begin<T>(h, Y, X, D, N, F, K, mw.k));
-    const long ms = mask_ndim == 2 ? (long)F : 0L;
-    // 16-byte accesses where ksvd_sweep takes them and every mask row is aligned for its V reals (F is then a
-    // multiple of V, so the rows are where M is)
-    const bool vec = V > 1 && ((size_t)F * sizeof(T)) % 16 == 0 && al16_ptr(D) &&
-                     reinterpret_cast<uintptr_t>(M) % (V * sizeof(real_t<T>)) == 0;
-    if (vec) DCP_TRY((ksvd_mask_atoms<T, V>(h, M, ms, X, D, F, K, cnt, mw)));
-    else DCP_TRY((ksvd_mask_atoms<T, 1>(h, M, ms, X, D, F, K, cnt, mw)));
-    return ksvd_sweep_end<T>(h, D, F, K, mw.k);
-}
-
-inline int ksvd_mask_check_mask(dcp_handle* h, int mask_ndim) {
-    if (mask_ndim != 1 && mask_ndim != 2) return fail(h, DCP_ERR_INVALID, "ksvd: mask_ndim must be 1 or 2");
-    return DCP_OK;
-}
-
-template <class T>
-inline int ksvd_mask_sweep_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, T* X, T* D, int64_t N,
-                               int64_t F, int64_t K, int row_nnz_max, double* maxdiff_out) {
-    if (!h) return DCP_ERR_INVALID;
-    if (!Y || !M || !X || !D || !maxdiff_out) return fail(h, DCP_ERR_INVALID, "null pointer");
-    DCP_TRY(ksvd_mask_check_mask(h, mask_ndim));
-    DCP_TRY(ksvd_check_sizes(h, N, F, K));
-    if (row_nnz_max < 1 || row_nnz_max > K) return fail(h, DCP_ERR_INVALID, "ksvd: row_nnz_max must be in [1, K]");
-    DCP_HIP_OK(h, hipSetDevice(h->device));
-    KsvdMaskWs<T> w;
-    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { ksvd_mask_layout<T>(a, w, N, F, K, row_nnz_max); }));
-    DCP_TRY(ksvd_count<T>(h, X, (int)N, (int)K, w.k));
-    int* host = nullptr;
-    DCP_TRY(ksvd_read_counts(h, w.k.meta, (int)K, nullptr, &host));
-    if (host[0] > row_nnz_max)
-        return fail(h, DCP_ERR_INVALID, "ksvd: a row of X has " + std::to_string(host[0]) +
-                                            " non-zeros, more than row_nnz_max = " + std::to_string(row_nnz_max));
-    DCP_TRY(ksvd_mask_sweep<T>(h, Y, M, mask_ndim, X, D, (int)N, (int)F, (int)K, host + 4, w));
-    return ksvd_read_maxdiff(h, w.k.mdpart, (long)K * F, maxdiff_out);
-}
-
-// The masked coder (as omp_mask_api runs it: the residual form for a 2-D mask, the Gram form on sqrt(m) y, sqrt(m) A
-// for a 1-D one), then the sweep, over one workspace layout.
-template <class T>
-inline int ksvd_mask_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, T* X, T* D, int64_t N,
-                              int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
-                              double* maxdiff_out, int* it_out) {
-    if (!h) return DCP_ERR_INVALID;
-    if (!Y || !M || !X || !D || !maxdiff_out || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
-    DCP_TRY(ksvd_mask_check_mask(h, mask_ndim));
-    if (rows_per_pass < 0) return fail(h, DCP_ERR_INVALID, "omp: rows_per_pass must not be negative");
-    DCP_TRY(ksvd_check_sizes(h, N, F, K));
-    if (coef_tol != coef_tol) return fail(h, DCP_ERR_INVALID, "omp: tol is NaN");
-    DCP_TRY(omp_check_sparsity(h, K, n_nonzero, omp_cap<T>()));
-    DCP_HIP_OK(h, hipSetDevice(h->device));
-    KsvdMaskWs<T> w;
-    const int* it_dev = nullptr;
-    if (mask_ndim == 1) {
-        LassoWs<T> lw;
-        T* Ys = nullptr;
-        T* As = nullptr;
-        DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
-            a.take(Ys, (size_t)N * F);
-            a.take(As, (size_t)K * F);
-            omp_layout<T>(a, lw, N, F, K);
-            ksvd_mask_layout<T>(a, w, N, F, K, n_nonzero);
-        }));
-        hipLaunchKernelGGL((omp_mask_sqrt_scale_kernel<T>), dim3(grid_for((long)N * F)), dim3(256), 0, h->stream, Y, M,
-                           (long)N, (long)F, Ys);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((omp_mask_sqrt_scale_kernel<T>), dim3(grid_for((long)K * F)), dim3(256), 0, h->stream,
-                           (const T*)D, M, (long)K, (long)F, As);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        DCP_TRY(omp_solve<T>(h, Ys, As, X, (int)N, (int)F, (int)K, n_nonzero, coef_tol, lw));
-        it_dev = lw.flag;
-    } else {
-        const int64_t Nc = omp_mask_rows_per_pass<T>(N, F, K, n_nonzero, rows_per_pass);
-        OmpMaskWs<T> ow;
-        DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
-            omp_mask_layout<T>(a, ow, Nc, F, K, n_nonzero);
-            ksvd_mask_layout<T>(a, w, N, F, K, n_nonzero);
-        }));
-        DCP_TRY(omp_mask_solve<T>(h, Y, M, (const T*)D, X, N, (int)F, (int)K, n_nonzero, coef_tol, Nc, ow));
-        it_dev = ow.it;
-    }
-    DCP_TRY(ksvd_count<T>(h, X, (int)N, (int)K, w.k));
-    int* host = nullptr;
-    DCP_TRY(ksvd_read_counts(h, w.k.meta, (int)K, it_dev, &host));
-    *it_out = host[K + 4];
-    if (host[0] > n_nonzero) return fail(h, DCP_ERR_INTERNAL, "ksvd: the coder returned a row beyond the sparsity");
-    DCP_TRY(ksvd_mask_sweep<T>(h, Y, M, mask_ndim, X, D, (int)N, (int)F, (int)K, host + 4, w));
-    return ksvd_read_maxdiff(h, w.k.mdpart, (long)K * F, maxdiff_out);
 }
 
 }  // namespace dcp

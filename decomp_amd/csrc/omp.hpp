@@ -357,21 +357,23 @@ inline int omp_solve(dcp_handle* h, const T* Y, const T* A, T* X, int N, int F, 
 // *it_out = the device word, after the stream has run
 inline int omp_read_it(dcp_handle* h, const int* it_dev, int* it_out) { return read_scalar(h, it_dev, it_out); }
 
-template <class T>
-inline int omp_api(dcp_handle* h, const T* Y, const T* A, T* X, int64_t N, int64_t F, int64_t K, int n_nonzero,
-                   double tol, int* it_out) {
-    if (!h) return DCP_ERR_INVALID;
-    if (!Y || !A || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
+// The argument checks every OMP and K-SVD entry shares, in this order: sizes, tol, sparsity.  An entry without a
+// channel axis (omp_gram_api) passes F = 1; one without a coder (the K-SVD sweep) takes the sizes part alone.
+inline int omp_check_sizes(dcp_handle* h, int64_t N, int64_t F, int64_t K) {
     if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
     if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL)
         return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
+    return DCP_OK;
+}
+
+// ynorm2_missing: omp_gram_api's tol >= 0 without the row norms, refused where it always was (before the sparsity)
+template <class T>
+inline int omp_check_problem(dcp_handle* h, int64_t N, int64_t F, int64_t K, int n_nonzero, double tol,
+                             bool ynorm2_missing = false) {
+    DCP_TRY(omp_check_sizes(h, N, F, K));
     if (tol != tol) return fail(h, DCP_ERR_INVALID, "omp: tol is NaN");
-    DCP_TRY(omp_check_sparsity(h, K, n_nonzero, omp_cap<T>()));
-    DCP_HIP_OK(h, hipSetDevice(h->device));
-    LassoWs<T> w;
-    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { omp_layout<T>(a, w, N, F, K); }));
-    DCP_TRY(omp_solve<T>(h, Y, A, X, (int)N, (int)F, (int)K, n_nonzero, tol, w));
-    return omp_read_it(h, w.flag, it_out);
+    if (ynorm2_missing) return fail(h, DCP_ERR_INVALID, "omp: ynorm2 is null but tol >= 0");
+    return omp_check_sparsity(h, K, n_nonzero, omp_cap<T>());
 }
 
 template <class T>
@@ -380,11 +382,7 @@ inline int omp_gram_api(dcp_handle* h, const T* alpha0, const T* G, const real_t
     typedef real_t<T> R;
     if (!h) return DCP_ERR_INVALID;
     if (!alpha0 || !G || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
-    if (N <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
-    if (N > 0x7fffffffLL || K > 0x7fffffffLL) return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
-    if (tol != tol) return fail(h, DCP_ERR_INVALID, "omp: tol is NaN");
-    if (tol >= 0.0 && !ynorm2) return fail(h, DCP_ERR_INVALID, "omp: ynorm2 is null but tol >= 0");
-    DCP_TRY(omp_check_sparsity(h, K, n_nonzero, omp_cap<T>()));
+    DCP_TRY(omp_check_problem<T>(h, N, 1, K, n_nonzero, tol, tol >= 0.0 && !ynorm2));
     DCP_HIP_OK(h, hipSetDevice(h->device));
     R* invn = nullptr;
     int* it_dev = nullptr;

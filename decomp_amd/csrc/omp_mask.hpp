@@ -429,43 +429,82 @@ inline int omp_mask_solve(dcp_handle* h, const T* Y, const real_t<T>* M, const T
     return DCP_OK;
 }
 
+// The coder of every entry that codes rows by OMP (dcp_omp_*, dcp_omp_mask_*, the K-SVD steps).  How a mask selects
+// the route is decided here and nowhere else:
+//   mask_ndim 0  no mask: omp_solve
+//   mask_ndim 1  one shared mask, one shared Gram matrix: omp_solve on sqrt(m) y, sqrt(m) A (Ys, As)
+//   mask_ndim 2  omp_mask_solve in passes of Nc rows
+// layout() takes the route's workspace (a caller appends its own items after it), solve() enqueues only, and
+// it_dev() is the device word that holds the step count once the stream has run.
 template <class T>
-inline int omp_mask_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, const T* A, T* X, int64_t N,
-                        int64_t F, int64_t K, int n_nonzero, double tol, int rows_per_pass, int* it_out) {
+struct OmpCoder {
     typedef real_t<T> R;
-    if (!h) return DCP_ERR_INVALID;
-    if (!Y || !M || !A || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
-    if (mask_ndim != 1 && mask_ndim != 2) return fail(h, DCP_ERR_INVALID, "omp: mask_ndim must be 1 or 2");
-    if (rows_per_pass < 0) return fail(h, DCP_ERR_INVALID, "omp: rows_per_pass must not be negative");
-    if (N <= 0 || F <= 0 || K <= 0) return fail(h, DCP_ERR_INVALID, "sizes must be positive");
-    if (N > 0x7fffffffLL || F > 0x7fffffffLL || K > 0x7fffffffLL)
-        return fail(h, DCP_ERR_INVALID, "dimension exceeds 2^31-1");
-    if (tol != tol) return fail(h, DCP_ERR_INVALID, "omp: tol is NaN");
-    DCP_TRY(omp_check_sparsity(h, K, n_nonzero, omp_cap<T>()));
-    DCP_HIP_OK(h, hipSetDevice(h->device));
-    if (mask_ndim == 1) {   // one shared mask, one shared Gram matrix: the Gram form on sqrt(m) y, sqrt(m) A
-        LassoWs<T> lw;
-        T* Ys = nullptr;
-        T* As = nullptr;
-        DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
+    const R* M;
+    int mask_ndim, rows_per_pass;
+    LassoWs<T> lw;
+    OmpMaskWs<T> ow;
+    T* Ys = nullptr;
+    T* As = nullptr;
+    int64_t Nc = 0;
+
+    OmpCoder(const R* M_, int ndim, int rpp) : M(M_), mask_ndim(ndim), rows_per_pass(rpp) {}
+
+    void layout(WsLayout& a, int64_t N, int64_t F, int64_t K, int s) {
+        if (mask_ndim == 2) {
+            Nc = omp_mask_rows_per_pass<T>(N, F, K, s, rows_per_pass);
+            omp_mask_layout<T>(a, ow, Nc, F, K, s);
+            return;
+        }
+        if (mask_ndim == 1) {
             a.take(Ys, (size_t)N * F);
             a.take(As, (size_t)K * F);
-            omp_layout<T>(a, lw, N, F, K);
-        }));
-        hipLaunchKernelGGL((omp_mask_sqrt_scale_kernel<T>), dim3(grid_for((long)N * F)), dim3(256), 0, h->stream, Y, M,
-                           (long)N, (long)F, Ys);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((omp_mask_sqrt_scale_kernel<T>), dim3(grid_for((long)K * F)), dim3(256), 0, h->stream, A, M,
-                           (long)K, (long)F, As);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        DCP_TRY(omp_solve<T>(h, Ys, As, X, (int)N, (int)F, (int)K, n_nonzero, tol, lw));
-        return omp_read_it(h, lw.flag, it_out);
+        }
+        omp_layout<T>(a, lw, N, F, K);
     }
-    const int64_t Nc = omp_mask_rows_per_pass<T>(N, F, K, n_nonzero, rows_per_pass);
-    OmpMaskWs<T> w;
-    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { omp_mask_layout<T>(a, w, Nc, F, K, n_nonzero); }));
-    DCP_TRY(omp_mask_solve<T>(h, Y, M, A, X, N, (int)F, (int)K, n_nonzero, tol, Nc, w));
-    return omp_read_it(h, w.it, it_out);
+
+    int sqrt_scale(dcp_handle* h, const T* a, int64_t rows, int64_t F, T* out) const {
+        hipLaunchKernelGGL((omp_mask_sqrt_scale_kernel<T>), dim3(grid_for((long)rows * F)), dim3(256), 0, h->stream, a, M,
+                           (long)rows, (long)F, out);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        return DCP_OK;
+    }
+
+    int solve(dcp_handle* h, const T* Y, const T* A, T* X, int64_t N, int64_t F, int64_t K, int s, double tol) {
+        if (mask_ndim == 2) return omp_mask_solve<T>(h, Y, M, A, X, N, (int)F, (int)K, s, tol, Nc, ow);
+        if (mask_ndim == 1) {
+            DCP_TRY(sqrt_scale(h, Y, N, F, Ys));
+            DCP_TRY(sqrt_scale(h, A, K, F, As));
+            Y = Ys;
+            A = As;
+        }
+        return omp_solve<T>(h, Y, A, X, (int)N, (int)F, (int)K, s, tol, lw);
+    }
+
+    const int* it_dev() const { return mask_ndim == 2 ? ow.it : lw.flag; }
+};
+
+// What a masked entry refuses about its mask arguments, after the null pointers and before the sizes (`who` is the
+// entry's family in the message; an entry without passes gives rows_per_pass = 0).
+inline int omp_check_mask(dcp_handle* h, const char* who, int mask_ndim, int rows_per_pass) {
+    if (mask_ndim != 1 && mask_ndim != 2)
+        return fail(h, DCP_ERR_INVALID, std::string(who) + ": mask_ndim must be 1 or 2");
+    if (rows_per_pass < 0) return fail(h, DCP_ERR_INVALID, "omp: rows_per_pass must not be negative");
+    return DCP_OK;
+}
+
+// dcp_omp_* (masked false: M, mask_ndim and rows_per_pass are nullptr, 0, 0) and dcp_omp_mask_*
+template <class T>
+inline int omp_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, bool masked, const T* A, T* X,
+                   int64_t N, int64_t F, int64_t K, int n_nonzero, double tol, int rows_per_pass, int* it_out) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!Y || (masked && !M) || !A || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (masked) DCP_TRY(omp_check_mask(h, "omp", mask_ndim, rows_per_pass));
+    DCP_TRY(omp_check_problem<T>(h, N, F, K, n_nonzero, tol));
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    OmpCoder<T> coder(M, mask_ndim, rows_per_pass);
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { coder.layout(a, N, F, K, n_nonzero); }));
+    DCP_TRY(coder.solve(h, Y, A, X, N, F, K, n_nonzero, tol));
+    return omp_read_it(h, coder.it_dev(), it_out);
 }
 
 }  // namespace dcp

@@ -55,15 +55,11 @@ def solve(y, D, n_nonzero_coefs, tol=1.0e-3, maxiter=1000, coef_tol=None, mask=N
     """
     kind = get_array_module(y, D, mask)
     assertion.assert_dtypes(y=y, D=D)
-    assertion.assert_dtypes(mask=mask, dtypes='f')
-    assertion.assert_nonnegative_host_or_device(mask)
+    assertion.assert_mask(mask)
     assertion.assert_ndim('y', y, ndim=2)
     assertion.assert_ndim('D', D, ndim=2)
     assertion.assert_shapes('y', y, 'D', D, axes=[-1])
-    if mask is not None and len(mask.shape) == 1:
-        assertion.assert_shapes('y', y, 'mask', mask, axes=[-1])
-    else:
-        assertion.assert_shapes('y', y, 'mask', mask)
+    assertion.assert_mask_shape(y, mask)
     K, F = int(D.shape[0]), int(D.shape[1])
     s = omp.check_sparsity(n_nonzero_coefs, K, _arrays.np_dtype(D))
     coef_tol_c = omp.check_tol(coef_tol, what='coef_tol')
@@ -80,17 +76,13 @@ def solve(y, D, n_nonzero_coefs, tol=1.0e-3, maxiter=1000, coef_tol=None, mask=N
         _arrays.l2_normalize_(Dd, strict=True)
         maxdiff = ctypes.c_double(0.0)
         omp_it = ctypes.c_int(0)
-        if mask is None:
+        md, mask_ndim = _arrays.mask_to_device(mask, yd, N, F)
+        if md is None:
             name = 'dcp_ksvd_step_' + _arrays.suffix(Dd)
             args = (_arrays.ptr(yd), _arrays.ptr(xd), _arrays.ptr(Dd), N, F, K, s, coef_tol_c)
         else:
-            md = _arrays.to_device(mask, dev)
-            rdt = torch.float64 if yd.dtype in (torch.float64, torch.complex128) else torch.float32
-            if md.dtype != rdt:
-                md = md.to(rdt)
-            md = md.contiguous()
             name = 'dcp_ksvd_mask_step_' + _arrays.suffix(Dd)
-            args = (_arrays.ptr(yd), _arrays.ptr(md), md.dim(), _arrays.ptr(xd), _arrays.ptr(Dd), N, F, K, s,
+            args = (_arrays.ptr(yd), _arrays.ptr(md), mask_ndim, _arrays.ptr(xd), _arrays.ptr(Dd), N, F, K, s,
                     coef_tol_c, 0)
         try:
             for it in range(1, maxiter):

@@ -94,16 +94,12 @@ def solve(y, A, alpha, x=None, tol=1.0e-3, method='ista', maxiter=1000,
         x = _ZerosLike(tuple(y.shape[:-1]) + (A.shape[0],), _arrays.np_dtype(y))
 
     assertion.assert_dtypes(y=y, A=A, x=x)                            # lasso.py:76-87
-    assertion.assert_dtypes(mask=mask, dtypes='f')
-    assertion.assert_nonnegative_host_or_device(mask)
+    assertion.assert_mask(mask)
     assertion.assert_ndim('A', A, ndim=2)
     assertion.assert_shapes('x', x, 'A', A, axes=1)
     assertion.assert_shapes('y', y, 'x', x, axes=np.arange(len(x.shape) - 1).tolist())
     assertion.assert_shapes('y', y, 'A', A, axes=[-1])
-    if mask is not None and len(mask.shape) == 1:
-        assertion.assert_shapes('y', y, 'mask', mask, axes=[-1])
-    else:
-        assertion.assert_shapes('y', y, 'mask', mask)
+    assertion.assert_mask_shape(y, mask)
     if method not in AVAILABLE_METHODS + AVAILABLE_NNLS_METHODS:      # lasso.py:88-90
         raise ValueError('Available methods are {0:s}. Given {1:s}'.format(
                             str(AVAILABLE_METHODS), method))
@@ -143,20 +139,7 @@ def solve_fastpath(y, A, alpha, x, tol, maxiter, method, xp, mask=None, **kwargs
     else:
         xd = _arrays.to_device(x, dev, copy=True).reshape(N, K)
     sfx = _arrays.suffix(yd)
-    rdt = {'f32': torch.float32, 'f64': torch.float64, 'c64': torch.float32,
-           'c128': torch.float64}[sfx]
-    mask_ndim = 0
-    md = None
-    if mask is not None:
-        md = _arrays.to_device(mask, dev)
-        if md.dtype != rdt:
-            md = md.to(rdt)
-        if md.dim() == 1:
-            mask_ndim = 1
-        else:
-            mask_ndim = 2
-            md = md.reshape(N, F)
-        md = md.contiguous()
+    md, mask_ndim = _arrays.mask_to_device(mask, yd, N, F)
     lib, h = _arrays.lib_handle(yd)
     it = ctypes.c_int(0)
     y2 = y2.contiguous()

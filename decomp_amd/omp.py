@@ -67,14 +67,10 @@ def solve(y, A, n_nonzero_coefs=None, tol=None, mask=None):
     """
     kind = get_array_module(y, A, mask)
     assertion.assert_dtypes(y=y, A=A)
-    assertion.assert_dtypes(mask=mask, dtypes='f')
-    assertion.assert_nonnegative_host_or_device(mask)
+    assertion.assert_mask(mask)
     assertion.assert_ndim('A', A, ndim=2)
     assertion.assert_shapes('y', y, 'A', A, axes=[-1])
-    if mask is not None and len(mask.shape) == 1:
-        assertion.assert_shapes('y', y, 'mask', mask, axes=[-1])
-    else:
-        assertion.assert_shapes('y', y, 'mask', mask)
+    assertion.assert_mask_shape(y, mask)
     if n_nonzero_coefs is None and tol is None:
         raise ValueError('Either n_nonzero_coefs or tol must be given.')
     K, F = int(A.shape[0]), int(A.shape[1])
@@ -96,19 +92,12 @@ def solve(y, A, n_nonzero_coefs=None, tol=None, mask=None):
     it = ctypes.c_int(0)
     if N > 0:
         lib, h = _arrays.lib_handle(yd)
-        if mask is None:
+        md, mask_ndim = _arrays.mask_to_device(mask, yd, N, F)
+        if md is None:
             name = 'dcp_omp_' + _arrays.suffix(yd)
             rc = getattr(lib, name)(h, _arrays.ptr(y2), _arrays.ptr(Ad), _arrays.ptr(xd), N, F, K, s, tol_c,
                                     ctypes.byref(it))
         else:
-            md = _arrays.to_device(mask, dev)
-            rdt = torch.float64 if yd.dtype in (torch.float64, torch.complex128) else torch.float32
-            if md.dtype != rdt:
-                md = md.to(rdt)
-            mask_ndim = 1 if md.dim() == 1 else 2
-            if mask_ndim == 2:
-                md = md.reshape(N, F)
-            md = md.contiguous()
             name = 'dcp_omp_mask_' + _arrays.suffix(yd)
             rc = getattr(lib, name)(h, _arrays.ptr(y2), _arrays.ptr(md), mask_ndim, _arrays.ptr(Ad), _arrays.ptr(xd),
                                     N, F, K, s, tol_c, 0, ctypes.byref(it))

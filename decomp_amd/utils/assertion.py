@@ -87,6 +87,21 @@ def assert_nonnegative_host_or_device(x):
     assert bool((x >= 0.0).all())
 
 
+def assert_mask(mask):
+    """The mask of lasso.solve, omp.solve and ksvd.solve, first half (lasso.py:77-78): a float array, non-negative.
+    None passes."""
+    assert_dtypes(mask=mask, dtypes='f')
+    assert_nonnegative_host_or_device(mask)
+
+
+def assert_mask_shape(y, mask):
+    """... second half, after the other shape checks (lasso.py:84-87): y's shape or, 1-D, y's last axis."""
+    if mask is not None and len(mask.shape) == 1:
+        assert_shapes('y', y, 'mask', mask, axes=[-1])
+    else:
+        assert_shapes('y', y, 'mask', mask)
+
+
 def assert_positive(x):
     """assertion.py:87-92: every element satisfies x > 0 (NaN fails).  NumPy arrays are scanned on the host,
     torch tensors where they live (argument validation, not part of the compute path)."""
