@@ -111,6 +111,14 @@ SIGNATURES = {
     'dcp_ksvd_mask_step_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int)]),
     'dcp_ksvd_mask_step_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int)]),
     'dcp_ksvd_mask_step_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int)]),
+    'dcp_ksvd_clean_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_int), _P(_c_int)]),
+    'dcp_ksvd_clean_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_int), _P(_c_int)]),
+    'dcp_ksvd_clean_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_int), _P(_c_int)]),
+    'dcp_ksvd_clean_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_int), _P(_c_int)]),
+    'dcp_ksvd_clean_step_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int), _c_f64, _c_f64, _P(_c_int)]),
+    'dcp_ksvd_clean_step_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int), _c_f64, _c_f64, _P(_c_int)]),
+    'dcp_ksvd_clean_step_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int), _c_f64, _c_f64, _P(_c_int)]),
+    'dcp_ksvd_clean_step_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int), _c_f64, _c_f64, _P(_c_int)]),
     'dcp_dict_stats_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
     'dcp_dict_update_f32': (_c_int, [_c_vp, _c_vp, _c_f64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
     'dcp_dict_step_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),

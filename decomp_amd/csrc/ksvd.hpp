@@ -6,7 +6,7 @@
 // One iteration: X = omp(Y, D, s) (omp_solve, unchanged); R = Y - X D once, on the GEMM cores (EpiSubFrom); then
 // the atom sweep, for k = 0 .. K-1 in order, with I = {i : X[i, k] != 0} in ascending row order, fixed for the
 // whole sweep (the lists are built once, before atom 0):
-//   I empty: atom k is left as it is (unused atoms are not replaced)
+//   I empty: atom k is left as it is (the sweep replaces no atom; the cleaning pass of ksvd_clean.hpp may, after it)
 //   g = X[I, k], d = D[k]:   u  = g^H R[I, :] + |g|^2 d       (= g^H E for E = R[I, :] + g d; E is never formed)
 //                            d' = u / |u|, or d where !(|u| > 0) (a NaN keeps d)
 //                            g' = R[I, :] d'^H + g (d . d'^H)
@@ -38,6 +38,9 @@
 // in ksvd_mask.hpp, which holds its three kernels.  The host path below is one for both: the atom loop launches the
 // three kernels of this file or those three, and the coder of a step is OmpCoder (omp_mask.hpp) for mask = none, 1-D
 // or 2-D.
+//
+// The replacement of unused and duplicate atoms after a sweep (dcp_ksvd_clean_step_*, dcp_ksvd_clean_*) is stated in
+// ksvd_clean.hpp, which holds its kernels, its workspace and its entry; the step below runs it on request.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -485,6 +488,16 @@ inline int ksvd_atoms(dcp_handle* h, KsvdMask<real_t<T>> m, T* X, T* D, int F, i
     return DCP_OK;
 }
 
+// w.R = Y - X D on the GEMM cores
+template <class T>
+inline int ksvd_residual(dcp_handle* h, const T* Y, const T* X, const T* D, int N, int F, int K, KsvdWs<T>& w) {
+    GemmArgs<T> a;
+    a.A = X; a.lda = K; a.B = D; a.ldb = F; a.M = N; a.N = F; a.K = K;
+    a.ext_ws = w.ext;
+    DCP_LAUNCH_OK(h, (gemm<FORM_NN>(h->stream, a, EpiSubFrom<T>{Y, (long)F, w.R, (long)F})));
+    return DCP_OK;
+}
+
 // What every sweep does before atom 0: the lists (on the counts of ksvd_count), the copy of D, R = Y - X D.
 template <class T>
 inline int ksvd_sweep_begin(dcp_handle* h, const T* Y, T* X, T* D, int N, int F, int K, KsvdWs<T>& w) {
@@ -494,13 +507,7 @@ inline int ksvd_sweep_begin(dcp_handle* h, const T* Y, T* X, T* D, int N, int F,
                        (const int*)w.blockoff, (const long long*)w.off, w.rows);
     DCP_LAUNCH_OK(h, hipGetLastError());
     DCP_HIP_OK(h, hipMemcpyAsync(w.Dold, D, (size_t)K * F * sizeof(T), hipMemcpyDeviceToDevice, st));
-    {   // R = Y - X D
-        GemmArgs<T> a;
-        a.A = X; a.lda = K; a.B = D; a.ldb = F; a.M = N; a.N = F; a.K = K;
-        a.ext_ws = w.ext;
-        DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a, EpiSubFrom<T>{Y, (long)F, w.R, (long)F})));
-    }
-    return DCP_OK;
+    return ksvd_residual<T>(h, Y, (const T*)X, (const T*)D, N, F, K, w);
 }
 
 // ... and after atom K - 1: mdpart[b] = max |D - Dold| over workgroup b's share (NaN wins, as np.max), as double
@@ -548,6 +555,13 @@ inline int ksvd_read_maxdiff(dcp_handle* h, const double* mdpart, long n, double
     return read_partial_max(h, mdpart, grid_for(n, kKsvdMdParts), reinterpret_cast<double*>(hostv), maxdiff_out);
 }
 
+}  // namespace dcp
+
+// ---- the cleaning pass (replacement of unused and duplicate atoms): its kernels, workspace and entry -------------
+#include "ksvd_clean.hpp"
+
+namespace dcp {
+
 // The entries.  masked false (dcp_ksvd_sweep_*, dcp_ksvd_step_*): M, mask_ndim and rows_per_pass are nullptr, 0, 0;
 // masked true (dcp_ksvd_mask_*): a null mask and mask_ndim outside {1, 2} are refused.
 template <class T>
@@ -572,22 +586,36 @@ inline int ksvd_sweep_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mas
     return ksvd_read_maxdiff(h, w.mdpart, (long)K * F, maxdiff_out);
 }
 
+// What dcp_ksvd_clean_step_* adds to a step: the threshold, the gate and where the number of marked atoms goes
+struct KsvdCleanCall {
+    double max_coherence, stop_tol;
+    int* n_marked_out;
+};
+
 // The coder (OmpCoder: plain OMP, or the masked coder as dcp_omp_mask_* runs it), then the sweep, over one
-// workspace layout.
+// workspace layout.  With `clean` (dcp_ksvd_clean_step_*; masked is then whether a mask was given) the cleaning
+// pass of ksvd_clean.hpp follows on the sweep's own R: the marking is enqueued before max|D_new - D_old| is read and
+// its count comes back in that same synchronisation, so the step gains no host round trip; energies, selection and
+// replacement are enqueued (and left in flight on the handle's stream) only if an atom is marked and
+// maxdiff >= stop_tol, which a NaN fails.
 template <class T>
 inline int ksvd_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, bool masked, T* X, T* D,
                          int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
-                         double* maxdiff_out, int* it_out) {
+                         double* maxdiff_out, int* it_out, const KsvdCleanCall* clean = nullptr) {
     if (!h) return DCP_ERR_INVALID;
-    if (!Y || (masked && !M) || !X || !D || !maxdiff_out || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (!Y || (masked && !M) || !X || !D || !maxdiff_out || !it_out || (clean && !clean->n_marked_out))
+        return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (clean) DCP_TRY(ksvd_clean_check(h, M, mask_ndim, clean->max_coherence, clean->stop_tol));
     if (masked) DCP_TRY(omp_check_mask(h, "ksvd", mask_ndim, rows_per_pass));
     DCP_TRY(omp_check_problem<T>(h, N, F, K, n_nonzero, coef_tol));
     DCP_HIP_OK(h, hipSetDevice(h->device));
-    OmpCoder<T> coder(M, mask_ndim, rows_per_pass);
+    OmpCoder<T> coder(M, mask_ndim, masked ? rows_per_pass : 0);
     KsvdWs<T> w;
+    KsvdCleanWs<T> c;
     DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
         coder.layout(a, N, F, K, n_nonzero);
         ksvd_layout<T>(a, w, N, F, K, n_nonzero, masked);
+        if (clean) ksvd_clean_layout<T>(a, c, N, F, K, clean->max_coherence > 0.0);
     }));
     DCP_TRY(coder.solve(h, Y, (const T*)D, X, N, F, K, n_nonzero, coef_tol));
     DCP_TRY(ksvd_count<T>(h, X, (int)N, (int)K, w));
@@ -597,7 +625,12 @@ inline int ksvd_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask
     if (host[0] > n_nonzero) return fail(h, DCP_ERR_INTERNAL, "ksvd: the coder returned a row beyond the sparsity");
     const KsvdMask<real_t<T>> m{M, mask_ndim == 2 ? (long)F : 0L};
     DCP_TRY(ksvd_sweep<T>(h, Y, m, X, D, (int)N, (int)F, (int)K, host + 4, w));
-    return ksvd_read_maxdiff(h, w.mdpart, (long)K * F, maxdiff_out);
+    if (!clean) return ksvd_read_maxdiff(h, w.mdpart, (long)K * F, maxdiff_out);
+    DCP_TRY(ksvd_clean_mark<T>(h, (const T*)X, (const T*)D, (int)N, (int)F, (int)K, clean->max_coherence, w, c));
+    DCP_TRY(ksvd_clean_read<T>(h, w, c, (long)K * F, maxdiff_out, clean->n_marked_out));
+    if (*clean->n_marked_out > 0 && *maxdiff_out >= clean->stop_tol)
+        DCP_TRY(ksvd_clean_apply<T>(h, Y, m, (const T*)X, D, (int)N, (int)F, (int)K, *clean->n_marked_out, w, c));
+    return DCP_OK;
 }
 
 }  // namespace dcp

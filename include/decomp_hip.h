@@ -652,6 +652,54 @@ int dcp_ksvd_mask_step_c128(dcp_handle* h, const void* Y, const double* M, int m
                             int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
                             double* maxdiff_out, int* it_out);
 
+/* ---- K-SVD: replacement of unused and duplicate atoms (not in the reference; csrc/ksvd_clean.hpp) ---------- */
+/* One cleaning pass on what a sweep leaves behind: X, D, R = Y - X D, the mask M (1 without one: M null with
+ * mask_ndim 0) and cnt_k, the non-zeros of column k of X.
+ *   marking      k = 0 .. K-1 in order, G = D D^H in the working dtype: atom k is marked if cnt_k == 0, or if
+ *                max_coherence > 0 and there is a j < k, itself not marked, with |G_kj| > max_coherence.  A marked
+ *                atom never marks another; of a coherent pair the lower index survives.
+ *   ranking      e_i = sum_f M_if |R_if|^2 (0 where !(e_i > 0)); rows by e descending, ties to the lower row.
+ *   replacement  the j-th marked atom (ascending) takes the j-th row i: z_f = Y_if where M_if > 0, elsewhere
+ *                sum_k X_ik D_kf from the row's non-zeros and the given D (never Y - R: Y at hidden entries does not
+ *                influence the result).  D[k] = z / |z| if e_i > 0 and |z| > 0, otherwise (NaN included, or no row
+ *                left) the atom is kept.  Every z is formed before any atom is written.  X is not touched.
+ * Bitwise reproducible.
+ *   dcp_ksvd_clean_*      : forms R = Y - X D as dcp_ksvd_sweep_* does and runs one pass on the caller's X and D
+ *                           (D updated in place); *n_marked_out, *n_replaced_out (host): atoms marked / replaced.
+ *                           Synchronises the stream before returning.
+ *   dcp_ksvd_clean_step_* : dcp_ksvd_mask_step_* (or, with M null and mask_ndim 0, dcp_ksvd_step_*; rows_per_pass is
+ *                           then ignored), then the pass on the sweep's own R.  The marking always runs and
+ *                           *n_marked_out comes back in the synchronisation that reads *maxdiff_out; the replacement
+ *                           is enqueued only if *n_marked_out > 0 and *maxdiff_out >= stop_tol (stop_tol = +inf:
+ *                           never; a NaN maxdiff: never) and may still be in flight on the handle's stream on return.
+ *                           *maxdiff_out is that of the sweep: the jump of a replaced atom does not enter it.
+ * DCP_ERR_INVALID with a message, before X or D is written: what the step entries refuse, a null pointer (M aside),
+ * mask_ndim outside {0, 1, 2} or not matching M, a NaN max_coherence or stop_tol. */
+int dcp_ksvd_clean_f32(dcp_handle* h, const float* Y, const float* M, int mask_ndim, const float* X, float* D,
+                       int64_t N, int64_t F, int64_t K, double max_coherence, int* n_marked_out, int* n_replaced_out);
+int dcp_ksvd_clean_f64(dcp_handle* h, const double* Y, const double* M, int mask_ndim, const double* X, double* D,
+                       int64_t N, int64_t F, int64_t K, double max_coherence, int* n_marked_out, int* n_replaced_out);
+int dcp_ksvd_clean_c64(dcp_handle* h, const void* Y, const float* M, int mask_ndim, const void* X, void* D, int64_t N,
+                       int64_t F, int64_t K, double max_coherence, int* n_marked_out, int* n_replaced_out);
+int dcp_ksvd_clean_c128(dcp_handle* h, const void* Y, const double* M, int mask_ndim, const void* X, void* D, int64_t N,
+                       int64_t F, int64_t K, double max_coherence, int* n_marked_out, int* n_replaced_out);
+int dcp_ksvd_clean_step_f32(dcp_handle* h, const float* Y, const float* M, int mask_ndim, float* X, float* D,
+                            int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                            double* maxdiff_out, int* it_out, double max_coherence, double stop_tol,
+                            int* n_marked_out);
+int dcp_ksvd_clean_step_f64(dcp_handle* h, const double* Y, const double* M, int mask_ndim, double* X, double* D,
+                            int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                            double* maxdiff_out, int* it_out, double max_coherence, double stop_tol,
+                            int* n_marked_out);
+int dcp_ksvd_clean_step_c64(dcp_handle* h, const void* Y, const float* M, int mask_ndim, void* X, void* D,
+                            int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                            double* maxdiff_out, int* it_out, double max_coherence, double stop_tol,
+                            int* n_marked_out);
+int dcp_ksvd_clean_step_c128(dcp_handle* h, const void* Y, const double* M, int mask_ndim, void* X, void* D,
+                            int64_t N, int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                            double* maxdiff_out, int* it_out, double max_coherence, double stop_tol,
+                            int* n_marked_out);
+
 /* ---- row movers of the minibatch containers (decomp/utils/data.py:124-156, 214-313) ------ */
 /* gather : out[i, :] = in[index[i], :]      scatter: out[index[i], :] = in[i, :]      i < rows
  * Rows are row_bytes long (any dtype); index: int64 in DEVICE memory.  `in` / `out` may be
