@@ -255,6 +255,14 @@ SIGNATURES = {
     'dcp_tm_scatter_windows_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
     'dcp_tm_scatter_windows_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
     'dcp_tm_scatter_windows_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
+    'dcp_tm_pursuit_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_tm_pursuit_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_tm_pursuit_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_tm_pursuit_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_tm_pursuit_lds_atoms_f32': (_c_int, []),
+    'dcp_tm_pursuit_lds_atoms_f64': (_c_int, []),
+    'dcp_tm_pursuit_lds_atoms_c64': (_c_int, []),
+    'dcp_tm_pursuit_lds_atoms_c128': (_c_int, []),
 }
 
 _lib = None

@@ -176,16 +176,15 @@ struct TmStep {
     int* flag;
 };
 
-template <class T, int PROX>
-__global__ void __launch_bounds__(256) tm_corr_step_kernel(const T* __restrict__ r, const T* __restrict__ D,
-                                                           TmGeom g, int lds_ok, TmStep<T, PROX> ep) {
-    typedef real_t<T> R;
+// (r A^H)[b, t, c] for c = 256 blockIdx.x + threadIdx.x, unscaled; zero where c >= C.  The whole workgroup calls it
+// (the staging has a barrier).
+template <class T>
+__device__ __forceinline__ T tm_corr_tile(const T* __restrict__ r, const T* __restrict__ D, const TmGeom& g,
+                                          int lds_ok, long t, long b, long c) {
     extern __shared__ __attribute__((aligned(16))) char tm_smem[];
     T* sD = reinterpret_cast<T*>(tm_smem);
     T* sR = sD + g.S;
-    const long t = blockIdx.y, b = blockIdx.z;
     const long c0 = (long)blockIdx.x * 256;
-    const long c = c0 + threadIdx.x;
     const long c1 = (c0 + 255 < g.C - 1) ? c0 + 255 : g.C - 1;
     long nlo = g.s * c0 - g.Q, nhi = g.s * c1 - g.Q + g.S - 1;
     if (nlo < 0) nlo = 0;
@@ -201,13 +200,24 @@ __global__ void __launch_bounds__(256) tm_corr_step_kernel(const T* __restrict__
         rsrc = sR;
         roff = nlo;
     }
-    if (c >= g.C) return;
+    T acc = zero_of<T>();
+    if (c >= g.C) return acc;
     const long base = g.s * c - g.Q;
     long k0 = -base, k1 = g.N - 1 - base;
     if (k0 < 0) k0 = 0;
     if (k1 > g.S - 1) k1 = g.S - 1;
-    T acc = zero_of<T>();
     for (long k = k0; k <= k1; ++k) acc = madd(acc, rsrc[base + k - roff], lds_ok ? sD[k] : conj_of(dsrc[k]));
+    return acc;
+}
+
+template <class T, int PROX>
+__global__ void __launch_bounds__(256) tm_corr_step_kernel(const T* __restrict__ r, const T* __restrict__ D,
+                                                           TmGeom g, int lds_ok, TmStep<T, PROX> ep) {
+    typedef real_t<T> R;
+    const long t = blockIdx.y, b = blockIdx.z;
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    const T acc = tm_corr_tile(r, D, g, lds_ok, t, b, c);
+    if (c >= g.C) return;
     const long tc = t * g.C + c;
     const long i = (b * g.T + t) * g.C + c;
     const R Linv = ep.scal[0];
@@ -220,6 +230,18 @@ __global__ void __launch_bounds__(256) tm_corr_step_kernel(const T* __restrict__
 }
 
 // ---- prepare ------------------------------------------------------------------------------------
+// |A_(t,c)|^2 over its taps inside [0, N)
+template <class T>
+__device__ __forceinline__ real_t<T> tm_row_norm2(const T* __restrict__ D, const TmGeom& g, long t, long c) {
+    const long base = g.s * c - g.Q;
+    long k0 = -base, k1 = g.N - 1 - base;
+    if (k0 < 0) k0 = 0;
+    if (k1 > g.S - 1) k1 = g.S - 1;
+    real_t<T> acc = 0;
+    for (long k = k0; k <= k1; ++k) acc += abs2(D[t * g.S + k]);
+    return acc;
+}
+
 // rho[t, c] = |A_(t,c)| over its taps inside [0, N); alpha_k = (alpha / rho) N; tol_k = tol rho; clears the flag
 template <class T>
 __global__ void __launch_bounds__(256) tm_rownorm_kernel(const T* __restrict__ D, TmGeom g, real_t<T> alpha,
@@ -229,14 +251,7 @@ __global__ void __launch_bounds__(256) tm_rownorm_kernel(const T* __restrict__ D
     typedef real_t<T> R;
     if (blockIdx.x == 0 && threadIdx.x == 0) *flag = 0;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < g.T * g.C; i += (long)gridDim.x * 256L) {
-        const long t = i / g.C, c = i % g.C;
-        const long base = g.s * c - g.Q;
-        long k0 = -base, k1 = g.N - 1 - base;
-        if (k0 < 0) k0 = 0;
-        if (k1 > g.S - 1) k1 = g.S - 1;
-        R acc = 0;
-        for (long k = k0; k <= k1; ++k) acc += abs2(D[t * g.S + k]);
-        const R nr = sqrt(acc);
+        const R nr = sqrt(tm_row_norm2(D, g, i / g.C, i % g.C));
         rho[i] = nr;
         rinv[i] = R(1) / nr;
         alphak[i] = (alpha / nr) * R(g.N);
@@ -767,6 +782,8 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
 
 }  // namespace dcp
 
+#include "template_pursuit.hpp"   // matching pursuit on the same operator
+
 // ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip) ------------------------------
 #define DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding)                                    \
     dcp::TmGeom g;                                                                                  \
@@ -823,6 +840,14 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
         return dcp::tm_lasso_solve<TYPE, dcp::PROX_REAL>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g,       \
                                                          (R)alpha, (R)tol, maxiter, method, it_out);          \
     }                                                                                                          \
+    extern "C" int dcp_tm_pursuit_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,      \
+                                         int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,       \
+                                         int64_t n_steps, double tol, int positive, int* it_out) {            \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        return dcp::tm_pursuit_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol,         \
+                                         positive, it_out);                                                    \
+    }                                                                                                          \
+    extern "C" int dcp_tm_pursuit_lds_atoms_##SFX(void) { return (int)dcp::tm_pursuit_lds_atoms<TYPE>(); }    \
     extern "C" int dcp_tm_dstep_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt,        \
                                        void* yX, int64_t B, int64_t T_, int64_t S, int64_t N, int64_t stride, \
                                        int padding, int acc_it, double* maxdiff) {                             \

@@ -9,7 +9,10 @@ size is formed on the hot path (include/decomp_hip.h ``dcp_tm_*``, decomp_amd/cs
     operator: one iteration is a residual pass over the signal and a correlation pass over the
     coefficients, the proximal step fused into the second;
   * the dictionary step's statistics XXt [T S, T S] and yX [T S] are built from lag correlations of
-    the coefficients, and D is updated by one fused chain of small kernels.
+    the coefficients, and D is updated by one fused chain of small kernels;
+  * ``pursuit`` (not in the reference) is greedy matching pursuit on the same operator, the coder with a given
+    number of events per signal: one correlation pass, then one workgroup per signal that keeps the correlations
+    up to date from the lag correlations of the templates (decomp_amd/csrc/template_pursuit.hpp).
 
 'cd', 'parallel_cd' and 'admm' have no structured form: for them ``_temp2mat`` is materialised on the
 device and the dense ``dcp_lasso_*`` solvers of decomp_amd.lasso run on it.  That path is correct but
@@ -18,6 +21,7 @@ dense (memory T C N, work per iteration of the dense solvers).
 The outer loop reads one number per iteration from the device, max|dD|, for the reference's stop test.
 """
 import ctypes
+import numbers
 
 import numpy as np
 
@@ -196,6 +200,75 @@ def predict(x, D, size, stride=1, padding='SAME'):
     _call(x3, 'predict', x3, Dd, B, T, S, size, stride, _pad_code(padding),
           out)
     return _arrays.to_caller(out.reshape(lead + (size,)), kind)
+
+
+def pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME', positive=False):
+    """
+    Greedy matching pursuit of every signal on the shift-invariant dictionary of the templates: peel off at most
+    ``n_nonzero_coefs`` events per signal, or stop once the residual energy |y - x * D|^2 is <= ``tol``.
+
+    y: [..., N]; D: templates [T, S], S <= N, used as given (not normalised); float or complex, both of one dtype.
+    With A[(t, c), n] = D[t, n - stride c + Q] and rho2[t, c] = |A_(t,c)|^2 over the taps inside the signal, a step
+    takes the atom with the largest |r . A_(t,c)^H|^2 / rho2 (the lowest flat index t C + c on ties) and adds
+    r . A^H / rho2 to its coefficient; ``positive`` (real dtypes) takes only atoms that correlate positively.  A signal
+    also stops when no atom scores above zero.
+    This is matching pursuit, not OMP: there is no re-fit on the support, and an atom may be taken again (its
+    coefficient accumulates), so ``n_nonzero_coefs`` bounds the STEPS and hence the non-zeros.  There is no sparsity
+    cap; with ``tol`` alone the step limit is T C.
+    Returns (it, x): x [..., T, C] in the layout of ``solve`` / ``predict`` (``predict(x, D, N, stride, padding)`` is
+    the approximation), it the largest number of steps any signal took.  NumPy in -> NumPy out; torch GPU tensors
+    stay on the device.  Runs in libdecomp_hip.so (``dcp_tm_pursuit_*``, decomp_amd/csrc/template_pursuit.hpp).
+    """
+    from . import omp
+    kind = get_array_module(y, D)
+    assertion.assert_dtypes(y=y, D=D)
+    assertion.assert_ndim('D', D, ndim=2)
+    if len(y.shape) < 1:
+        raise assertion.DimInvalidError('y must have at least 1 dimension')
+    if padding not in ('SAME', 'VALID'):
+        raise ValueError("padding must be 'SAME' or 'VALID'. Given {0!r}".format(padding))
+    if not _is_int(stride) or int(stride) < 1:
+        raise ValueError('stride must be a positive integer. Given {0!r}'.format(stride))
+    stride = int(stride)
+    T, S = int(D.shape[0]), int(D.shape[1])
+    N = int(y.shape[-1])
+    if T < 1 or S < 1 or S > N:
+        raise ValueError('templates [{0:d}, {1:d}] need 1 <= T and 1 <= S <= N = {2:d}'.format(T, S, N))
+    if n_nonzero_coefs is None and tol is None:
+        raise ValueError('Either n_nonzero_coefs or tol must be given.')
+    C = _coef_size(S, N, stride=stride, padding=padding)
+    tol_c = omp.check_tol(tol)
+    if n_nonzero_coefs is None:
+        n_steps = T * C
+    elif not _is_int(n_nonzero_coefs) or not 1 <= int(n_nonzero_coefs) <= T * C:
+        raise ValueError('n_nonzero_coefs must be an integer in [1, T C = {0:d}]. Given {1!r}'.format(
+            T * C, n_nonzero_coefs))
+    else:
+        n_steps = int(n_nonzero_coefs)
+    if not isinstance(positive, (bool, np.bool_)):
+        raise ValueError('positive must be a bool. Given {0!r}'.format(positive))
+    if positive and _arrays.np_dtype(y).kind == 'c':
+        raise ValueError('positive=True needs a real dtype.')
+
+    import torch
+    yd = _arrays.to_device(y)
+    Dd = _arrays.to_device(D, yd.device.index).contiguous()
+    _same_device(yd, Dd)
+    lead = tuple(yd.shape[:-1])
+    y2 = yd.reshape(-1, N).contiguous()
+    B = y2.shape[0]
+    it = ctypes.c_int(0)
+    if B > 0:
+        xd = torch.empty((B, T, C), dtype=yd.dtype, device=yd.device)
+        _call(y2, 'pursuit', y2, Dd, xd, B, T, S, N, stride, _pad_code(padding), n_steps, tol_c,
+              1 if positive else 0, ctypes.byref(it))
+    else:
+        xd = torch.zeros((0, T, C), dtype=yd.dtype, device=yd.device)
+    return it.value, _arrays.to_caller(xd.reshape(lead + (T, C)), kind)
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, (bool, np.bool_))
 
 
 def _lasso(y, D, x, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol):

@@ -845,7 +845,14 @@ int dcp_dict_mask_step_c128(dcp_handle* h, const void* Y, const double* mask, vo
  *              then D <- l2(D + (yX - XXt D) / (Gershgorin(XXt) + 1e-15)) in place; *maxdiff = max|dD|.
  *   gather_windows:  Yw [m, w] = Y[idx_b[j], idx_n[j] : + w], Xw [m, T, cw] = X[idx_b[j], :, idx_n[j] : + cw]
  *              (cw = coefficients of a w-sample window; the caller keeps idx_n[j] + cw <= C, idx_n[j] + w <= N)
- *   scatter_windows: X[idx_b[j], :, idx_n[j] : + cw] = Xw[j] in order j = 0 .. m - 1 (the last window wins). */
+ *   scatter_windows: X[idx_b[j], :, idx_n[j] : + cw] = Xw[j] in order j = 0 .. m - 1 (the last window wins).
+ *   pursuit:   matching pursuit of every signal on A (decomp_amd/csrc/template_pursuit.hpp states the algorithm): at
+ *              most n_steps (in [1, T C]) greedy steps, each taking the atom of the largest |alpha|^2 / rho2 (lowest
+ *              flat index t C + c on ties; positive != 0, real dtypes: only atoms with alpha > 0) and adding
+ *              alpha / rho2 to its coefficient; a signal stops once its residual energy is <= tol (tol < 0: no such
+ *              stop) or no atom scores > 0.  D is used as given.  X [B, T, C] is written entirely (the caller does not
+ *              zero it); *it_out = the largest number of steps a signal took.  Synchronises the stream.
+ *   pursuit_lds_atoms: the largest T C for which pursuit keeps the correlations in LDS (above: global workspace). */
 int dcp_tm_temp2mat_f32(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
 int dcp_tm_temp2mat_f64(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
 int dcp_tm_temp2mat_c64(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
@@ -874,6 +881,14 @@ int dcp_tm_scatter_windows_f32(dcp_handle* h, const void* Xw, void* X, const int
 int dcp_tm_scatter_windows_f64(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding);
 int dcp_tm_scatter_windows_c64(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding);
 int dcp_tm_scatter_windows_c128(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding);
+int dcp_tm_pursuit_f32(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int positive, int* it_out);
+int dcp_tm_pursuit_f64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int positive, int* it_out);
+int dcp_tm_pursuit_c64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int positive, int* it_out);
+int dcp_tm_pursuit_c128(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int positive, int* it_out);
+int dcp_tm_pursuit_lds_atoms_f32(void);
+int dcp_tm_pursuit_lds_atoms_f64(void);
+int dcp_tm_pursuit_lds_atoms_c64(void);
+int dcp_tm_pursuit_lds_atoms_c128(void);
 
 #ifdef __cplusplus
 }
