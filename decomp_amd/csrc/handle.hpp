@@ -50,7 +50,8 @@ struct dcp_handle {
     int64_t pf_rows = 0, pf_row_bytes = 0;
     bool pf_inflight = false;   // started on the side stream, not yet joined
     // coordinate descent inside the dictionary step: the stop flag of the solve's last ten sweeps is still on its way
-    // to this pinned word when lasso_solve returns; lasso_settle_deferred() turns it into *lasso_deferred_it
+    // to this pinned word when lasso_cd_gram, which arms the deferral, returns; lasso_settle_deferred() turns it into
+    // *lasso_deferred_it
     int* lasso_deferred_flag = nullptr;
     int* lasso_deferred_it = nullptr;
     int lasso_deferred_it_met = 0;

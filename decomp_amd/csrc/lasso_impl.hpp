@@ -25,6 +25,7 @@
 #include "kernels_small.hpp"
 #include "nmf_impl.hpp"  // kMaxSplits, column_sums
 #include "lasso_extra.hpp"  // parallel_cd and admm kernels
+#include "prox_loop.hpp"    // prox_gradient_loop, flag_publish_kernel, poll_host_flag
 
 namespace dcp {
 
@@ -764,23 +765,7 @@ inline int gram_kk(dcp_handle* h, const T* P, const T* Q, int K, int F, LassoWs<
     return DCP_OK;
 }
 
-// *host = *flag, *flag = 0: the stop flag of a check iteration goes to device-mapped pinned host memory (the host polls
-// it one iteration later) and is cleared for the next check.  One 2 us launch instead of a fill kernel in front of the
-// iteration, a copy kernel behind it and an event (whose barrier packet idles the GPU ~5 us): 14 -> ~3 us per check.
-template <class T = void>
-__global__ void flag_publish_kernel(int* __restrict__ flag, int* __restrict__ host) {
-    if (threadIdx.x == 0) {
-        const int f = *flag;
-        *flag = 0;
-        *host = f;
-    }
-}
-
-// Wait for flag_publish_kernel's store: the word was set to the sentinel -1 before that kernel was enqueued (polling:
-// the GPU sat idle ~2 ms per dictionary step behind a blocking wait once the host ran a step ahead).
-inline int poll_host_flag(dcp_handle* h, int* host_flag) { return wait_pinned_word(h, host_flag, -1); }
-
-// The dictionary step's deferred *it_out of a coordinate-descent solve (see the Gram-form loop in lasso_solve): called
+// The dictionary step's deferred *it_out of a coordinate-descent solve (see lasso_cd_gram): called
 // once the rest of the step has been enqueued, when the flag has long landed.
 inline int lasso_settle_deferred(dcp_handle* h) {
     if (h->lasso_deferred_flag == nullptr) return DCP_OK;
@@ -796,11 +781,6 @@ inline int lasso_settle_deferred(dcp_handle* h) {
     }
     h->lasso_deferred_it = nullptr;
     return DCP_OK;
-}
-
-template <class T>
-inline int read_flag(dcp_handle* h, int* flag_dev, int* host_flag, bool* violated) {
-    return read_scalar(h, (const int*)flag_dev, violated, host_flag);
 }
 
 // scal[0] = 1 / L, scal[2] = L for L = max_j sum_i |M[i, j]|  (eigen.py:20)
@@ -832,6 +812,436 @@ struct LassoExtra {
     bool start_prefetch = false;
 };
 
+// One prepared solve, as the solvers below read it.
+template <class T>
+struct LassoProblem {
+    typedef real_t<T> R;
+    dcp_handle* h;
+    hipStream_t st;
+    int N, F, K;
+    const R* mask;       // null, [F] (mask_ndim 1: folded into An and Ym by lasso_prepare) or [N,F] (mask_ndim 2)
+    int mask_ndim;
+    const R* rowscale;   // 2-D mask: its row sums [N]; null otherwise
+    T* X;                // [N,K] in: initial estimate, out: solution
+    LassoWs<T>& w;       // after lasso_prepare: An, s, alphak, tolk, yAt, flag = 0, and (see there) xb[0] = x * s
+    int* host_flag;      // 64 bytes of pinned host memory
+    int maxiter;
+    const LassoExtra& extra;
+};
+
+// What a solver leaves: the reference's iteration count and the buffer that holds x * s.
+template <class T>
+struct LassoOutcome {
+    int it;
+    T* result;
+    bool final_in_place;   // the last iteration's epilogue has already written x = result / s into X
+};
+
+// v [N,K] times a K x K matrix (A A^H, or what a solver made of it); complex: its real extended image goes to ext2
+template <class T>
+inline GemmArgs<T> codes_kk_product(const LassoProblem<T>& p, const T* v, const T* M) {
+    GemmArgs<T> a;
+    a.A = v; a.lda = p.K; a.B = M; a.ldb = p.K; a.M = p.N; a.N = p.K; a.K = p.K;
+    a.ext_ws = p.w.ext2;
+    return a;
+}
+
+// 2-D mask: T1 = (v An) o M, then T1 An^H with the solver's step in the epilogue
+template <class T, class Epi>
+inline int masked_back_projection(const LassoProblem<T>& p, const T* v, const Epi& epi) {
+    const LassoWs<T>& w = p.w;
+    GemmArgs<T> a1;
+    a1.A = v; a1.lda = p.K; a1.B = w.An; a1.ldb = p.F; a1.M = p.N; a1.N = p.F; a1.K = p.K;
+    a1.ext_ws = w.ext1;
+    DCP_LAUNCH_OK(p.h, (gemm<FORM_NN>(p.st, a1, EpiMulMask<T>{p.mask, p.F, w.T1, p.F})));
+    GemmArgs<T> a2;
+    a2.A = w.T1; a2.lda = p.F; a2.B = w.An; a2.ldb = p.F; a2.M = p.N; a2.N = p.K; a2.K = p.F;
+    a2.conjB = true;
+    a2.ext_ws = w.ext1;
+    DCP_LAUNCH_OK(p.h, (gemm<FORM_NT>(p.st, a2, epi)));
+    return DCP_OK;
+}
+
+// parallel_cd and admm: step(i, check) enqueues iteration i; the stop test of every tenth one (lasso.py:479, :612) is
+// read synchronously right behind it.  *met_at = the iteration whose test was met; untouched when maxiter ran out.
+template <class T, class Step>
+inline int sync_checked_loop(const LassoProblem<T>& p, Step&& step, int* met_at) {
+    for (int i = 0; i < p.maxiter; ++i) {
+        const int check = (i % 10 == 0) ? 1 : 0;
+        if (check) DCP_HIP_OK(p.h, hipMemsetAsync(p.w.flag, 0, sizeof(int), p.st));
+        DCP_TRY(step(i, check));
+        if (check) {
+            bool viol = true;
+            DCP_TRY(read_scalar(p.h, (const int*)p.w.flag, &viol, p.host_flag));
+            if (!viol) { *met_at = i; break; }
+        }
+    }
+    return DCP_OK;
+}
+
+// Mask folding, row normalisation, the scaled alpha / tol, x * s and y A^H (lasso.py:120-131).  scale_x = false
+// leaves xb[0] to the solver (lasso_prox forms x * s in a pass it makes anyway).
+template <class T>
+inline int lasso_prepare(const LassoProblem<T>& p, const T* Y, const T* A, real_t<T> alpha, real_t<T> tol,
+                         bool scale_x) {
+    typedef real_t<T> R;
+    LassoWs<T>& w = p.w;
+    const int N = p.N, F = p.F, K = p.K;
+    // ---- 1-D mask folds into y and A (lasso.py:120-122); any mask: Ym = y o M ----
+    const T* Ause = A;
+    const T* Yuse = p.mask_ndim != 0 ? w.Ym : Y;
+    if (p.mask_ndim == 1) {
+        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for((long)K * F)), dim3(256), 0, p.st, A, p.mask,
+                           (long)K, (long)F, 0L, w.An);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+        Ause = w.An;
+    }
+    if (p.mask_ndim != 0) {   // (mask row stride 0: the same [F] mask for every sample)
+        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for((long)N * F)), dim3(256), 0, p.st, Y, p.mask,
+                           (long)N, (long)F, p.mask_ndim == 2 ? (long)F : 0L, w.Ym);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+        if (p.mask_ndim == 1)
+            hipLaunchKernelGGL((reduce_vector_kernel<SumOp, R, FinStore<R>>), dim3(1), dim3(256), 0, p.st, p.mask,
+                               (long)F, FinStore<R>{w.scal + 1});   // sum(mask)
+        else
+            hipLaunchKernelGGL((rowsum_kernel<R>), dim3(N), dim3(256), 0, p.st, p.mask, (long)F, (long)F, w.rowscale);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+    }
+    // ---- A scaling (lasso.py:124-131): s = |A_k|, An = A / s, alpha/s, tol*s, x*s ----
+    hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(K), dim3(256), 0, p.st, Ause, (long)F, (long)F, 1,
+                       (const T*)nullptr, 0L, w.An, (long)F, (R*)nullptr, w.s);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    hipLaunchKernelGGL((lasso_scalars_kernel<R>), dim3(grid_for(K, 64)), dim3(256), 0, p.st, w.s, (long)K,
+                       alpha, tol, p.mask_ndim == 1 ? w.scal + 1 : (const R*)nullptr,
+                       p.mask_ndim == 2 ? R(1) : R(F), w.alphak, w.tolk, w.flag);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    if (scale_x) {
+        hipLaunchKernelGGL((col_scale_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, p.st, (const T*)p.X,
+                           (const R*)w.s, (long)N, (long)K, 1, w.xb[0]);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+    }
+    // ---- yAt = (y o M) An^H ----
+    GemmArgs<T> a;
+    a.A = Yuse; a.lda = F; a.B = w.An; a.ldb = F; a.M = N; a.N = K; a.K = F; a.conjB = true;
+    a.ext_ws = w.ext1;
+    // deep reduction, few big tiles: ordered split-K partials in the (still unused) iterate buffers
+    const long stride = (long)(w.xb[2] - w.xb[1]);
+    const int ys = (stride >= (long)N * K && w.xb[3] - w.xb[2] == stride) ? plan_deep_nt(a, 3) : 1;
+    if (ys > 1) {
+        DCP_LAUNCH_OK(p.h, (gemm<FORM_NT>(p.st, a, EpiSlab<T>{w.xb[1], K, stride})));
+        launch_reduce_slabs<T>(p.st, (const T*)w.xb[1], stride, ys, (long)N * K, w.yAt);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+    } else {
+        DCP_LAUNCH_OK(p.h, (gemm<FORM_NT>(p.st, a, EpiStore<T>{w.yAt, K})));
+    }
+    if (p.extra.start_prefetch) DCP_TRY(start_registered_prefetch(p.h));
+    return DCP_OK;
+}
+
+// ns sweeps of the Gram-form coordinate descent over xb[0] and G; check_first: the first one raises *flag when its
+// stop test is violated; cond != null: the device skips the launch when *cond is zero.
+// (the register form holds a row's K coefficients in one wave: 64 lanes x up to 32 slots;
+//  wider dictionaries take the memory-resident form -- the reference has no limit, lasso.py:526-552)
+template <class T, int PROX>
+inline int launch_cd_gram(const LassoProblem<T>& p, int ns, int check_first, const int* cond) {
+    typedef real_t<T> R;
+    const LassoWs<T>& w = p.w;
+    const int K = p.K;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((p.N + 3) / 4), dim3(256), 0, p.st, w.xb[0], w.G, (const T*)w.AAt,
+                           (const R*)w.alphak, (const R*)w.tolk, (long)p.N, K, ns, check_first, w.flag, cond);
+    };
+    if (K <= 64) launch(cd_gram_kernel<T, PROX, 1>);
+    else if (K <= 128) launch(cd_gram_kernel<T, PROX, 2>);
+    else if (K <= 256) launch(cd_gram_kernel<T, PROX, 4>);
+    else if (K <= 512) launch(cd_gram_kernel<T, PROX, 8>);
+    else if (K <= 1024) launch(cd_gram_kernel<T, PROX, 16>);
+    else if (K <= cd_register_limit()) launch(cd_gram_kernel<T, PROX, 32>);
+    else launch(cd_gram_wide_kernel<T, PROX>);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    return DCP_OK;
+}
+
+// ---------------- coordinate descent, Gram form (mask none or 1-D) ----------------
+// gram_ready: AAt already holds An An^H (parallel_cd's fallback).  it_out: where a deferred count goes.
+template <class T, int PROX>
+inline int lasso_cd_gram(const LassoProblem<T>& p, bool gram_ready, int* it_out, LassoOutcome<T>* out) {
+    LassoWs<T>& w = p.w;
+    const int maxiter = p.maxiter;
+    if (!gram_ready) DCP_TRY(gram_kk<T>(p.h, w.An, w.An, p.K, p.F, w, w.AAt));
+    const GemmArgs<T> g = codes_kk_product<T>(p, w.xb[0], w.AAt);   // G = yAt - x AAt
+    DCP_LAUNCH_OK(p.h, (gemm<FORM_NN>(p.st, g, EpiSubFrom<T>{w.yAt, p.K, w.G, p.K})));
+    // Ten sweeps = a check sweep (0, 10, 20, ...: lasso.py:546-551) launched on its own and the up to nine sweeps
+    // behind it in a second launch that the DEVICE skips when the check sweep met the test (its flag is still
+    // zero): the codes are then exactly those the reference returns, and nothing on the host has to read the flag
+    // between the two launches.  The flag travels to pinned host memory behind them (flag_publish_kernel) and is
+    // polled only where the host needs it: to decide on ANOTHER ten sweeps, or for *it_out -- which the
+    // dictionary step defers to the end of the step (LassoExtra::no_final_sync), so that its default solve
+    // (cd x 10) puts no host round trip into the middle of the step.
+    // (Rounds 3-4 ran one launch per ten sweeps with the post-check codes parked in a snapshot and read the flag
+    // synchronously: ~37 us of idle GPU per solve in the kernel trace, plus a fill and a copy kernel.)
+    int sweep = 0;
+    while (sweep < maxiter) {
+        int last = sweep + 9;
+        if (last > maxiter - 1) last = maxiter - 1;
+        // (w.flag is zero here: lasso_scalars_kernel at the start of the solve, flag_publish_kernel afterwards)
+        DCP_TRY((launch_cd_gram<T, PROX>(p, 1, 1, nullptr)));                              // the check sweep
+        if (last > sweep) DCP_TRY((launch_cd_gram<T, PROX>(p, last - sweep, 0, w.flag)));  // the rest, unless met
+        *reinterpret_cast<volatile int*>(p.host_flag) = -1;                 // sentinel: nothing has landed yet
+        hipLaunchKernelGGL(flag_publish_kernel<void>, dim3(1), dim3(64), 0, p.st, w.flag, p.host_flag);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+        if (last == maxiter - 1 && p.extra.no_final_sync) {
+            // the last ten sweeps of a solve inside the dictionary step: *it_out is settled by
+            // lasso_settle_deferred() once the rest of the step has been enqueued
+            p.h->lasso_deferred_flag = p.host_flag;
+            p.h->lasso_deferred_it = it_out;
+            p.h->lasso_deferred_it_met = sweep;
+            break;
+        }
+        DCP_TRY(poll_host_flag(p.h, p.host_flag));
+        if (*p.host_flag == 0) {
+            out->it = sweep;
+            break;
+        }
+        sweep = last + 1;
+    }
+    return DCP_OK;
+}
+
+// ---------------- coordinate descent with a 2-D mask (as written) ----------------
+template <class T, int PROX>
+inline int lasso_cd_rows(const LassoProblem<T>& p, LassoOutcome<T>* out) {
+    typedef real_t<T> R;
+    LassoWs<T>& w = p.w;
+    const int N = p.N, F = p.F, K = p.K, maxiter = p.maxiter;
+    T* xcur = w.xb[0];
+    GemmArgs<T> a;   // r = y o M - (x An) o M
+    a.A = xcur; a.lda = K; a.B = w.An; a.ldb = F; a.M = N; a.N = F; a.K = K;
+    a.ext_ws = w.ext1;
+    DCP_LAUNCH_OK(p.h, (gemm<FORM_NN>(p.st, a, EpiMaskedResidual<T>{w.Ym, p.mask, w.T1, (long)F})));
+    // A_k . conj(A_k) of the normalised rows, as the reference evaluates it (== 1 up to rounding)
+    hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(K), dim3(256), 0, p.st, (const T*)w.An, (long)F,
+                       (long)F, 1, (const T*)nullptr, 0L, w.Am, (long)F, (R*)nullptr, w.akk);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    hipLaunchKernelGGL((square_vec_kernel<R>), dim3(grid_for(K, 64)), dim3(256), 0, p.st,
+                       (const R*)w.akk, (long)K, w.akk);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    int sweep = 0;
+    while (sweep < maxiter) {
+        int last = (sweep % 10 == 0) ? sweep : (sweep / 10 + 1) * 10;
+        int check_last = 1;
+        if (last > maxiter - 1) { last = maxiter - 1; check_last = (last % 10 == 0); }
+        const int ns = last - sweep + 1;
+        DCP_HIP_OK(p.h, hipMemsetAsync(w.flag, 0, sizeof(int), p.st));
+        hipLaunchKernelGGL((cd_mask_kernel<T, PROX>), dim3(N), dim3(256), 0, p.st, xcur, w.T1,
+                           (const T*)w.An, p.mask, (const R*)w.akk, (const R*)w.alphak,
+                           (const R*)w.rowscale, (const R*)w.tolk, K, (long)F, ns, check_last,
+                           w.flag);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+        sweep = last + 1;
+        if (check_last) {
+            bool viol = true;
+            DCP_TRY(read_scalar(p.h, (const int*)w.flag, &viol, p.host_flag));
+            if (!viol) { out->it = last; break; }
+        }
+    }
+    return DCP_OK;
+}
+
+// ---------------- parallel coordinate descent (lasso.py:476-484, 515-523) ----------------
+// p = int(K / Gershgorin(A A^H)) coordinates per row and iteration, unmasked Gram matrix in every variant
+// (lasso.py:464-470, 503-509); p <= 1 falls back to plain coordinate descent.
+template <class T, int PROX>
+inline int lasso_pcd(const LassoProblem<T>& p, int* it_out, LassoOutcome<T>* out) {
+    typedef real_t<T> R;
+    LassoWs<T>& w = p.w;
+    const int K = p.K;
+    DCP_TRY(gram_kk<T>(p.h, w.An, w.An, K, p.F, w, w.AAt));
+    DCP_TRY(gershgorin_bound<T>(p.h, w.AAt, K, w));
+    R bound = 0;
+    DCP_TRY(read_scalar(p.h, (const R*)(w.scal + 2), &bound,
+                        reinterpret_cast<R*>(reinterpret_cast<char*>(p.host_flag) + 16)));
+    const R ratio = (R)K / bound;
+    const int pcd_p = (ratio == ratio && ratio < R(2147483647)) ? (int)ratio : 0;
+    if (pcd_p <= 1) {
+        if (p.mask_ndim == 2)
+            return fail(p.h, DCP_ERR_REF_TYPEERROR,
+                        "parallel_cd with a full mask and p <= 1: the reference's fallback call "
+                        "raises TypeError (lasso.py:509)");
+        return lasso_cd_gram<T, PROX>(p, true, it_out, out);
+    }
+    if (p.extra.order == nullptr || p.extra.order_rows < (int64_t)p.maxiter)
+        return fail(p.h, DCP_ERR_INVALID, "parallel_cd needs a shuffle table of >= maxiter rows");
+    // iteration i reads x0 from xb[i & 1], leaves x0 + dx * select in the other and its full update in xb[2]
+    T* Xnew = w.xb[2];
+    int met_at = -1;
+    DCP_TRY(sync_checked_loop(p, [&](int i, int check) -> int {
+        T* X0 = w.xb[i & 1];
+        EpiPcdStep<T, PROX> epi{w.yAt, X0, Xnew, w.xb[(i & 1) ^ 1], (long)K, w.alphak, w.tolk, p.rowscale,
+                                p.extra.order + (long)i * K, pcd_p, check, w.flag};
+        if (p.mask_ndim == 2) return masked_back_projection(p, X0, epi);
+        DCP_LAUNCH_OK(p.h, (gemm<FORM_NN>(p.st, codes_kk_product<T>(p, X0, w.AAt), epi)));   // back = x0 AAt
+        return DCP_OK;
+    }, &met_at));
+    if (met_at >= 0) out->it = met_at;
+    out->result = met_at >= 0 ? Xnew : w.xb[p.maxiter & 1];   // met: the full update (lasso.py:479-480)
+    return DCP_OK;
+}
+
+// ---------------- ADMM (lasso.py:586-618) ----------------
+template <class T, int PROX>
+inline int lasso_admm(const LassoProblem<T>& p, LassoOutcome<T>* out) {
+    typedef real_t<T> R;
+    typedef work_t<T> TW;
+    LassoWs<T>& w = p.w;
+    const int N = p.N, K = p.K;
+    const R rho = (R)p.extra.rho;
+    T* xcur = w.xb[0];
+    DCP_TRY(gram_kk<T>(p.h, w.An, w.An, K, p.F, w, w.AAt));
+    hipLaunchKernelGGL((inv_load_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, p.st,
+                       (const T*)w.AAt, K, p.extra.rho, w.inv_a);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    TW* src = w.inv_a;
+    TW* dst = w.inv_b;
+    for (int k = 0; k < K; ++k) {
+        hipLaunchKernelGGL((gj_step_kernel<TW>), dim3(grid_for((long)K * K)), dim3(256), 0, p.st,
+                           (const TW*)src, dst, K, k);
+        TW* t = src; src = dst; dst = t;
+    }
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    T* Minv = w.AAt;     // (AAt + rho I)^-1 replaces AAt
+    hipLaunchKernelGGL((inv_store_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, p.st,
+                       (const TW*)src, (long)K * K, Minv);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    T* U = w.xb[1];
+    hipLaunchKernelGGL((admm_init_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, p.st,
+                       (const T*)w.yAt, (const T*)xcur, (long)N * K, rho, U, w.xb[2]);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    DCP_TRY(sync_checked_loop(p, [&](int i, int check) -> int {
+        T* V = w.xb[2 + (i & 1)];    // v ping-pongs between xb[2] and xb[3]
+        T* Vn = w.xb[3 - (i & 1)];
+        EpiAdmmStep<T, PROX> epi{w.yAt, xcur, U, Vn, (long)K, w.alphak, w.tolk, rho, check, w.flag};
+        DCP_LAUNCH_OK(p.h, (gemm<FORM_NN>(p.st, codes_kk_product<T>(p, V, Minv), epi)));   // x_new = V Minv
+        return DCP_OK;
+    }, &out->it));   // lasso.py:612-614
+    return DCP_OK;
+}
+
+// ---------------- ADMM with a 2-D mask: one K x K system per row (lasso.py:621-657) ----------------
+template <class T, int PROX>
+inline int lasso_admm_rows(const LassoProblem<T>& p, LassoOutcome<T>* out) {
+    typedef real_t<T> R;
+    typedef work_t<T> TW;
+    LassoWs<T>& w = p.w;
+    const int N = p.N, K = p.K;
+    const R rho = (R)p.extra.rho;
+    T* xcur = w.xb[0];
+    // dynamic LDS of the two per-row kernels: pivot row + column (2 K work elements) and V (K elements);
+    // beyond the default 64 KiB the per-function cap is raised, up to the CU's 160 KiB (K <= 10240 real,
+    // 5120 complex -- where ONE row's K x K system is already 0.8 GB; the reference, lasso.py:620-657,
+    // holds the same N K^2 array)
+    const size_t gj_lds = (size_t)2 * K * sizeof(TW), step_lds = (size_t)K * sizeof(T);
+    if (gj_lds > 160 * 1024)
+        return fail(p.h, DCP_ERR_UNSUPPORTED, "masked admm: n_features too large for the per-row inverse");
+    if (gj_lds > 65536)
+        DCP_HIP_OK(p.h, hipFuncSetAttribute(reinterpret_cast<const void*>(&gj_batched_kernel<TW>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)gj_lds));
+    if (step_lds > 65536)
+        DCP_HIP_OK(p.h, hipFuncSetAttribute(reinterpret_cast<const void*>(&admm_mask_step_kernel<T, PROX>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds));
+    hipLaunchKernelGGL((admm_mask_system_kernel<T>), dim3(N), dim3(256), 0, p.st, (const T*)w.An, p.mask,
+                       K, (long)p.F, p.extra.rho, w.inv_a);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    hipLaunchKernelGGL((gj_batched_kernel<TW>), dim3(N), dim3(256), (size_t)2 * K * sizeof(TW), p.st,
+                       w.inv_a, K);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    T* U = w.xb[1];
+    T* V = w.xb[2];
+    hipLaunchKernelGGL((admm_init_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, p.st,
+                       (const T*)w.yAt, (const T*)xcur, (long)N * K, rho, U, V);
+    DCP_LAUNCH_OK(p.h, hipGetLastError());
+    DCP_TRY(sync_checked_loop(p, [&](int, int check) -> int {
+        hipLaunchKernelGGL((admm_mask_step_kernel<T, PROX>), dim3(N), dim3(256),
+                           (size_t)K * sizeof(T), p.st, (const T*)w.yAt, (const TW*)w.inv_a, xcur, U, V,
+                           K, (const R*)w.alphak, (const R*)w.rowscale, (const R*)w.tolk, rho, check,
+                           w.flag);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+        return DCP_OK;
+    }, &out->it));
+    return DCP_OK;
+}
+
+// ---------------- ista / acc_ista / fista ----------------
+template <class T, int PROX>
+inline int lasso_prox(const LassoProblem<T>& p, int method, LassoOutcome<T>* out) {
+    typedef real_t<T> R;
+    LassoWs<T>& w = p.w;
+    const int N = p.N, F = p.F, K = p.K;
+    const T* Abar = w.An;
+    if (p.mask_ndim == 2) {   // Lipschitz bound from (A o mean_batch(M)) A^H   (lasso.py:317)
+        DCP_TRY(column_sums<R>(p.h, p.mask, F, N, F, w.part, w.mbar));
+        hipLaunchKernelGGL((scale_vec_kernel<R>), dim3(grid_for(F, 64)), dim3(256), 0, p.st,
+                           (const R*)w.mbar, (long)F, R(N), w.mbar);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for((long)K * F)), dim3(256), 0, p.st,
+                           (const T*)w.An, (const R*)w.mbar, (long)K, (long)F, 0L, w.Am);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+        Abar = w.Am;
+    }
+    DCP_TRY(gram_kk<T>(p.h, Abar, w.An, K, F, w, w.AAt));
+    DCP_TRY(gershgorin_bound<T>(p.h, w.AAt, K, w));
+    if (p.mask_ndim != 2) {   // AAt becomes H = I - Linv A A^H (see EpiProxStepH); xb[0] = x * s in the same pass
+        hipLaunchKernelGGL((hform_prepare_kernel<T>), dim3(grid_for((long)K * K + (long)N * K)), dim3(256), 0, p.st,
+                           w.AAt, (long)K, w.yAt, (long)N * K, (const R*)w.scal, (const T*)p.X, (const R*)w.s, w.xb[0]);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+    }
+    const bool mom = (method != DCP_LASSO_ISTA);
+    bool wrote_final = false;
+    auto step = [&](int i, T* V, T* P, T* Nw, T* Vn, R coef, int check, bool is_last) -> int {
+        if (p.mask_ndim == 2) {   // back = ((V An) o M) An^H, prox step in the epilogue
+            EpiProxStep<T, PROX> epi{w.yAt, V, P, Nw, Vn, (long)K, w.scal, w.alphak, w.tolk, p.rowscale, coef, check,
+                                     w.flag};
+            return masked_back_projection(p, V, epi);
+        }
+        GemmArgs<T> a = codes_kk_product<T>(p, V, w.AAt);   // back = V H, prox step in the epilogue
+        // complex: the extended image of A A^H (ext2 holds nothing else during the loop) is built by
+        // the first iteration and reused by the others (a product with fewer samples than atoms takes
+        // the planar-rows form instead, which images V and ignores this flag)
+        a.ext_ready = i > 0 && gemm_route<FORM_NN>(a).image != IMG_ROWS_A;
+        // float32, >= 512 atoms, at least one 128 x 128 tile per two CUs: the 8-wave 128 x 128 x 64 tile
+        // (8192 x 512 x 512: 45 us against 50 us on the 64 x 64 tile for the bare product; dictionary step
+        // 1.64 -> 1.62 ms).  complex64 measured slower on it and keeps the automatic choice.
+        if (std::is_same<T, float>::value && K >= 512 && (long)ceil_div(N, 128) * ceil_div(K, 128) >= 128)
+            a.tile = TILE_MID;
+        EpiProxStepH<T, PROX> epih{w.yAt, P, Nw, Vn, (long)K, w.scal, w.alphak, w.tolk,
+                                   coef, check, (check || mom) ? 1 : 0, w.flag};
+        if (is_last && method != DCP_LASSO_ACC_ISTA) {   // the iterate lasso.py:297 / :415 return
+            epih.xfinal = p.X;
+            epih.sdiv = w.s;
+            wrote_final = true;
+        }
+        DCP_LAUNCH_OK(p.h, (gemm<FORM_NN>(p.st, a, epih)));
+        return DCP_OK;
+    };
+    ProxLoopResult<T> res;
+    DCP_TRY(prox_gradient_loop<T>(p.h, w.xb, method, p.maxiter, w.flag, p.host_flag, step, &res));
+    *out = LassoOutcome<T>{res.it, res.result, wrote_final && !res.converged};
+    return DCP_OK;
+}
+
+// X = x / s (lasso.py:189) unless the solver's last epilogue wrote it, the optional synchronisation, *it_out.
+template <class T>
+inline int lasso_finish(const LassoProblem<T>& p, const LassoOutcome<T>& out, int* it_out) {
+    if (!out.final_in_place) {
+        hipLaunchKernelGGL((col_scale_kernel<T>), dim3(grid_for((long)p.N * p.K)), dim3(256), 0, p.st,
+                           (const T*)out.result, (const real_t<T>*)p.w.s, (long)p.N, (long)p.K, 0, p.X);
+        DCP_LAUNCH_OK(p.h, hipGetLastError());
+    }
+    if (!p.extra.no_final_sync) DCP_HIP_OK(p.h, hipStreamSynchronize(p.st));
+    *it_out = out.it;
+    return DCP_OK;
+}
+
 // solve_fastpath (lasso.py:97-189).  Y [N,F], A [K,F], X [N,K] (in: initial estimate, out:
 // solution), mask: null, [F] (mask_ndim 1) or [N,F] (mask_ndim 2).  *it_out as the reference.
 template <class T, int PROX>
@@ -840,469 +1250,25 @@ inline int lasso_solve(dcp_handle* h, const T* Y, const real_t<T>* mask, int mas
                        int maxiter, int method, int* it_out, LassoWs<T>& w,
                        const LassoExtra& extra = LassoExtra()) {
     typedef real_t<T> R;
-    hipStream_t st = h->stream;
     h->lasso_deferred_flag = nullptr;   // (a deferral an earlier, failed call never settled dies here)
     h->lasso_deferred_it = nullptr;
     h->lasso_deferred_copy = false;
-    const int N = (int)N64, F = (int)F64, K = (int)K64;
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, 64, &hostv));
-    int* host_flag = reinterpret_cast<int*>(hostv);
-
-    // ---- 1-D mask folds into y and A (lasso.py:120-122); any mask: Ym = y o M ----
-    const T* Ause = A;
-    const T* Yuse = Y;
-    if (mask_ndim == 1) {
-        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for((long)K * F)), dim3(256), 0, st, A, mask,
-                           (long)K, (long)F, 0L, w.An);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        Ause = w.An;
-        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for((long)N * F)), dim3(256), 0, st, Y, mask,
-                           (long)N, (long)F, 0L, w.Ym);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        Yuse = w.Ym;
-        hipLaunchKernelGGL((reduce_vector_kernel<SumOp, R, FinStore<R>>), dim3(1), dim3(256), 0, st, mask, (long)F,
-                           FinStore<R>{w.scal + 1});   // sum(mask)
-        DCP_LAUNCH_OK(h, hipGetLastError());
-    } else if (mask_ndim == 2) {
-        hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for((long)N * F)), dim3(256), 0, st, Y, mask,
-                           (long)N, (long)F, (long)F, w.Ym);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        Yuse = w.Ym;
-        hipLaunchKernelGGL((rowsum_kernel<R>), dim3(N), dim3(256), 0, st, mask, (long)F, (long)F,
-                           w.rowscale);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-    }
-    // ---- A scaling (lasso.py:124-131): s = |A_k|, An = A / s, alpha/s, tol*s, x*s ----
-    hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(K), dim3(256), 0, st, Ause, (long)F, (long)F, 1,
-                       (const T*)nullptr, 0L, w.An, (long)F, (R*)nullptr, w.s);
-    DCP_LAUNCH_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((lasso_scalars_kernel<R>), dim3(grid_for(K, 64)), dim3(256), 0, st, w.s, (long)K,
-                       alpha, tol, mask_ndim == 1 ? w.scal + 1 : (const R*)nullptr,
-                       mask_ndim == 2 ? R(1) : R(F), w.alphak, w.tolk, w.flag);
-    DCP_LAUNCH_OK(h, hipGetLastError());
-    T* xcur = w.xb[0];
+    const LassoProblem<T> p{h, h->stream, (int)N64, (int)F64, (int)K64, mask, mask_ndim,
+                            mask_ndim == 2 ? (const R*)w.rowscale : nullptr, X, w, reinterpret_cast<int*>(hostv),
+                            maxiter, extra};
+    const bool prox = method == DCP_LASSO_ISTA || method == DCP_LASSO_ACC_ISTA || method == DCP_LASSO_FISTA;
     // ista / acc_ista / fista without a 2-D mask: x * s is formed by hform_prepare_kernel in its pass over [N, K]
-    const bool hform_family = (method == DCP_LASSO_ISTA || method == DCP_LASSO_ACC_ISTA || method == DCP_LASSO_FISTA) &&
-                              mask_ndim != 2;
-    if (!hform_family) {
-        hipLaunchKernelGGL((col_scale_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, st, (const T*)X,
-                           (const R*)w.s, (long)N, (long)K, 1, xcur);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-    }
-
-    // ---- yAt = (y o M) An^H ----
-    {
-        GemmArgs<T> a;
-        a.A = Yuse; a.lda = F; a.B = w.An; a.ldb = F; a.M = N; a.N = K; a.K = F; a.conjB = true;
-        a.ext_ws = w.ext1;
-        // deep reduction, few big tiles: ordered split-K partials in the (still unused) iterate buffers
-        const long stride = (long)(w.xb[2] - w.xb[1]);
-        const int ys = (stride >= (long)N * K && w.xb[3] - w.xb[2] == stride) ? plan_deep_nt(a, 3) : 1;
-        if (ys > 1) {
-            DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, a, EpiSlab<T>{w.xb[1], K, stride})));
-            launch_reduce_slabs<T>(st, (const T*)w.xb[1], stride, ys, (long)N * K, w.yAt);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-        } else {
-            DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, a, EpiStore<T>{w.yAt, K})));
-        }
-    }
-    if (extra.start_prefetch) DCP_TRY(start_registered_prefetch(h));
-    const R* rowscale = mask_ndim == 2 ? w.rowscale : nullptr;
-    int it = maxiter - 1;
-    T* result = xcur;
-    bool final_in_place = false;   // the last iteration's epilogue already wrote result / s into X
-
-    // ---- parallel_cd: p = int(K / Gershgorin(A A^H)), unmasked Gram matrix in every variant
-    //      (lasso.py:464-470, 503-509); p <= 1 falls back to plain coordinate descent ----
-    bool have_gram = false;
-    int pcd_p = 0;
-    if (method == DCP_LASSO_PARALLEL_CD) {
-        DCP_TRY(gram_kk<T>(h, w.An, w.An, K, F, w, w.AAt));
-        have_gram = true;
-        DCP_TRY(gershgorin_bound<T>(h, w.AAt, K, w));
-        R bound = 0;
-        DCP_TRY(read_scalar(h, (const R*)(w.scal + 2), &bound,
-                            reinterpret_cast<R*>(reinterpret_cast<char*>(hostv) + 16)));
-        const R ratio = (R)K / bound;
-        pcd_p = (ratio == ratio && ratio < R(2147483647)) ? (int)ratio : 0;
-        if (pcd_p <= 1) {
-            if (mask_ndim == 2)
-                return fail(h, DCP_ERR_REF_TYPEERROR,
-                            "parallel_cd with a full mask and p <= 1: the reference's fallback call "
-                            "raises TypeError (lasso.py:509)");
-            method = DCP_LASSO_CD;
-        } else if (extra.order == nullptr || extra.order_rows < (int64_t)maxiter) {
-            return fail(h, DCP_ERR_INVALID, "parallel_cd needs a shuffle table of >= maxiter rows");
-        }
-    }
-
-    if (method == DCP_LASSO_PARALLEL_CD) {
-        // ---------------- parallel coordinate descent (lasso.py:476-484, 515-523) ----------------
-        T* X0 = xcur;
-        T* Xn = w.xb[1];
-        T* Xnew = w.xb[2];
-        bool converged = false;
-        for (int i = 0; i < maxiter; ++i) {
-            const int check = (i % 10 == 0) ? 1 : 0;
-            if (check) DCP_HIP_OK(h, hipMemsetAsync(w.flag, 0, sizeof(int), st));
-            EpiPcdStep<T, PROX> epi{w.yAt, X0, Xnew, Xn, (long)K, w.alphak, w.tolk, rowscale,
-                                    extra.order + (long)i * K, pcd_p, check, w.flag};
-            if (mask_ndim == 2) {
-                GemmArgs<T> a1;   // T1 = (x0 An) o M
-                a1.A = X0; a1.lda = K; a1.B = w.An; a1.ldb = F; a1.M = N; a1.N = F; a1.K = K;
-                a1.ext_ws = w.ext1;
-                DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a1, EpiMulMask<T>{mask, F, w.T1, F})));
-                GemmArgs<T> a2;   // back = T1 An^H
-                a2.A = w.T1; a2.lda = F; a2.B = w.An; a2.ldb = F; a2.M = N; a2.N = K; a2.K = F;
-                a2.conjB = true;
-                a2.ext_ws = w.ext1;
-                DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, a2, epi)));
-            } else {
-                GemmArgs<T> a;    // back = x0 AAt
-                a.A = X0; a.lda = K; a.B = w.AAt; a.ldb = K; a.M = N; a.N = K; a.K = K;
-                a.ext_ws = w.ext2;
-                DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a, epi)));
-            }
-            if (check) {
-                bool viol = true;
-                DCP_TRY(read_flag<T>(h, w.flag, host_flag, &viol));
-                if (!viol) { it = i; result = Xnew; converged = true; break; }   // lasso.py:479-480
-            }
-            T* t = X0; X0 = Xn; Xn = t;                                          // x0 += dx * select
-        }
-        if (!converged) result = X0;
-    } else if (method == DCP_LASSO_ADMM && mask_ndim != 2) {
-        // ---------------- ADMM (lasso.py:586-618) ----------------
-        typedef work_t<T> TW;
-        const R rho = (R)extra.rho;
-        DCP_TRY(gram_kk<T>(h, w.An, w.An, K, F, w, w.AAt));
-        hipLaunchKernelGGL((inv_load_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, st,
-                           (const T*)w.AAt, K, extra.rho, w.inv_a);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        TW* src = w.inv_a;
-        TW* dst = w.inv_b;
-        for (int k = 0; k < K; ++k) {
-            hipLaunchKernelGGL((gj_step_kernel<TW>), dim3(grid_for((long)K * K)), dim3(256), 0, st,
-                               (const TW*)src, dst, K, k);
-            TW* t = src; src = dst; dst = t;
-        }
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        T* Minv = w.AAt;     // (AAt + rho I)^-1 replaces AAt
-        hipLaunchKernelGGL((inv_store_kernel<T>), dim3(grid_for((long)K * K)), dim3(256), 0, st,
-                           (const TW*)src, (long)K * K, Minv);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        T* U = w.xb[1];
-        T* V = w.xb[2];
-        T* Vn = w.xb[3];
-        hipLaunchKernelGGL((admm_init_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, st,
-                           (const T*)w.yAt, (const T*)xcur, (long)N * K, rho, U, V);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        for (int i = 0; i < maxiter; ++i) {
-            const int check = (i % 10 == 0) ? 1 : 0;
-            if (check) DCP_HIP_OK(h, hipMemsetAsync(w.flag, 0, sizeof(int), st));
-            EpiAdmmStep<T, PROX> epi{w.yAt, xcur, U, Vn, (long)K, w.alphak, w.tolk, rho, check, w.flag};
-            GemmArgs<T> a;    // x_new = V Minv
-            a.A = V; a.lda = K; a.B = Minv; a.ldb = K; a.M = N; a.N = K; a.K = K;
-            a.ext_ws = w.ext2;
-            DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a, epi)));
-            if (check) {
-                bool viol = true;
-                DCP_TRY(read_flag<T>(h, w.flag, host_flag, &viol));
-                if (!viol) { it = i; break; }                                    // lasso.py:612-614
-            }
-            T* t = V; V = Vn; Vn = t;
-        }
-        result = xcur;
-    } else if (method == DCP_LASSO_ADMM) {
-        // ---------------- ADMM with a 2-D mask: one K x K system per row (lasso.py:621-657) --------
-        typedef work_t<T> TW;
-        const R rho = (R)extra.rho;
-        // dynamic LDS of the two per-row kernels: pivot row + column (2 K work elements) and V (K elements);
-        // beyond the default 64 KiB the per-function cap is raised, up to the CU's 160 KiB (K <= 10240 real,
-        // 5120 complex -- where ONE row's K x K system is already 0.8 GB; the reference, lasso.py:620-657,
-        // holds the same N K^2 array)
-        const size_t gj_lds = (size_t)2 * K * sizeof(TW), step_lds = (size_t)K * sizeof(T);
-        if (gj_lds > 160 * 1024)
-            return fail(h, DCP_ERR_UNSUPPORTED, "masked admm: n_features too large for the per-row inverse");
-        if (gj_lds > 65536)
-            DCP_HIP_OK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&gj_batched_kernel<TW>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)gj_lds));
-        if (step_lds > 65536)
-            DCP_HIP_OK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&admm_mask_step_kernel<T, PROX>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds));
-        hipLaunchKernelGGL((admm_mask_system_kernel<T>), dim3(N), dim3(256), 0, st, (const T*)w.An, mask,
-                           K, (long)F, extra.rho, w.inv_a);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((gj_batched_kernel<TW>), dim3(N), dim3(256), (size_t)2 * K * sizeof(TW), st,
-                           w.inv_a, K);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        T* U = w.xb[1];
-        T* V = w.xb[2];
-        hipLaunchKernelGGL((admm_init_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, st,
-                           (const T*)w.yAt, (const T*)xcur, (long)N * K, rho, U, V);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        for (int i = 0; i < maxiter; ++i) {
-            const int check = (i % 10 == 0) ? 1 : 0;
-            if (check) DCP_HIP_OK(h, hipMemsetAsync(w.flag, 0, sizeof(int), st));
-            hipLaunchKernelGGL((admm_mask_step_kernel<T, PROX>), dim3(N), dim3(256),
-                               (size_t)K * sizeof(T), st, (const T*)w.yAt, (const TW*)w.inv_a, xcur, U, V,
-                               K, (const R*)w.alphak, (const R*)w.rowscale, (const R*)w.tolk, rho, check,
-                               w.flag);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            if (check) {
-                bool viol = true;
-                DCP_TRY(read_flag<T>(h, w.flag, host_flag, &viol));
-                if (!viol) { it = i; break; }
-            }
-        }
-        result = xcur;
-    } else if (method == DCP_LASSO_CD && mask_ndim != 2) {
-        // ---------------- coordinate descent, Gram form ----------------
-        if (!have_gram) DCP_TRY(gram_kk<T>(h, w.An, w.An, K, F, w, w.AAt));
-        {   // g = yAt - x AAt
-            GemmArgs<T> a;
-            a.A = xcur; a.lda = K; a.B = w.AAt; a.ldb = K; a.M = N; a.N = K; a.K = K;
-            a.ext_ws = w.ext2;
-            DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a, EpiSubFrom<T>{w.yAt, K, w.G, K})));
-        }
-        // Ten sweeps = a check sweep (0, 10, 20, ...: lasso.py:546-551) launched on its own and the up to nine sweeps
-        // behind it in a second launch that the DEVICE skips when the check sweep met the test (its flag is still
-        // zero): the codes are then exactly those the reference returns, and nothing on the host has to read the flag
-        // between the two launches.  The flag travels to pinned host memory behind them (flag_publish_kernel) and is
-        // polled only where the host needs it: to decide on ANOTHER ten sweeps, or for *it_out -- which the
-        // dictionary step defers to the end of the step (LassoExtra::no_final_sync), so that its default solve
-        // (cd x 10) puts no host round trip into the middle of the step.
-        // (Rounds 3-4 ran one launch per ten sweeps with the post-check codes parked in a snapshot and read the flag
-        // synchronously: ~37 us of idle GPU per solve in the kernel trace, plus a fill and a copy kernel.)
-        int sweep = 0;
-        result = xcur;
-        const int grid = (N + 3) / 4;
-        auto launch = [&](int ns, int check_first, const int* cond) -> int {
-#define DCP_CD_LAUNCH(MM)                                                                            \
-    hipLaunchKernelGGL((cd_gram_kernel<T, PROX, MM>), dim3(grid), dim3(256), 0, st, xcur, w.G,       \
-                       (const T*)w.AAt, (const R*)w.alphak, (const R*)w.tolk, (long)N, K, ns,        \
-                       check_first, w.flag, cond)
-            // (the register form holds a row's K coefficients in one wave: 64 lanes x up to 32 slots;
-            //  wider dictionaries take the memory-resident form -- the reference has no limit, lasso.py:526-552)
-            if (K <= 64) DCP_CD_LAUNCH(1);
-            else if (K <= 128) DCP_CD_LAUNCH(2);
-            else if (K <= 256) DCP_CD_LAUNCH(4);
-            else if (K <= 512) DCP_CD_LAUNCH(8);
-            else if (K <= 1024) DCP_CD_LAUNCH(16);
-            else if (K <= cd_register_limit()) DCP_CD_LAUNCH(32);
-            else
-                hipLaunchKernelGGL((cd_gram_wide_kernel<T, PROX>), dim3(grid), dim3(256), 0, st, xcur, w.G,
-                                   (const T*)w.AAt, (const R*)w.alphak, (const R*)w.tolk, (long)N, K, ns,
-                                   check_first, w.flag, cond);
-#undef DCP_CD_LAUNCH
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            return DCP_OK;
-        };
-        while (sweep < maxiter) {
-            int last = sweep + 9;
-            if (last > maxiter - 1) last = maxiter - 1;
-            // (w.flag is zero here: lasso_scalars_kernel at the start of the solve, flag_publish_kernel afterwards)
-            DCP_TRY(launch(1, 1, nullptr));                                     // the check sweep
-            if (last > sweep) DCP_TRY(launch(last - sweep, 0, w.flag));         // sweeps sweep + 1 .. last, unless met
-            *reinterpret_cast<volatile int*>(host_flag) = -1;                   // sentinel: nothing has landed yet
-            hipLaunchKernelGGL(flag_publish_kernel<void>, dim3(1), dim3(64), 0, st, w.flag, host_flag);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            if (last == maxiter - 1 && extra.no_final_sync) {
-                // the last ten sweeps of a solve inside the dictionary step: *it_out is settled by
-                // lasso_settle_deferred() once the rest of the step has been enqueued
-                h->lasso_deferred_flag = host_flag;
-                h->lasso_deferred_it = it_out;
-                h->lasso_deferred_it_met = sweep;
-                break;
-            }
-            DCP_TRY(poll_host_flag(h, host_flag));
-            if (*host_flag == 0) {
-                it = sweep;
-                break;
-            }
-            sweep = last + 1;
-        }
-    } else if (method == DCP_LASSO_CD) {
-        // ---------------- coordinate descent with a 2-D mask (as written) ----------------
-        {   // r = y o M - (x An) o M
-            GemmArgs<T> a;
-            a.A = xcur; a.lda = K; a.B = w.An; a.ldb = F; a.M = N; a.N = F; a.K = K;
-            a.ext_ws = w.ext1;
-            DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a, EpiMaskedResidual<T>{w.Ym, mask, w.T1, (long)F})));
-        }
-        // A_k . conj(A_k) of the normalised rows, as the reference evaluates it (== 1 up to rounding)
-        hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(K), dim3(256), 0, st, (const T*)w.An, (long)F,
-                           (long)F, 1, (const T*)nullptr, 0L, w.Am, (long)F, (R*)nullptr, w.akk);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((square_vec_kernel<R>), dim3(grid_for(K, 64)), dim3(256), 0, st,
-                           (const R*)w.akk, (long)K, w.akk);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        int sweep = 0;
-        while (sweep < maxiter) {
-            int last = (sweep % 10 == 0) ? sweep : (sweep / 10 + 1) * 10;
-            int check_last = 1;
-            if (last > maxiter - 1) { last = maxiter - 1; check_last = (last % 10 == 0); }
-            const int ns = last - sweep + 1;
-            DCP_HIP_OK(h, hipMemsetAsync(w.flag, 0, sizeof(int), st));
-            hipLaunchKernelGGL((cd_mask_kernel<T, PROX>), dim3(N), dim3(256), 0, st, xcur, w.T1,
-                               (const T*)w.An, mask, (const R*)w.akk, (const R*)w.alphak,
-                               (const R*)w.rowscale, (const R*)w.tolk, K, (long)F, ns, check_last,
-                               w.flag);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            sweep = last + 1;
-            if (check_last) {
-                bool viol = true;
-                DCP_TRY(read_flag<T>(h, w.flag, host_flag, &viol));
-                if (!viol) { it = last; break; }
-            }
-        }
-        result = xcur;
-    } else {
-        // ---------------- ista / acc_ista / fista ----------------
-        if (mask_ndim == 2) {
-            // Lipschitz bound from (A o mean_batch(M)) A^H   (lasso.py:317)
-            DCP_TRY(column_sums<R>(h, mask, F, N, F, w.part, w.mbar));
-            hipLaunchKernelGGL((scale_vec_kernel<R>), dim3(grid_for(F, 64)), dim3(256), 0, st,
-                               (const R*)w.mbar, (long)F, R(N), w.mbar);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            hipLaunchKernelGGL((mul_mask_kernel<T>), dim3(grid_for((long)K * F)), dim3(256), 0, st,
-                               (const T*)w.An, (const R*)w.mbar, (long)K, (long)F, 0L, w.Am);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            DCP_TRY(gram_kk<T>(h, w.Am, w.An, K, F, w, w.AAt));
-        } else {
-            DCP_TRY(gram_kk<T>(h, w.An, w.An, K, F, w, w.AAt));
-        }
-        DCP_TRY(gershgorin_bound<T>(h, w.AAt, K, w));
-        const bool hform = (mask_ndim != 2);
-        if (hform) {
-            hipLaunchKernelGGL((hform_prepare_kernel<T>), dim3(grid_for((long)K * K + (long)N * K)), dim3(256), 0, st,
-                               w.AAt, (long)K, w.yAt, (long)N * K, (const R*)w.scal, (const T*)X, (const R*)w.s, xcur);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-        }
-
-        // Buffer roles (pointers rotate over the four [N,K] buffers):
-        //   P = the iterate the stop test compares with (the reference's x0)
-        //   V = the point fed to the step (x0 for ista, v / w0 with momentum)
-        //   Nw, Vn = this iteration's outputs (x0_new and the next V)
-        const bool mom = (method != DCP_LASSO_ISTA);
-        T* P = xcur;
-        T* V = xcur;
-        T* lastP = xcur;
-        T* lastNw = xcur;
-        double beta = 1.0;
-        bool converged = false;
-        bool wrote_final = false;
-        // The stop test of a check iteration (i % 10 == 0, lasso.py:293) is read ONE iteration late: its flag
-        // travels to the host (flag_publish_kernel) while iteration i + 1 is already enqueued, so the GPU does not
-        // idle through a host round trip in the middle of every solve (the dictionary step runs ten
-        // iterations and checks at i = 0).  Iteration i + 1 only READS iteration i's output, so when the test
-        // had passed that output is still intact and i + 1 is simply discarded.
-        int pend_i = -1;
-        T* pend_x = nullptr;
-        auto resolve = [&](bool* stop) -> int {
-            *stop = false;
-            if (pend_i < 0) return DCP_OK;
-            DCP_TRY(poll_host_flag(h, host_flag));
-            if (*host_flag == 0) {
-                it = pend_i;
-                result = pend_x;
-                converged = true;
-                *stop = true;
-            }
-            pend_i = -1;
-            return DCP_OK;
-        };
-        for (int i = 0; i < maxiter; ++i) {
-            T* Nw = nullptr;
-            T* Vn = nullptr;
-            for (int b = 0; b < 4; ++b) {
-                T* c = w.xb[b];
-                if (c == P || c == V) continue;
-                if (Nw == nullptr) Nw = c;
-                else if (Vn == nullptr) Vn = c;
-            }
-            R coef = R(0);
-            double beta_new = beta;
-            if (method == DCP_LASSO_ACC_ISTA) {
-                coef = (R)((double)i / (double)(i + 3));                    // lasso.py:353
-            } else if (method == DCP_LASSO_FISTA) {
-                beta_new = 0.5 * (1.0 + sqrt(1.0 + 4.0 * beta * beta));     // lasso.py:411
-                coef = (R)((beta - 1.0) / beta_new);
-            }
-            const int check = (i % 10 == 0) ? 1 : 0;   // (w.flag is zero here: lasso_scalars_kernel, flag_publish_kernel)
-            EpiProxStep<T, PROX> epi{w.yAt, V, P, Nw, mom ? Vn : (T*)nullptr, (long)K, w.scal,
-                                     w.alphak, w.tolk, rowscale, coef, check, w.flag};
-            const bool had_pending = pend_i >= 0;
-            if (mask_ndim == 2) {
-                GemmArgs<T> a1;   // T1 = (V An) o M
-                a1.A = V; a1.lda = K; a1.B = w.An; a1.ldb = F; a1.M = N; a1.N = F; a1.K = K;
-                a1.ext_ws = w.ext1;
-                DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a1, EpiMulMask<T>{mask, F, w.T1, F})));
-                GemmArgs<T> a2;   // back = T1 An^H, prox step in the epilogue
-                a2.A = w.T1; a2.lda = F; a2.B = w.An; a2.ldb = F; a2.M = N; a2.N = K; a2.K = F;
-                a2.conjB = true;
-                a2.ext_ws = w.ext1;
-                DCP_LAUNCH_OK(h, (gemm<FORM_NT>(st, a2, epi)));
-            } else {
-                GemmArgs<T> a;    // back = V H (H = I - Linv A A^H, see EpiProxStepH), prox step in the epilogue
-                a.A = V; a.lda = K; a.B = w.AAt; a.ldb = K; a.M = N; a.N = K; a.K = K;
-                a.ext_ws = w.ext2;
-                // complex: the extended image of A A^H (ext2 holds nothing else during the loop) is built by
-                // the first iteration and reused by the others (a product with fewer samples than atoms takes
-                // the planar-rows form instead, which images V and ignores this flag)
-                a.ext_ready = i > 0 && gemm_route<FORM_NN>(a).image != IMG_ROWS_A;
-                // float32, >= 512 atoms, at least one 128 x 128 tile per two CUs: the 8-wave 128 x 128 x 64 tile
-                // (8192 x 512 x 512: 45 us against 50 us on the 64 x 64 tile for the bare product; dictionary step
-                // 1.64 -> 1.62 ms).  complex64 measured slower on it and keeps the automatic choice.
-                if (std::is_same<T, float>::value && K >= 512 && (long)ceil_div(N, 128) * ceil_div(K, 128) >= 128)
-                    a.tile = TILE_MID;
-                EpiProxStepH<T, PROX> epih{w.yAt, P, Nw, mom ? Vn : (T*)nullptr, (long)K, w.scal, w.alphak, w.tolk,
-                                           coef, check, (check || mom) ? 1 : 0, w.flag};
-                if (i == maxiter - 1 && method != DCP_LASSO_ACC_ISTA) {   // the iterate lasso.py:297 / :415 return
-                    epih.xfinal = X;
-                    epih.sdiv = w.s;
-                    wrote_final = true;
-                }
-                DCP_LAUNCH_OK(h, (gemm<FORM_NN>(st, a, epih)));
-            }
-            if (had_pending) {   // the check iteration before this one: was its test met?  (lasso.py:293-294)
-                bool stop = false;
-                DCP_TRY(resolve(&stop));
-                if (stop) break;   // this iteration is discarded
-            }
-            if (check) {
-                *reinterpret_cast<volatile int*>(host_flag) = -1;   // sentinel: nothing is in flight into it here
-                hipLaunchKernelGGL(flag_publish_kernel<void>, dim3(1), dim3(64), 0, st, w.flag, host_flag);
-                DCP_LAUNCH_OK(h, hipGetLastError());
-                pend_i = i;
-                pend_x = Nw;
-            }
-            lastP = P;
-            lastNw = Nw;
-            P = Nw;
-            V = mom ? Vn : Nw;
-            beta = beta_new;
-        }
-        if (!converged) {   // a check on the very last iteration
-            bool stop = false;
-            DCP_TRY(resolve(&stop));
-        }
-        // QUIRK: on exhaustion ista / fista return the latest iterate, acc_ista the one
-        // before it (its `x0 = x0_new` sits at the top of the loop body, lasso.py:351-357).
-        if (!converged) result = (method == DCP_LASSO_ACC_ISTA) ? lastP : lastNw;
-        final_in_place = wrote_final && !converged;
-    }
-
-    // ---- x / s  (lasso.py:189) ----
-    if (!final_in_place) {
-        hipLaunchKernelGGL((col_scale_kernel<T>), dim3(grid_for((long)N * K)), dim3(256), 0, st,
-                           (const T*)result, (const R*)w.s, (long)N, (long)K, 0, X);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-    }
-    if (!extra.no_final_sync) DCP_HIP_OK(h, hipStreamSynchronize(st));
-    *it_out = it;
-    return DCP_OK;
+    DCP_TRY(lasso_prepare<T>(p, Y, A, alpha, tol, !(prox && mask_ndim != 2)));
+    LassoOutcome<T> out{maxiter - 1, w.xb[0], false};
+    if (method == DCP_LASSO_PARALLEL_CD) DCP_TRY((lasso_pcd<T, PROX>(p, it_out, &out)));
+    else if (method == DCP_LASSO_ADMM && mask_ndim != 2) DCP_TRY((lasso_admm<T, PROX>(p, &out)));
+    else if (method == DCP_LASSO_ADMM) DCP_TRY((lasso_admm_rows<T, PROX>(p, &out)));
+    else if (method == DCP_LASSO_CD && mask_ndim != 2) DCP_TRY((lasso_cd_gram<T, PROX>(p, false, it_out, &out)));
+    else if (method == DCP_LASSO_CD) DCP_TRY((lasso_cd_rows<T, PROX>(p, &out)));
+    else DCP_TRY((lasso_prox<T, PROX>(p, method, &out)));
+    return lasso_finish<T>(p, out, it_out);
 }
 
 }  // namespace dcp

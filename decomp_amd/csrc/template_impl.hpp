@@ -571,8 +571,8 @@ inline int tm_launch_step(dcp_handle* h, const T* r, const T* D, const TmGeom& g
 }
 
 // Structured solve_fastpath for ista / acc_ista / fista (+ _pos).  Y [B, N], D [T, S], X [B, T, C]
-// (in: initial estimate, out: solution).  The stop test of a check iteration (i % 10 == 0) is published to
-// pinned host memory and read one iteration late, as lasso_solve does.
+// (in: initial estimate, out: solution).  The outer loop and its lagged stop test are prox_gradient_loop
+// (prox_loop.hpp), shared with the dense solver.
 template <class T, int PROX>
 inline int tm_lasso_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, real_t<T> alpha,
                           real_t<T> tol, int maxiter, int method, int* it_out) {
@@ -633,81 +633,19 @@ inline int tm_lasso_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmG
     launch_tm_max<R>(st, colsum, TC, R(0), scal);
     DCP_LAUNCH_OK(h, hipGetLastError());
 
-    const bool mom = method != DCP_LASSO_ISTA;
-    T* P = xb[0];
-    T* V = xb[0];
-    T* lastP = xb[0];
-    T* lastNw = xb[0];
-    T* result = xb[0];
-    int it = maxiter - 1;
-    double beta = 1.0;
-    bool converged = false;
-    int pend_i = -1;
-    T* pend_x = nullptr;
-    auto resolve = [&](bool* stop) -> int {
-        *stop = false;
-        if (pend_i < 0) return DCP_OK;
-        DCP_TRY(poll_host_flag(h, host_flag));
-        if (*host_flag == 0) {
-            it = pend_i;
-            result = pend_x;
-            converged = true;
-            *stop = true;
-        }
-        pend_i = -1;
-        return DCP_OK;
-    };
-    for (int i = 0; i < maxiter; ++i) {
-        T* Nw = nullptr;
-        T* Vn = nullptr;
-        for (int q = 0; q < 4; ++q) {
-            T* c = xb[q];
-            if (c == P || c == V) continue;
-            if (Nw == nullptr) Nw = c;
-            else if (Vn == nullptr) Vn = c;
-        }
-        R coef = R(0);
-        double beta_new = beta;
-        if (method == DCP_LASSO_ACC_ISTA) {
-            coef = (R)((double)i / (double)(i + 3));                    // lasso.py:353
-        } else if (method == DCP_LASSO_FISTA) {
-            beta_new = 0.5 * (1.0 + sqrt(1.0 + 4.0 * beta * beta));     // lasso.py:411
-            coef = (R)((beta - 1.0) / beta_new);
-        }
-        const int check = (i % 10 == 0) ? 1 : 0;
-        const bool had_pending = pend_i >= 0;
+    // ---- one iteration: the residual of V, then correlation + prox step into Nw (and Vn) ----
+    auto step = [&](int, T* V, T* P, T* Nw, T* Vn, R coef, int check, bool) -> int {
         DCP_TRY(tm_launch_residual<T>(h, Y, V, rinv, D, g, r));
-        TmStep<T, PROX> ep{V, P, Nw, mom ? Vn : nullptr, rinv, alphak, tolk, scal, coef, check, flag};
-        DCP_TRY((tm_launch_step<T, PROX>(h, r, D, g, ep)));
-        if (had_pending) {
-            bool stop = false;
-            DCP_TRY(resolve(&stop));
-            if (stop) break;
-        }
-        if (check) {
-            *reinterpret_cast<volatile int*>(host_flag) = -1;
-            hipLaunchKernelGGL(flag_publish_kernel<void>, dim3(1), dim3(64), 0, st, flag, host_flag);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            pend_i = i;
-            pend_x = Nw;
-        }
-        lastP = P;
-        lastNw = Nw;
-        P = Nw;
-        V = mom ? Vn : Nw;
-        beta = beta_new;
-    }
-    if (!converged) {
-        bool stop = false;
-        DCP_TRY(resolve(&stop));
-    }
-    // on exhaustion ista / fista return the latest iterate, acc_ista the one before it (lasso.py:357)
-    if (!converged) result = (method == DCP_LASSO_ACC_ISTA) ? lastP : lastNw;
-    hipLaunchKernelGGL((tm_scale_kernel<T>), dim3(tm_grid(BX)), dim3(256), 0, st, (const T*)result, (const R*)rho, BX,
-                       TC, 0, X);
+        TmStep<T, PROX> ep{V, P, Nw, Vn, rinv, alphak, tolk, scal, coef, check, flag};
+        return tm_launch_step<T, PROX>(h, r, D, g, ep);
+    };
+    ProxLoopResult<T> res;
+    DCP_TRY(prox_gradient_loop<T>(h, xb, method, maxiter, flag, host_flag, step, &res));
+    hipLaunchKernelGGL((tm_scale_kernel<T>), dim3(tm_grid(BX)), dim3(256), 0, st, (const T*)res.result, (const R*)rho,
+                       BX, TC, 0, X);
     DCP_LAUNCH_OK(h, hipGetLastError());
     DCP_HIP_OK(h, hipStreamSynchronize(st));
-    *it_out = it;
+    *it_out = res.it;
     return DCP_OK;
 }
 

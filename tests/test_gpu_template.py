@@ -231,6 +231,39 @@ def test_lasso_multi_tile(N, B, s, padding):
     assert _rel(xd.cpu().numpy(), ref) < 1e-10
 
 
+@pytest.mark.parametrize('maxiter', [1, 2, 10, 11, 12, 21, 31])
+@pytest.mark.parametrize('method', ['ista', 'acc_ista', 'fista'])
+def test_structured_lasso_iteration_count_edges(method, maxiter):
+    """The stop bookkeeping of the structured solver (the check every ten iterations is read one iteration late):
+    exhaustion, a check on the very last iteration (maxiter 11, 21), the test met on the last iteration (21 at
+    tol 3e-3), an early exit at iteration 20 with iteration 21 discarded (31 at tol 3e-3), an exit at iteration 0
+    (tol 1e3) -- iteration count and codes against the oracle."""
+    import torch
+    from decomp_amd import template_matching as tm
+    from oracle import template_matching as otm
+    rng = np.random.RandomState(maxiter)
+    B, N, T, S, s, padding, alpha = 3, 48, 2, 7, 2, 'VALID', 0.02
+    C, _ = geom(S, N, s, padding)
+    D = rng.randn(T, S)
+    D /= np.linalg.norm(D, axis=1, keepdims=True)
+    xt = rng.randn(B, T, C) * (rng.uniform(size=(B, T, C)) < 0.1)
+    y = otm.predict(xt, D, N, s, padding) + 0.05 * rng.randn(B, N)
+    yd, Dd = torch.from_numpy(y).cuda(), torch.from_numpy(D).cuda()
+    for tol in (0.0, 3e-3, 1e3):
+        trace = []
+        it_ref, x_ref = otm.lasso_step(y, D, np.zeros((B, T, C)), alpha, s, padding, method, maxiter, tol, trace=trace)
+        stats = [float(np.max(t)) for t in trace]
+        print(method, maxiter, tol, 'it', it_ref, 'stop statistics', stats)
+        if tol > 0:   # no stop decision may hang on rounding: otherwise the inputs are wrong, not the kernel
+            assert all(abs(v) >= 1e-4 for v in stats), stats
+        xd = torch.zeros((B, T, C), dtype=torch.float64, device='cuda')
+        it = tm._lasso(yd, Dd, xd, alpha, s, padding, method, maxiter, tol)
+        err = float(np.max(np.abs(xd.cpu().numpy() - x_ref)))
+        print('  it', it, 'max|x - x_oracle|', err)
+        assert it == it_ref, (tol, it, it_ref)
+        assert err <= 1e-9 * max(1.0, float(np.max(np.abs(x_ref)))), (tol, err)
+
+
 @pytest.mark.parametrize('N,B,s,padding', SHAPES)
 @pytest.mark.parametrize('dtype', ['float64', 'complex128'])
 def test_dstep_multi_tile(N, B, s, padding, dtype):
