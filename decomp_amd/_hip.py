@@ -263,6 +263,14 @@ SIGNATURES = {
     'dcp_tm_pursuit_lds_atoms_f64': (_c_int, []),
     'dcp_tm_pursuit_lds_atoms_c64': (_c_int, []),
     'dcp_tm_pursuit_lds_atoms_c128': (_c_int, []),
+    'dcp_tm_omp_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
+    'dcp_tm_omp_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
+    'dcp_tm_omp_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
+    'dcp_tm_omp_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
+    'dcp_tm_omp_lds_atoms_f32': (_c_int, []),
+    'dcp_tm_omp_lds_atoms_f64': (_c_int, []),
+    'dcp_tm_omp_lds_atoms_c64': (_c_int, []),
+    'dcp_tm_omp_lds_atoms_c128': (_c_int, []),
 }
 
 _lib = None

@@ -721,6 +721,7 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
 }  // namespace dcp
 
 #include "template_pursuit.hpp"   // matching pursuit on the same operator
+#include "template_omp.hpp"       // orthogonal (re-fitting) pursuit on the same operator
 
 // ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip) ------------------------------
 #define DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding)                                    \
@@ -786,6 +787,13 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
                                          positive, it_out);                                                    \
     }                                                                                                          \
     extern "C" int dcp_tm_pursuit_lds_atoms_##SFX(void) { return (int)dcp::tm_pursuit_lds_atoms<TYPE>(); }    \
+    extern "C" int dcp_tm_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,          \
+                                     int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,           \
+                                     int64_t n_steps, double tol, int* it_out) {                              \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        return dcp::tm_omp_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol, it_out);    \
+    }                                                                                                          \
+    extern "C" int dcp_tm_omp_lds_atoms_##SFX(void) { return (int)dcp::tm_omp_lds_atoms<TYPE>(); }            \
     extern "C" int dcp_tm_dstep_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt,        \
                                        void* yX, int64_t B, int64_t T_, int64_t S, int64_t N, int64_t stride, \
                                        int padding, int acc_it, double* maxdiff) {                             \

@@ -253,6 +253,33 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_pursuit_kernel(const T* 
     if (tid == 0 && steps > 0) atomicMax(it_max, steps);
 }
 
+// The prepare launches of the greedy coders: rho2 [K], the lag correlations corr [T, T, 2 S - 1], alpha0 = y A^H
+// [B, K]; clears *it_dev
+template <class T>
+inline int tm_pursuit_prepare(dcp_handle* h, const T* Y, const T* D, const TmGeom& g, real_t<T>* rho2, T* corr,
+                              T* alpha0, int* it_dev) {
+    hipStream_t st = h->stream;
+    const long K = g.T * g.C;
+    hipLaunchKernelGGL((tm_pursuit_rho2_kernel<T>), dim3(tm_grid(K)), dim3(256), 0, st, D, g, rho2, it_dev);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    hipLaunchKernelGGL((tm_lagcorr_kernel<T>), dim3(g.T * g.T), dim3(256), 0, st, D, g, corr);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    {   // alpha0, the batch in slices of at most 65535 signals (the grid's z extent)
+        const long span = 255 * g.s + g.S;
+        size_t bytes = (size_t)(g.S + span) * sizeof(T);
+        const int lds_ok = bytes <= kTmLdsBytes;
+        if (!lds_ok) bytes = 0;
+        for (long b0 = 0; b0 < g.B; b0 += 65535) {
+            TmGeom gs = g;
+            gs.B = g.B - b0 < 65535 ? g.B - b0 : 65535;
+            hipLaunchKernelGGL((tm_corr_store_kernel<T>), dim3((g.C + 255) / 256, g.T, gs.B), dim3(256), bytes, st,
+                               Y + b0 * g.N, D, gs, lds_ok, alpha0 + b0 * K);
+            DCP_LAUNCH_OK(h, hipGetLastError());
+        }
+    }
+    return DCP_OK;
+}
+
 // Y [B, N], D [T, S] -> X [B, T, C]; *it_out = the largest number of steps a signal took.  Synchronises the stream.
 template <class T>
 inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
@@ -273,23 +300,7 @@ inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const T
         a.take(tab, lds ? 0 : g.B * nseg);
         a.take(it_dev, 4);
     }));
-    hipLaunchKernelGGL((tm_pursuit_rho2_kernel<T>), dim3(tm_grid(K)), dim3(256), 0, st, D, g, rho2, it_dev);
-    DCP_LAUNCH_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((tm_lagcorr_kernel<T>), dim3(g.T * g.T), dim3(256), 0, st, D, g, corr);
-    DCP_LAUNCH_OK(h, hipGetLastError());
-    {   // alpha0, the batch in slices of at most 65535 signals (the grid's z extent)
-        const long span = 255 * g.s + g.S;
-        size_t bytes = (size_t)(g.S + span) * sizeof(T);
-        const int lds_ok = bytes <= kTmLdsBytes;
-        if (!lds_ok) bytes = 0;
-        for (long b0 = 0; b0 < g.B; b0 += 65535) {
-            TmGeom gs = g;
-            gs.B = g.B - b0 < 65535 ? g.B - b0 : 65535;
-            hipLaunchKernelGGL((tm_corr_store_kernel<T>), dim3((g.C + 255) / 256, g.T, gs.B), dim3(256), bytes, st,
-                               Y + b0 * g.N, D, gs, lds_ok, alpha0 + b0 * K);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-        }
-    }
+    DCP_TRY(tm_pursuit_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev));
     const R t = tol >= 0.0 ? (R)tol : R(-1);
     if (lds) {
         const size_t bytes = tm_pursuit_lds_bytes<T>(K);

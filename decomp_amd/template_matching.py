@@ -12,7 +12,10 @@ size is formed on the hot path (include/decomp_hip.h ``dcp_tm_*``, decomp_amd/cs
     the coefficients, and D is updated by one fused chain of small kernels;
   * ``pursuit`` (not in the reference) is greedy matching pursuit on the same operator, the coder with a given
     number of events per signal: one correlation pass, then one workgroup per signal that keeps the correlations
-    up to date from the lag correlations of the templates (decomp_amd/csrc/template_pursuit.hpp).
+    up to date from the lag correlations of the templates (decomp_amd/csrc/template_pursuit.hpp);
+  * ``orthogonal_pursuit`` (not in the reference) is its re-fitting form, batch OMP on the same operator: the Gram
+    entries of the support are single reads of the lag correlations, the factor an s x s Cholesky per signal
+    (decomp_amd/csrc/template_omp.hpp).
 
 'cd', 'parallel_cd' and 'admm' have no structured form: for them ``_temp2mat`` is materialised on the
 device and the dense ``dcp_lasso_*`` solvers of decomp_amd.lasso run on it.  That path is correct but
@@ -220,6 +223,60 @@ def pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME', posi
     stay on the device.  Runs in libdecomp_hip.so (``dcp_tm_pursuit_*``, decomp_amd/csrc/template_pursuit.hpp).
     """
     from . import omp
+    kind, stride, T, S, N, C = _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding)
+    tol_c = omp.check_tol(tol)
+    if n_nonzero_coefs is None:
+        n_steps = T * C
+    elif not _is_int(n_nonzero_coefs) or not 1 <= int(n_nonzero_coefs) <= T * C:
+        raise ValueError('n_nonzero_coefs must be an integer in [1, T C = {0:d}]. Given {1!r}'.format(
+            T * C, n_nonzero_coefs))
+    else:
+        n_steps = int(n_nonzero_coefs)
+    if not isinstance(positive, (bool, np.bool_)):
+        raise ValueError('positive must be a bool. Given {0!r}'.format(positive))
+    if positive and _arrays.np_dtype(y).kind == 'c':
+        raise ValueError('positive=True needs a real dtype.')
+
+    return _pursuit_call('pursuit', kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c, 1 if positive else 0)
+
+
+def orthogonal_pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME'):
+    """
+    Orthogonal matching pursuit of every signal on the shift-invariant dictionary of the templates: take at most
+    ``n_nonzero_coefs`` events per signal, re-fitting the coefficients of all events taken so far after each one, or
+    stop once the residual energy |y - x * D|^2 is <= ``tol``.
+
+    y: [..., N]; D: templates [T, S], S <= N, used as given (not normalised); float or complex, both of one dtype.
+    With A[(t, c), n] = D[t, n - stride c + Q] and rho2[t, c] = |A_(t,c)|^2 over the taps inside the signal, a step
+    takes the atom outside the support with the largest |r . A_(t,c)^H|^2 / rho2 (the lowest flat index t C + c on
+    ties); x on the support is then the least-squares fit of y, so the residual is orthogonal to every atom taken and
+    overlapping events are not biased as they are in ``pursuit``.  A signal also stops when no atom scores above zero
+    or the best atom is numerically in the span of the support (its Cholesky pivot is <= 4096 eps rho2).
+    ``n_nonzero_coefs`` is an integer in [1, min(T C, cap)], cap = 64 for real and 32 for complex dtypes (that of
+    ``omp.solve``); with ``tol`` alone the limit is min(T C, cap).  Longer recordings are coded in windows.
+    Returns (it, x): x [..., T, C] in the layout of ``solve`` / ``predict`` / ``pursuit``, it the largest support any
+    signal reached.  NumPy in -> NumPy out; torch GPU tensors stay on the device.  The dense operator and its Gram
+    matrix are never formed: the Gram entries are read from the lag correlations of the templates
+    (``dcp_tm_omp_*``, decomp_amd/csrc/template_omp.hpp).
+    """
+    from . import omp
+    kind, stride, T, S, N, C = _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding)
+    tol_c = omp.check_tol(tol)
+    dt = _arrays.np_dtype(y)
+    most = min(T * C, omp.sparsity_cap(dt))
+    if n_nonzero_coefs is None:
+        n_steps = most
+    elif not _is_int(n_nonzero_coefs) or not 1 <= int(n_nonzero_coefs) <= most:
+        raise ValueError('n_nonzero_coefs must be an integer in [1, min(T C = {0:d}, {1:d})] (the cap is {2:d} for '
+                         'real and {3:d} for complex dtypes). Given {4!r}'.format(
+                             T * C, omp.sparsity_cap(dt), omp.CAP_REAL, omp.CAP_COMPLEX, n_nonzero_coefs))
+    else:
+        n_steps = int(n_nonzero_coefs)
+    return _pursuit_call('omp', kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c)
+
+
+def _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding):
+    """The argument checks the greedy coders share, before any GPU call: (kind, stride, T, S, N, C)."""
     kind = get_array_module(y, D)
     assertion.assert_dtypes(y=y, D=D)
     assertion.assert_ndim('D', D, ndim=2)
@@ -236,20 +293,11 @@ def pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME', posi
         raise ValueError('templates [{0:d}, {1:d}] need 1 <= T and 1 <= S <= N = {2:d}'.format(T, S, N))
     if n_nonzero_coefs is None and tol is None:
         raise ValueError('Either n_nonzero_coefs or tol must be given.')
-    C = _coef_size(S, N, stride=stride, padding=padding)
-    tol_c = omp.check_tol(tol)
-    if n_nonzero_coefs is None:
-        n_steps = T * C
-    elif not _is_int(n_nonzero_coefs) or not 1 <= int(n_nonzero_coefs) <= T * C:
-        raise ValueError('n_nonzero_coefs must be an integer in [1, T C = {0:d}]. Given {1!r}'.format(
-            T * C, n_nonzero_coefs))
-    else:
-        n_steps = int(n_nonzero_coefs)
-    if not isinstance(positive, (bool, np.bool_)):
-        raise ValueError('positive must be a bool. Given {0!r}'.format(positive))
-    if positive and _arrays.np_dtype(y).kind == 'c':
-        raise ValueError('positive=True needs a real dtype.')
+    return kind, stride, T, S, N, _coef_size(S, N, stride=stride, padding=padding)
 
+
+def _pursuit_call(name, kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c, *flags):
+    """dcp_tm_<name>_* on the signals of y, flattened to [B, N]: (it, x [..., T, C])."""
     import torch
     yd = _arrays.to_device(y)
     Dd = _arrays.to_device(D, yd.device.index).contiguous()
@@ -260,8 +308,7 @@ def pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME', posi
     it = ctypes.c_int(0)
     if B > 0:
         xd = torch.empty((B, T, C), dtype=yd.dtype, device=yd.device)
-        _call(y2, 'pursuit', y2, Dd, xd, B, T, S, N, stride, _pad_code(padding), n_steps, tol_c,
-              1 if positive else 0, ctypes.byref(it))
+        _call(y2, name, y2, Dd, xd, B, T, S, N, stride, _pad_code(padding), n_steps, tol_c, *(flags + (ctypes.byref(it),)))
     else:
         xd = torch.zeros((0, T, C), dtype=yd.dtype, device=yd.device)
     return it.value, _arrays.to_caller(xd.reshape(lead + (T, C)), kind)

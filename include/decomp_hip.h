@@ -852,7 +852,16 @@ int dcp_dict_mask_step_c128(dcp_handle* h, const void* Y, const double* mask, vo
  *              alpha / rho2 to its coefficient; a signal stops once its residual energy is <= tol (tol < 0: no such
  *              stop) or no atom scores > 0.  D is used as given.  X [B, T, C] is written entirely (the caller does not
  *              zero it); *it_out = the largest number of steps a signal took.  Synchronises the stream.
- *   pursuit_lds_atoms: the largest T C for which pursuit keeps the correlations in LDS (above: global workspace). */
+ *   pursuit_lds_atoms: the largest T C for which pursuit keeps the correlations in LDS (above: global workspace).
+ *   omp:       orthogonal matching pursuit of every signal on A (decomp_amd/csrc/template_omp.hpp states the
+ *              algorithm): at most n_steps (in [1, min(T C, cap)], cap = 64 real, 32 complex) atoms per signal, each
+ *              the atom outside the support with the largest |alpha|^2 / rho2 (lowest flat index on ties), followed by
+ *              the least-squares re-fit of the signal on the support through a Cholesky factor of the support's Gram
+ *              matrix, whose entries are read from the lag correlations of the templates.  A signal stops once its
+ *              residual energy is <= tol (tol < 0: no such stop), no atom scores > 0, or the best atom is numerically
+ *              dependent on the support.  X [B, T, C] is written entirely; *it_out = the largest support a signal
+ *              reached.  Synchronises the stream.
+ *   omp_lds_atoms: the largest T C for which omp keeps the correlations in LDS (above: global workspace). */
 int dcp_tm_temp2mat_f32(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
 int dcp_tm_temp2mat_f64(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
 int dcp_tm_temp2mat_c64(dcp_handle* h, const void* D, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, void* out);
@@ -889,6 +898,14 @@ int dcp_tm_pursuit_lds_atoms_f32(void);
 int dcp_tm_pursuit_lds_atoms_f64(void);
 int dcp_tm_pursuit_lds_atoms_c64(void);
 int dcp_tm_pursuit_lds_atoms_c128(void);
+int dcp_tm_omp_f32(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int* it_out);
+int dcp_tm_omp_f64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int* it_out);
+int dcp_tm_omp_c64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int* it_out);
+int dcp_tm_omp_c128(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int* it_out);
+int dcp_tm_omp_lds_atoms_f32(void);
+int dcp_tm_omp_lds_atoms_f64(void);
+int dcp_tm_omp_lds_atoms_c64(void);
+int dcp_tm_omp_lds_atoms_c128(void);
 
 #ifdef __cplusplus
 }
