@@ -13,23 +13,18 @@
 //      z's last entry is new), L^H v = z, x_I = conj(v)
 // The coefficients are those for the caller's A (y ~ x A); the selection is invariant to the scaling of the atoms.
 //
-// eps_dep = 4096 eps (2^-11 float, 2^-40 double): the pivot of a duplicated atom is a rounding residue of
-// G_kk (1 + O(n eps)) - |w|^2, and G itself carries the rounding of an F-long MFMA sum (O(sqrt(F) eps) relative):
-// 4096 eps rejects it in every dtype with s <= 64, while an atom 1.3 degrees (float) off the span still passes.
+// eps_dep = 4096 eps (omp_eps_dep in greedy.hpp, with the reason).
 //
 // Kernel.  64-thread workgroups, one wave; the wave owns one row at a time and walks the rows grid-stride.  Every
 // branch of the greedy loop is wave-uniform (the stop decisions are formed from butterfly reductions that leave the
 // same value in all 64 lanes, and pass through readfirstlane); a workgroup is one wave, so rows that stop at different
 // steps cannot wait for each other.  No atomics except one integer max per wave for the step count; every sum has a
 // fixed order, so results are bitwise reproducible.
-//   selection   each lane takes the correlations k = lane, lane + 64, ... (increasing, strict >: ties keep the lower
-//               k), then a 6-step xor butterfly on (value, index), ties to the lower index.  alpha is not stored: a
-//               lane forms alpha_k from alpha0_k and the rows G[I_j, :] (row I_j is contiguous in k: coalesced; G is
-//               Hermitian, row I_j holds a_Ij . a_k^H as needed, no conjugate) right where it scores it.
-//   L           wave-private in LDS, lane j owns row j, row stride s | 1 elements (odd: the column walk L[lane][m] of
-//               the forward substitution hits 32 distinct banks per half-wave in every dtype).  Forward and backward
-//               substitution are n broadcast-and-FMA steps each (v_readlane of the pivot lane's value); 1 / L_jj
-//               lives in lane j's register.  LDS reads are unconditional at clamped addresses and masked afterwards.
+//   selection   each lane takes the correlations k = lane, lane + 64, ... (greedy_lane_best), then the butterfly on
+//               (value, index) of greedy.hpp.  alpha is not stored: a lane forms alpha_k from alpha0_k and the rows
+//               G[I_j, :] (row I_j is contiguous in k: coalesced; G is Hermitian, row I_j holds a_Ij . a_k^H as
+//               needed, no conjugate) right where it scores it.
+//   L           the OmpFactor of greedy.hpp in the wave's LDS (OmpCarve); z, x and 1 / L_jj live in lane j's registers.
 //   alpha0      tier 0, K <= 512 (kOmpRegK): in registers, 1 / 2 / 4 / 8 per lane, with 1 / n_k beside them
 //               tier 1, K <= 2048 (kOmpLdsK): the row's alpha0 in LDS
 //               tier 2, above: read from the global [N, K] alpha0 itself at every step (L2)
@@ -37,6 +32,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "greedy.hpp"
 #include "lasso_impl.hpp"
 
 namespace dcp {
@@ -48,31 +44,10 @@ constexpr int kOmpChunk = 4;     // correlations per lane and pass in tiers 1 an
 template <class T>
 constexpr int omp_cap() { return scalar_traits<T>::is_complex ? 32 : 64; }
 
-template <class R> DCP_HD R omp_eps_dep();
-template <> DCP_HD float  omp_eps_dep<float>()  { return 4.8828125e-4f; }              // 4096 * 2^-23 = 2^-11
-template <> DCP_HD double omp_eps_dep<double>() { return 9.094947017729282e-13; }      // 4096 * 2^-52 = 2^-40
-
-// v where keep, else +0, by a bit mask (a select of a loaded value may be sunk into a branch around the load)
-__device__ __forceinline__ float omp_keep(float v, bool keep) { return __int_as_float(__float_as_int(v) & -(int)keep); }
-__device__ __forceinline__ double omp_keep(double v, bool keep) {
-    return __longlong_as_double(__double_as_longlong(v) & -(long long)keep);
-}
-template <class R>
-__device__ __forceinline__ cx<R> omp_keep(cx<R> v, bool keep) { return cx<R>{omp_keep(v.re, keep), omp_keep(v.im, keep)}; }
-
 __device__ __forceinline__ float  omp_mag(float a)  { return fabsf(a); }
 __device__ __forceinline__ double omp_mag(double a) { return fabs(a); }
 template <class R>
 __device__ __forceinline__ R omp_mag(cx<R> a) { return sqrt(abs2(a)); }
-
-// LDS carve: L [s][s | 1], xs [s] (T), then the alpha0 row (tier 1), then sel [s] (int)
-__host__ __device__ inline int omp_ld(int s) { return s | 1; }
-template <class T>
-inline size_t omp_lds_bytes(int s, int K, int tier) {
-    size_t b = ((size_t)s * omp_ld(s) + s + (tier == 1 ? (size_t)K : 0)) * sizeof(T);
-    b = (b + 15) & ~size_t(15);
-    return b + (((size_t)s * sizeof(int) + 15) & ~size_t(15));
-}
 
 // Scores U correlations of this lane, k = kbase + 64 q + lane: alpha_k = a0[q] - sum_j xs[j] G[sel[j], k], masked out
 // where k >= K, k is in the support or n_k = 0; keeps the lane's best (bc, bk), lower k on ties.
@@ -103,16 +78,13 @@ __device__ __forceinline__ void omp_score(const T (&a0)[U], const real_t<T> (&in
         }
     }
 #pragma unroll
-    for (int q = 0; q < U; ++q) {
-        R c = omp_mag(a[q]) * inv[q];
-        const bool ok = !hit[q] && kq[q] < K && inv[q] > R(0) && c >= R(0);   // (a NaN never wins)
-        c = ok ? c : R(-1);
-        if (c > bc) { bc = c; bk = kq[q]; }
-    }
+    for (int q = 0; q < U; ++q)
+        greedy_lane_best(bc, bk, omp_mag(a[q]) * inv[q], !hit[q] && kq[q] < K && inv[q] > R(0), kq[q]);
 }
 
 // grid: any; one 64-thread workgroup walks rows blockIdx.x, blockIdx.x + gridDim.x, ...
-// TIER 0: K <= 64 NPL.  ynorm2 is read only when tol >= 0.  *it_max (zero on entry) receives the largest support size.
+// TIER 0: K <= 64 NPL; dynamic LDS OmpCarve<T>(s, TIER == 1 ? K : 0).bytes.  ynorm2 is read only when tol >= 0.
+// *it_max (zero on entry) receives the largest support size.
 template <class T, int TIER, int NPL>
 __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ alpha0, const T* __restrict__ G,
                                                         const real_t<T>* __restrict__ invn,
@@ -121,15 +93,12 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
     typedef real_t<T> R;
     extern __shared__ __attribute__((aligned(16))) unsigned char omp_lds[];
     const int lane = threadIdx.x;
-    const int ld = omp_ld(s);
-    T* L = reinterpret_cast<T*>(omp_lds);
-    T* xs = L + (size_t)s * ld;
-    T* a0s = xs + s;   // tier 1 only
-    int* sel = reinterpret_cast<int*>(omp_lds + (((((size_t)s * ld + s + (TIER == 1 ? (size_t)K : 0)) * sizeof(T)) + 15) &
-                                                 ~size_t(15)));
+    const OmpCarve<T> cv(s, TIER == 1 ? K : 0);
+    T* xs = reinterpret_cast<T*>(omp_lds + cv.xs);
+    T* a0s = reinterpret_cast<T*>(omp_lds + cv.a0s);   // tier 1 only
+    int* sel = reinterpret_cast<int*>(omp_lds + cv.sel);
+    OmpFactor<T> fac{reinterpret_cast<T*>(omp_lds), omp_ld(s), lane, lane < s ? lane : s - 1, 0};
     const bool use_tol = tol >= R(0);
-    const int lc = lane < s ? lane : s - 1;   // this lane's row / column of L, clamped into the image
-    const R eps_dep = omp_eps_dep<R>();
 
     // tier 0: 1 / n_k of this lane's atoms, once per wave
     R invr[NPL];
@@ -185,40 +154,25 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
                     omp_score<T, kOmpChunk>(a0c, invc, kb, lane, G, K, n, xs, sel, bc, bk);
                 }
             }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const R oc = lane_xor(bc, m);
-                const int ok = lane_xor(bk, m);
-                const bool take = oc > bc || (oc == bc && ok < bk);
-                bc = take ? oc : bc;
-                bk = take ? ok : bk;
-            }
+            greedy_wave_best(bc, bk);
             if (__builtin_amdgcn_readfirstlane((int)!(bc > R(0)))) break;   // nothing correlates
             const int kstar = __builtin_amdgcn_readfirstlane(bk);
             // ---- the Cholesky pivot: L w = G[I, k*] ----
             const R gkk = real_part(G[(long)kstar * K + kstar]);
             const T a0k = a0row[kstar];
-            T b = omp_keep(G[(long)my_sel * K + kstar], lane < n);
-            T w = zero_of<T>();
-            R wn2 = R(0);
-            for (int m = 0; m < n; ++m) {
-                const T wm = lane_bcast(scale(b, dinv), m);
-                wn2 += abs2(wm);
-                const T lcol = omp_keep(L[lc * ld + m], lane > m && lane < n);   // column m: odd stride, no conflict
-                b = fmsub(b, lcol, wm);
-                if (lane == m) w = wm;
-            }
+            fac.n = n;
+            R wn2;
+            const T w = fac.forward(omp_keep(G[(long)my_sel * K + kstar], lane < n), dinv, wn2);
             const R d = gkk - wn2;
-            if (__builtin_amdgcn_readfirstlane((int)!(d > eps_dep * gkk))) break;   // dependent: keep the previous x
+            if (__builtin_amdgcn_readfirstlane((int)fac.dependent(d, gkk))) break;   // keep the previous x
             // ---- accept: row n of L, z_n, then L^H v = z ----
             const R ldiag = sqrt(d), rdiag = R(1) / ldiag;
+            const T wc = omp_keep(conj_of(w), lane < n);
             {
-                const T wc = conj_of(w);
                 const T zn_part = wave_sum_all(omp_keep(mul(wc, z), lane < n));   // sum_{m<n} L[n][m] z_m
                 const T zn = scale(sub(conj_of(a0k), zn_part), rdiag);
-                if (lane < n) L[n * ld + lane] = wc;
+                fac.accept(wc, ldiag);
                 if (lane == n) {
-                    L[n * ld + n] = from_real<T>(ldiag);
                     sel[n] = kstar;
                     my_sel = kstar;
                     a0sel = a0k;
@@ -227,15 +181,7 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
                 }
             }
             __syncthreads();
-            T t = omp_keep(z, lane <= n);
-            T v = zero_of<T>();
-            for (int m = n; m >= 0; --m) {
-                const T vm = lane_bcast(scale(t, dinv), m);
-                const T lrow = omp_keep(L[m * ld + lc], lane < m);   // row m: contiguous
-                t = fmsub(t, conj_of(lrow), vm);
-                if (lane == m) v = vm;
-            }
-            x = conj_of(v);
+            x = conj_of(fac.backward(z, dinv, wc));
             if (lane <= n) xs[lane] = x;   // (the scoring loop's reads of xs lie before the barrier above)
             ++n;
             __syncthreads();
@@ -243,16 +189,7 @@ __global__ void __launch_bounds__(64) omp_greedy_kernel(const T* __restrict__ al
         }
 
         // ---- the row of X, zeros off the support ----
-        T* xrow = X + row * K;
-        for (int k = lane; k < K; k += 64) {
-            T val = zero_of<T>();
-            for (int j = 0; j < n; ++j) {
-                const bool here = sel[j] == k;
-                const T xj = xs[j];
-                val = here ? xj : val;
-            }
-            xrow[k] = val;
-        }
+        omp_scatter_row(sel, xs, n, X + row * K, K, lane);
         wave_max = n > wave_max ? n : wave_max;
         __syncthreads();   // the next row's writes to xs / sel after this row's reads
     }
@@ -288,7 +225,7 @@ template <class T, int TIER, int NPL>
 inline hipError_t launch_omp_cfg(hipStream_t st, const T* alpha0, const T* G, const real_t<T>* invn,
                                  const real_t<T>* ynorm2, T* X, int N, int K, int s, real_t<T> tol, int* it_dev) {
     const int grid = N < 8192 ? N : 8192;
-    hipLaunchKernelGGL((omp_greedy_kernel<T, TIER, NPL>), dim3(grid), dim3(64), omp_lds_bytes<T>(s, K, TIER), st,
+    hipLaunchKernelGGL((omp_greedy_kernel<T, TIER, NPL>), dim3(grid), dim3(64), OmpCarve<T>(s, TIER == 1 ? K : 0).bytes, st,
                        alpha0, G, invn, ynorm2, X, N, K, s, tol, it_dev);
     return hipGetLastError();
 }
@@ -327,9 +264,11 @@ inline void omp_layout(WsLayout& a, LassoWs<T>& w, int64_t N, int64_t F, int64_t
     if (scalar_traits<T>::is_complex) a.take(w.ext1, (size_t)4 * K * F);
 }
 
-inline int omp_check_sparsity(dcp_handle* h, int64_t K, int n_nonzero, int cap) {
+// `what` is the refused parameter with its entry's family, `size` the name of the number of atoms, in the message
+inline int omp_check_sparsity(dcp_handle* h, int64_t K, int64_t n_nonzero, int cap, const char* what = "omp: n_nonzero",
+                              const char* size = "K") {
     if (n_nonzero < 1 || n_nonzero > cap || n_nonzero > K)
-        return fail(h, DCP_ERR_INVALID, "omp: n_nonzero must be in [1, min(K, " + std::to_string(cap) +
+        return fail(h, DCP_ERR_INVALID, std::string(what) + " must be in [1, min(" + size + ", " + std::to_string(cap) +
                                             ")] (the cap is 64 for real and 32 for complex dtypes)");
     return DCP_OK;
 }

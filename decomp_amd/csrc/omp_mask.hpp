@@ -23,11 +23,11 @@
 // without a host round trip:
 //   a. alpha [Nc, K] = Rm A^H on the GEMM cores (step 2's correlations: 2 Nc K F flops, where the flops are)
 //   b. omp_mask_step_kernel: 64-thread workgroups, a wave owns a row.  It loads the row's state from the workspace
-//      (a finished row leaves by a wave-uniform branch), scores alpha / sqrt(W) as omp.hpp does (lane-strided,
-//      strict >, butterfly on (value, index)), forms the n + 1 weighted dot products of step 3 from the atom rows
-//      and the row of M (lanes stride f: contiguous loads; A stays in L2; four atoms share one pass over m o conj(a_k*)),
-//      runs omp.hpp's substitutions on the factor (copied to LDS: lane j owns row j, row stride s | 1), appends the
-//      factor's new row to the workspace, rebuilds r from y and writes m o r and sum m |r|^2.
+//      (a finished row leaves by a wave-uniform branch), scores alpha / sqrt(W) as omp.hpp does (greedy_lane_best,
+//      greedy_wave_best), forms the n + 1 weighted dot products of step 3 from the atom rows and the row of M (lanes
+//      stride f: contiguous loads; A stays in L2; four atoms share one pass over m o conj(a_k*)), runs the
+//      substitutions of greedy.hpp's OmpFactor on the factor (copied to LDS), appends the factor's new row to the
+//      workspace, rebuilds r from y and writes m o r and sum m |r|^2.
 // After the last step omp_mask_finish_kernel writes the rows of X (zeros off the support) and the step count.
 // Every sum has a fixed order (per lane in increasing f, then the xor butterfly); the only atomic is one integer
 // max per row for the step count.  Bitwise reproducible.
@@ -102,14 +102,6 @@ inline void omp_mask_layout(WsLayout& a, OmpMaskWs<T>& w, int64_t Nc, int64_t F,
     if (scalar_traits<T>::is_complex) a.take(w.ext1, (size_t)4 * K * F);
 }
 
-// LDS of the step kernel: L [s][s | 1], xs [s] (T), then sel [s] (int)
-template <class T>
-inline size_t omp_mask_lds_bytes(int s) {
-    size_t b = ((size_t)s * omp_ld(s) + s) * sizeof(T);
-    b = (b + 15) & ~size_t(15);
-    return b + (((size_t)s * sizeof(int) + 15) & ~size_t(15));
-}
-
 // out = |a|^2 elementwise; clears *it_zero
 template <class T>
 __global__ void __launch_bounds__(256) omp_mask_abs2_kernel(const T* __restrict__ a, long n, real_t<T>* __restrict__ out,
@@ -152,7 +144,7 @@ __global__ void __launch_bounds__(64) omp_mask_init_kernel(const T* __restrict__
 }
 
 // One greedy step of every unfinished row of a pass (steps 1 .. 5 of the header; alpha holds this step's product).
-// grid: Nc workgroups of 64 threads.  tol < 0: no residual stop.
+// grid: Nc workgroups of 64 threads; dynamic LDS OmpCarve<T>(s).bytes.  tol < 0: no residual stop.
 template <class T>
 __global__ void __launch_bounds__(64) omp_mask_step_kernel(const T* __restrict__ Y, const real_t<T>* __restrict__ M,
                                                            const T* __restrict__ A, const T* __restrict__ alpha,
@@ -165,10 +157,11 @@ __global__ void __launch_bounds__(64) omp_mask_step_kernel(const T* __restrict__
     extern __shared__ __attribute__((aligned(16))) unsigned char omp_mask_lds[];
     const int lane = threadIdx.x;
     const long row = blockIdx.x;
+    const OmpCarve<T> cv(s);
     const int ld = omp_ld(s);
     T* L = reinterpret_cast<T*>(omp_mask_lds);
-    T* xs = L + (size_t)s * ld;
-    int* sel = reinterpret_cast<int*>(omp_mask_lds + (((((size_t)s * ld + s) * sizeof(T)) + 15) & ~size_t(15)));
+    T* xs = reinterpret_cast<T*>(omp_mask_lds + cv.xs);
+    int* sel = reinterpret_cast<int*>(omp_mask_lds + cv.sel);
 
     const int st = __builtin_amdgcn_readfirstlane(stat[row]);
     int n = st & (kOmpMaskDone - 1);
@@ -181,7 +174,6 @@ __global__ void __launch_bounds__(64) omp_mask_step_kernel(const T* __restrict__
         }
     }
     const int lc = lane < s ? lane : s - 1;   // this lane's row / column of L, clamped into the image
-    const R eps_dep = omp_eps_dep<R>();
     const T* yrow = Y + row * F;
     const R* mrow = M + row * F;
     const T* arow = alpha + row * K;
@@ -221,20 +213,10 @@ __global__ void __launch_bounds__(64) omp_mask_step_kernel(const T* __restrict__
 #pragma unroll
         for (int q = 0; q < kOmpChunk; ++q) {
             const R inv = wv[q] > R(0) ? R(1) / sqrt(wv[q]) : R(0);
-            R c = omp_mag(a[q]) * inv;
-            const bool ok = !hit[q] && kq[q] < K && inv > R(0) && c >= R(0);   // (a NaN never wins)
-            c = ok ? c : R(-1);
-            if (c > bc) { bc = c; bk = kq[q]; }
+            greedy_lane_best(bc, bk, omp_mag(a[q]) * inv, !hit[q] && kq[q] < K && inv > R(0), kq[q]);
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const R oc = lane_xor(bc, m);
-        const int ok = lane_xor(bk, m);
-        const bool take = oc > bc || (oc == bc && ok < bk);
-        bc = take ? oc : bc;
-        bk = take ? ok : bk;
-    }
+    greedy_wave_best(bc, bk);
     if (__builtin_amdgcn_readfirstlane((int)!(bc > R(0)))) {   // nothing correlates
         if (lane == 0) stat[row] = n | kOmpMaskDone;
         return;
@@ -271,31 +253,22 @@ __global__ void __launch_bounds__(64) omp_mask_step_kernel(const T* __restrict__
     }
 
     // ---- the Cholesky pivot: L w = g ----
-    T w = zero_of<T>();
-    R wn2 = R(0);
-    for (int m = 0; m < n; ++m) {
-        const T wm = lane_bcast(scale(b, dinv), m);
-        wn2 += abs2(wm);
-        const T lcol = omp_keep(L[lc * ld + m], lane > m && lane < n);   // column m: odd stride, no conflict
-        b = fmsub(b, lcol, wm);
-        if (lane == m) w = wm;
-    }
+    const OmpFactor<T> fac{L, ld, lane, lc, n};
+    R wn2;
+    const T w = fac.forward(b, dinv, wn2);
     const R d = gkk - wn2;
-    if (__builtin_amdgcn_readfirstlane((int)!(d > eps_dep * gkk))) {   // dependent: keep the previous x
+    if (__builtin_amdgcn_readfirstlane((int)fac.dependent(d, gkk))) {   // keep the previous x
         if (lane == 0) stat[row] = n | kOmpMaskDone;
         return;
     }
     // ---- accept: row n of L, z_n, then L^H v = z ----
     const R ldiag = sqrt(d), rdiag = R(1) / ldiag;
+    const T wc = omp_keep(conj_of(w), lane < n);
     {
-        const T wc = conj_of(w);
         const T zn = scale(conj_of(alk), rdiag);
-        if (lane < n) {
-            L[n * ld + lane] = wc;
-            lrow_g[omp_mask_tri(n) + lane] = wc;
-        }
+        fac.accept(wc, ldiag);
+        if (lane < n) lrow_g[omp_mask_tri(n) + lane] = wc;
         if (lane == n) {
-            L[n * ld + n] = from_real<T>(ldiag);
             lrow_g[omp_mask_tri(n) + n] = from_real<T>(ldiag);
             sel[n] = kstar;
             selg[row * s + n] = kstar;
@@ -305,15 +278,7 @@ __global__ void __launch_bounds__(64) omp_mask_step_kernel(const T* __restrict__
         }
     }
     __syncthreads();
-    T t = omp_keep(z, lane <= n);
-    T v = zero_of<T>();
-    for (int m = n; m >= 0; --m) {
-        const T vm = lane_bcast(scale(t, dinv), m);
-        const T lrow = omp_keep(L[m * ld + lc], lane < m);   // row m: contiguous
-        t = fmsub(t, conj_of(lrow), vm);
-        if (lane == m) v = vm;
-    }
-    const T x = conj_of(v);
+    const T x = conj_of(fac.backward(z, dinv, wc));
     if (lane <= n) {
         xs[lane] = x;
         xg[row * s + lane] = x;
@@ -364,18 +329,7 @@ __global__ void __launch_bounds__(64) omp_mask_finish_kernel(const T* __restrict
     const int lane = threadIdx.x;
     const long row = blockIdx.x;
     const int n = __builtin_amdgcn_readfirstlane(stat[row]) & (kOmpMaskDone - 1);
-    const T* xr = xg + row * s;
-    const int* sr = selg + row * s;
-    T* xrow = X + row * K;
-    for (int k = lane; k < K; k += 64) {
-        T val = zero_of<T>();
-        for (int j = 0; j < n; ++j) {
-            const bool here = sr[j] == k;
-            const T xj = xr[j];
-            val = here ? xj : val;
-        }
-        xrow[k] = val;
-    }
+    omp_scatter_row(selg + row * s, xg + row * s, n, X + row * K, K, lane);
     if (lane == 0 && n > 0) atomicMax(it_max, n);
 }
 
@@ -417,7 +371,7 @@ inline int omp_mask_solve(dcp_handle* h, const T* Y, const real_t<T>* M, const T
                 ext_ready = true;
             }
             ProfScope ps(h, DCP_PROF_XUPDATE);
-            hipLaunchKernelGGL((omp_mask_step_kernel<T>), dim3(nc), dim3(64), omp_mask_lds_bytes<T>(s), st, Yp, Mp, A,
+            hipLaunchKernelGGL((omp_mask_step_kernel<T>), dim3(nc), dim3(64), OmpCarve<T>(s).bytes, st, Yp, Mp, A,
                                (const T*)w.alpha, (const R*)w.W, w.Rm, w.L, w.z, w.x, w.sel, w.stat, w.r2, F, K, s, t);
             DCP_LAUNCH_OK(h, hipGetLastError());
         }

@@ -1,6 +1,7 @@
 // Orthogonal convolutional pursuit on the template operator (template_matching.orthogonal_pursuit, dcp_tm_omp_*):
 // batch OMP (Rubinstein, Zibulevsky & Elad 2008) on the shift-invariant dictionary.  Included from template_impl.hpp
-// after template_pursuit.hpp, whose prepare kernels, segment table and comparison it uses.
+// after template_pursuit.hpp, whose prepare kernels, segment table, table reduction, window, Gram entry and launch
+// it uses; the factor is greedy.hpp's OmpFactor.
 //
 // Per signal y [N], independent of the others, with A[(t, c), n] = D[t, n - s c + Q], rho2[t, c] = |A_(t,c)|^2 and
 // G[i, k] = A_i . A_k^H over the samples inside [0, N), alpha0 = y A^H, support I = (), x = 0, E = |y|^2, at most
@@ -15,7 +16,7 @@
 // r is never formed.  alpha is kept up to date in Gram form: alpha -= sum_j (x_j - x_j^previous) G[I_j, :], every term
 // touching only the T (2 dh + 1) atoms within dh of I_j.  G[i, k] is one read of the lag correlations
 // Corr[t_i, t_k, s (c_i - c_k)] when every tap of atom i lies inside the signal, else the explicit sum over the overlap
-// inside [0, N) (the `inside` rule of tm_pursuit_kernel); it is an exact zero when |c_i - c_k| > dh.
+// inside [0, N) (tm_pursuit_gram); it is an exact zero when |c_i - c_k| > dh.
 //
 // A support atom that no chain of overlaps connects to k* keeps its coefficient bit for bit: its entry of w is an
 // exact zero (its G entry is, and so is every factor entry that couples it to the cluster of k*), so row n of L holds
@@ -27,9 +28,8 @@
 // waiting between workgroups, no float atomics (one integer max per signal for `it`), every loop bounded by n_steps.
 //   arg-max     the 64-atom segment table of template_pursuit.hpp; support atoms score -1 (one bit per atom, a
 //               64-bit word per segment, set when the atom is taken).  Ties go to the lower index at every level.
-//   factor      wave 0, lane j owning row j as in omp.hpp: L [n][n | 1] in LDS (odd row stride), sel, alpha0_I, z,
-//               x_I, the previous x_I and 1 / L_jj in LDS beside it, lane j reading and writing entry j alone.  The
-//               new row is used from registers in the step that forms it, so L is read only across a barrier.
+//   factor      wave 0 on greedy.hpp's OmpFactor: L [n][n | 1] in LDS, sel, alpha0_I, z, x_I, the previous x_I and
+//               1 / L_jj in LDS beside it, lane j reading and writing entry j alone.
 //   alpha       for j = 0 .. n - 1 in order, skipping x_j == x_j^previous (never the new atom): entry (t', c') of
 //               window j belongs to thread (t' mod TPB) W + (c' mod W), W the power of two >= 2 dh + 1 (at most
 //               1024), TPB = 1024 / W -- a function of the entry alone, so an entry that several windows cover is
@@ -90,48 +90,15 @@ __device__ __forceinline__ bool tm_omp_is_zero(T v) {
     else return v == T(0);
 }
 
-// G[(t, c), (tp, cp)] = A_(t,c) . A_(tp,cp)^H over the samples inside [0, N): Corr when atom (t, c) lies inside the
-// signal, else the explicit sum; an exact zero when the atoms do not overlap
-template <class T>
-__device__ __forceinline__ T tm_omp_gram(const T* __restrict__ D, const T* __restrict__ corr, const TmGeom& g, int t,
-                                         int c, int tp, int cp) {
-    const long m = g.s * ((long)c - cp);   // sum_k D[t, k] conj(D[tp, k + m])
-    if (m > g.S - 1 || m < -(g.S - 1)) return zero_of<T>();
-    const long bj = g.s * c - g.Q;         // first sample of the taps of atom (t, c)
-    if (bj >= 0 && bj + g.S - 1 <= g.N - 1) return corr[((long)t * g.T + tp) * (2 * g.S - 1) + m + g.S - 1];
-    long k0 = m < 0 ? -m : 0, k1 = m > 0 ? g.S - 1 - m : g.S - 1;
-    if (k0 < -bj) k0 = -bj;
-    if (k1 > g.N - 1 - bj) k1 = g.N - 1 - bj;
-    T G = zero_of<T>();
-    for (long k = k0; k <= k1; ++k) G = madd(G, D[t * g.S + k], conj_of(D[tp * g.S + k + m]));
-    return G;
-}
-
-// tab[seg] <- the best atom of flat indices [64 seg, 64 seg + 64) & [0, K) outside the support (bit i % 64 of
-// taken[i / 64]); the whole wave calls it
-template <class T>
-__device__ __forceinline__ void tm_omp_segment(const T* al, const real_t<T>* __restrict__ rho2, int K, int seg,
-                                               const unsigned long long* taken, TmBest<T>* tab) {
-    typedef real_t<T> R;
-    const int lane = threadIdx.x & 63;
-    const int i = seg * kTmPursuitSeg + lane;
-    const int ic = i < K ? i : K - 1;
-    const T a = al[ic];
-    const R r2 = rho2[ic];
-    const bool out = i >= K || ((taken[seg] >> lane) & 1ull) != 0;
-    R sc = tm_pursuit_score(a, r2, 0);
-    if (out) sc = R(-1);
-    int bi = i;
-    tm_pursuit_wave_best(sc, bi);
-    const int wl = bi - seg * kTmPursuitSeg;   // the winner's lane
-    const T wa = lane_get(a, wl);
-    const R wr = lane_get(r2, wl);
-    if (lane == 0) tab[seg] = TmBest<T>{wa, sc, wr, bi};
+// lane l of the wave: atom 64 seg + l is in the support (bit i % 64 of taken[i / 64])
+__device__ __forceinline__ bool tm_omp_taken(const unsigned long long* taken, int seg) {
+    return ((taken[seg] >> (threadIdx.x & 63)) & 1ull) != 0;
 }
 
 // grid: B workgroups of kTmPursuitThreads threads; dynamic LDS TmOmpCarve<T>(n_max, K, LDS).bytes.  alpha0 [B, K]
 // (K = T C < 2^31) is read only; ws_al [B, K], ws_tab [B, nseg] and ws_taken [B, nseg] are alpha, the table and the
-// support bits of the global tier (unused in the LDS tier).  X [B, K] is written entirely.  *it_max (zero on entry) receives the largest support.
+// support bits of the global tier (unused in the LDS tier).  X [B, K] is written entirely.  *it_max (zero on entry)
+// receives the largest support.
 template <class T, bool LDS>
 __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __restrict__ Y, const T* __restrict__ D,
                                                                    const T* __restrict__ corr,
@@ -153,7 +120,6 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
     const int C = (int)g.C, Tn = (int)g.T, K = Tn * C, nseg = (K + kTmPursuitSeg - 1) / kTmPursuitSeg;
     const int nd = (int)g.nd();
     const TmOmpCarve<T> cv(n_max, K, LDS);
-    const int ld = omp_ld(n_max);
     T* L = reinterpret_cast<T*>(tm_smem);
     T* a0s = reinterpret_cast<T*>(tm_smem + cv.a0s);
     T* zs = reinterpret_cast<T*>(tm_smem + cv.z);
@@ -180,17 +146,9 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
     for (int i = tid; i < nseg; i += NT) taken[i] = 0ull;
     T* x = X + b * K;
     for (int i = tid; i < K; i += NT) x[i] = zero_of<T>();
-    R yn2;
-    {   // |y|^2, a fixed-order sum
-        R acc = 0;
-        for (long n = tid; n < g.N; n += NT) acc += abs2(Y[b * g.N + n]);
-        const R tot = block_sum_256<NW>(acc, shS);
-        if (tid == 0) shE = tot;
-        __syncthreads();
-        yn2 = shE;
-    }
+    const R yn2 = tm_pursuit_ynorm2(Y + b * g.N, g.N, shS, &shE);
     int n = 0;   // the support size
-    for (int seg = wave; seg < nseg; seg += NW) tm_omp_segment(al, rho2, K, seg, taken, tab);
+    for (int seg = wave; seg < nseg; seg += NW) tm_pursuit_segment(al, rho2, K, seg, 0, tm_omp_taken(taken, seg), tab);
     __syncthreads();
     // entry (t', c') of any window belongs to thread (t' mod TPB) W + (c' mod W), W = the power of two >= nd (<= NT)
     int W = 1;
@@ -201,25 +159,13 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
     const int wq0 = wave / nsp, wp0 = wave - wq0 * nsp, dq = NW / nsp, dr = NW - dq * nsp;
 
     const bool use_tol = tol >= R(0);
-    const R eps_dep = omp_eps_dep<R>();
     const int lc = lane < n_max ? lane : n_max - 1;   // this lane's row of the factor, clamped into the image
     R E = yn2;
     for (int it = 0; it < n_max; ++it) {
         if (use_tol && !(E > tol)) break;
-        // ---- the table's best atom ----
-        R bs = R(-1);
-        int bi = 0x7fffffff;
-        for (int j = tid; j < nseg; j += NT) tm_pursuit_better(bs, bi, tab[j].s, tab[j].i);
-        tm_pursuit_wave_best(bs, bi);
-        if (lane == 0) {
-            shS[wave] = bs;
-            shI[wave] = bi;
-        }
-        __syncthreads();
-        bs = shS[0];
-        bi = shI[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) tm_pursuit_better(bs, bi, shS[w], shI[w]);
+        R bs;
+        int bi;
+        tm_pursuit_table_best(tab, nseg, shS, shI, bs, bi);
         if (!(bs > R(0))) break;
         // ---- wave 0: the Cholesky pivot L w = G[I, k*], then the re-fit ----
         if (wave == 0) {
@@ -227,42 +173,21 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
             const R gkk = rho2[bi];
             const T a0k = a0row[bi];
             const int tj = lane < n ? selt[lc] : ts, cj = lane < n ? selc[lc] : cs;
-            T bb = omp_keep(tm_omp_gram(D, corr, g, tj, cj, ts, cs), lane < n);
+            const T bb = omp_keep(tm_pursuit_gram(D, corr, g, tj, cj, tm_pursuit_inside(g, cj), ts, cs), lane < n);
             const R dv = omp_keep(dinv[lc], lane < n);
-            T w = zero_of<T>();
-            R wn2 = R(0);
-            for (int m = 0; m < n; ++m) {
-                const T wm = lane_bcast(scale(bb, dv), m);
-                wn2 += abs2(wm);
-                const T lcol = omp_keep(L[lc * ld + m], lane > m && lane < n);   // column m: odd stride, no conflict
-                bb = fmsub(bb, lcol, wm);
-                if (lane == m) w = wm;
-            }
+            const OmpFactor<T> fac{L, omp_ld(n_max), lane, lc, n};
+            R wn2;
+            const T w = fac.forward(bb, dv, wn2);
             const R d = gkk - wn2;
-            if (!(d > eps_dep * gkk)) {   // dependent: keep the previous x
+            if (fac.dependent(d, gkk)) {   // keep the previous x
                 if (lane == 0) shGo = 0;
             } else {
                 const R ldiag = sqrt(d), rdiag = R(1) / ldiag;
                 const T wc = omp_keep(conj_of(w), lane < n);   // row n of L, left of the diagonal
                 const T zj = omp_keep(zs[lc], lane < n);
                 const T zn = scale(sub(conj_of(a0k), wave_sum_all(mul(wc, zj))), rdiag);
-                if (lane < n) L[n * ld + lane] = wc;
-                // L^H v = z, row n from registers
-                T t = lane == n ? zn : zj;
-                const R dl = lane == n ? rdiag : dv;
-                T v = zero_of<T>();
-                {
-                    const T vm = lane_bcast(scale(t, dl), n);
-                    t = fmsub(t, conj_of(wc), vm);
-                    if (lane == n) v = vm;
-                }
-                for (int m = n - 1; m >= 0; --m) {
-                    const T vm = lane_bcast(scale(t, dl), m);
-                    const T lrow = omp_keep(L[m * ld + lc], lane < m);   // row m: contiguous
-                    t = fmsub(t, conj_of(lrow), vm);
-                    if (lane == m) v = vm;
-                }
-                const T xn = conj_of(v);
+                fac.accept(wc, ldiag);
+                const T xn = conj_of(fac.backward(lane == n ? zn : zj, lane == n ? rdiag : dv, wc));
                 const T xo = omp_keep(xs[lc], lane < n);
                 const T a0m = lane == n ? a0k : omp_keep(a0s[lc], lane < n);
                 if (lane <= n) {
@@ -270,7 +195,6 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
                     xs[lane] = xn;
                 }
                 if (lane == n) {
-                    L[n * ld + n] = from_real<T>(ldiag);
                     sel[n] = bi;
                     selt[n] = ts;
                     selc[n] = cs;
@@ -303,14 +227,14 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
                         const int j = j0 + u < n ? j0 + u : n - 1;
                         const T dx = sub(xs[j], xp[j]);
                         const int tj = selt[j], cj = selc[j];
-                        const int ca = cj - g.dh > 0 ? (int)(cj - g.dh) : 0;
-                        const int cb = cj + g.dh < C - 1 ? (int)(cj + g.dh) : C - 1;
+                        int ca, cb;
+                        tm_pursuit_window(g, cj, ca, cb);
                         const int cp = ca + cw + ((r - ca) & (W - 1));   // the c' >= ca + cw with c' = r (mod W)
                         const bool on = j0 + u < n && (j == n - 1 || !tm_omp_is_zero(dx)) && cp <= cb;
                         iu[u] = on ? tp * C + cp : -1;
                         dxu[u] = dx;
                         Gu[u] = zero_of<T>();
-                        if (on) Gu[u] = tm_omp_gram(D, corr, g, tj, cj, tp, cp);
+                        if (on) Gu[u] = tm_pursuit_gram(D, corr, g, tj, cj, tm_pursuit_inside(g, cj), tp, cp);
                     }
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
@@ -325,14 +249,13 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
         // ---- reduce the marked segments again: template t' of window j wrote [t' C + ca, t' C + cb] ----
         for (int j = 0; j < n; ++j) {
             if (j != n - 1 && tm_omp_is_zero(sub(xs[j], xp[j]))) continue;
-            const int cj = selc[j];
-            const int ca = cj - g.dh > 0 ? (int)(cj - g.dh) : 0;
-            const int cb = cj + g.dh < C - 1 ? (int)(cj + g.dh) : C - 1;
+            int ca, cb;
+            tm_pursuit_window(g, selc[j], ca, cb);
             int tq = wq0, p = wp0;
             while (tq < Tn) {
                 const int seg = (tq * C + ca) / kTmPursuitSeg + p;
                 if (seg <= (tq * C + cb) / kTmPursuitSeg && __builtin_amdgcn_readfirstlane(tab[seg].i) == -1)
-                    tm_omp_segment(al, rho2, K, seg, taken, tab);
+                    tm_pursuit_segment(al, rho2, K, seg, 0, tm_omp_taken(taken, seg), tab);
                 tq += dq;
                 p += dr;
                 if (p >= nsp) {
@@ -374,24 +297,9 @@ inline int tm_omp_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeo
     DCP_TRY(tm_pursuit_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev));
     const R t = tol >= 0.0 ? (R)tol : R(-1);
     const size_t bytes = TmOmpCarve<T>(n_steps, K, lds).bytes;
-    if (lds) {
-        if (bytes > 65536) {
-            static DynLdsRaised raised;   // per instantiation
-            std::atomic<bool>& done = raised.on_current_device();
-            if (!done) {
-                const int most = (int)TmOmpCarve<T>(omp_cap<T>(), tm_omp_lds_atoms<T>(), true).bytes;
-                DCP_LAUNCH_OK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&tm_omp_kernel<T, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, most));
-                done = true;
-            }
-        }
-        hipLaunchKernelGGL((tm_omp_kernel<T, true>), dim3(g.B), dim3(kTmPursuitThreads), bytes, st, Y, D,
-                           (const T*)corr, (const R*)rho2, (const T*)alpha0, al, tab, taken, X, g, n_steps, t, it_dev);
-    } else {
-        hipLaunchKernelGGL((tm_omp_kernel<T, false>), dim3(g.B), dim3(kTmPursuitThreads), bytes, st, Y, D,
-                           (const T*)corr, (const R*)rho2, (const T*)alpha0, al, tab, taken, X, g, n_steps, t, it_dev);
-    }
-    DCP_LAUNCH_OK(h, hipGetLastError());
+    DCP_LAUNCH_OK(h, (tm_pursuit_launch<&tm_omp_kernel<T, true>, &tm_omp_kernel<T, false>>(
+                         st, g.B, lds, bytes, TmOmpCarve<T>(omp_cap<T>(), tm_omp_lds_atoms<T>(), true).bytes, Y, D,
+                         (const T*)corr, (const R*)rho2, (const T*)alpha0, al, tab, taken, X, g, n_steps, t, it_dev)));
     return read_scalar(h, (const int*)it_dev, it_out);
 }
 
@@ -401,10 +309,7 @@ inline int tm_omp_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom&
     if (!Y || !D || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
     const int64_t K = (int64_t)g.T * g.C;
     if (K > 0x7fffff00LL) return fail(h, DCP_ERR_INVALID, "orthogonal pursuit: T C exceeds 2^31 - 257");
-    const int cap = omp_cap<T>();
-    if (n_steps < 1 || n_steps > K || n_steps > cap)
-        return fail(h, DCP_ERR_INVALID, "orthogonal pursuit: n_steps must be in [1, min(T C, " + std::to_string(cap) +
-                                            ")] (the cap is 64 for real and 32 for complex dtypes)");
+    DCP_TRY(omp_check_sparsity(h, K, n_steps, omp_cap<T>(), "orthogonal pursuit: n_steps", "T C"));
     if (tol != tol) return fail(h, DCP_ERR_INVALID, "orthogonal pursuit: tol is NaN");
     return tm_omp_solve<T>(h, Y, D, X, g, (int)n_steps, tol, it_out);
 }

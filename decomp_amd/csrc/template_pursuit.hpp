@@ -25,7 +25,7 @@
 //               the table (each thread its entries, a 6-step butterfly per wave, the 16 wave results through LDS),
 //               updates T (2 dh + 1) correlations and re-reduces only the segments those lie in: at most
 //               T (ceil(2 dh / 64) + 1).  Ties go to the lower index at every level (lane, wave, segment, table):
-//               the comparison is (score, -index) throughout.
+//               the comparison is greedy_better of greedy.hpp throughout.
 //   per step    3 workgroup barriers (table result | alpha update | segment refresh), T (2 dh + 1) multiply-adds
 //               (one per thread up to 1024), <= T (ceil(2 dh / 64) + 1) segment reductions shared by 16 waves,
 //               ceil(nseg / 1024) table entries per thread, 1 global read-modify-write of x by one thread.  The global
@@ -39,7 +39,12 @@
 //   x           written straight to global memory (zeroed by the kernel: the caller's X is written entirely).
 // Every value a signal's workgroup computes depends on that signal, D and the geometry alone, in a fixed order:
 // results are bitwise reproducible and bitwise independent of the rest of the batch.
+//
+// The pieces orthogonal pursuit (template_omp.hpp) runs on as well are defined here once: the prepare launches, the
+// segment table with its `excluded` lanes, the table's best atom, |y|^2, the window of an atom, the Gram entry and the
+// launch of a tier.
 #pragma once
+#include "greedy.hpp"
 
 namespace dcp {
 
@@ -99,30 +104,11 @@ __device__ __forceinline__ real_t<T> tm_pursuit_score(T a, real_t<T> rho2, int p
     return (ok && sc >= R(0)) ? sc : R(-1);
 }
 
-// (s, i) <- the better of (s, i) and (s2, i2): the larger score, the lower index on a tie
-template <class R>
-__device__ __forceinline__ void tm_pursuit_better(R& s, int& i, R s2, int i2) {
-    if (s2 > s || (s2 == s && i2 < i)) {
-        s = s2;
-        i = i2;
-    }
-}
-
-// the best (score, index) over the wave, the same in every lane (the order is total: a butterfly is enough)
-template <class R>
-__device__ __forceinline__ void tm_pursuit_wave_best(R& s, int& i) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const R s2 = lane_xor(s, m);
-        const int i2 = lane_xor(i, m);
-        tm_pursuit_better(s, i, s2, i2);
-    }
-}
-
-// tab[seg] <- the best atom of flat indices [64 seg, 64 seg + 64) & [0, K); the whole wave calls it
+// tab[seg] <- the best atom of flat indices [64 seg, 64 seg + 64) & [0, K) whose lane is not `excluded`; the whole wave
+// calls it
 template <class T>
 __device__ __forceinline__ void tm_pursuit_segment(const T* al, const real_t<T>* __restrict__ rho2, int K, int seg,
-                                                   int positive, TmBest<T>* tab) {
+                                                   int positive, bool excluded, TmBest<T>* tab) {
     typedef real_t<T> R;
     const int lane = threadIdx.x & 63;
     const int i = seg * kTmPursuitSeg + lane;
@@ -130,13 +116,90 @@ __device__ __forceinline__ void tm_pursuit_segment(const T* al, const real_t<T>*
     const T a = al[ic];
     const R r2 = rho2[ic];
     R sc = tm_pursuit_score(a, r2, positive);
-    if (i >= K) sc = R(-1);
+    if (i >= K || excluded) sc = R(-1);
     int bi = i;
-    tm_pursuit_wave_best(sc, bi);
+    greedy_wave_best(sc, bi);
     const int wl = bi - seg * kTmPursuitSeg;   // the winner's lane
     const T wa = lane_get(a, wl);
     const R wr = lane_get(r2, wl);
     if (lane == 0) tab[seg] = TmBest<T>{wa, sc, wr, bi};
+}
+
+// The table's best (score, index), the same in every thread: each thread its entries, the butterfly per wave, the
+// wave results through shS / shI [kTmPursuitWaves].  One workgroup barrier, inside.
+template <class T>
+__device__ __forceinline__ void tm_pursuit_table_best(const TmBest<T>* tab, int nseg, real_t<T>* shS, int* shI,
+                                                      real_t<T>& bs, int& bi) {
+    const int tid = threadIdx.x;
+    bs = real_t<T>(-1);
+    bi = 0x7fffffff;
+    for (int j = tid; j < nseg; j += kTmPursuitThreads) greedy_better(bs, bi, tab[j].s, tab[j].i);
+    greedy_wave_best(bs, bi);
+    if ((tid & 63) == 0) {
+        shS[tid >> 6] = bs;
+        shI[tid >> 6] = bi;
+    }
+    __syncthreads();
+    bs = shS[0];
+    bi = shI[0];
+#pragma unroll
+    for (int w = 1; w < kTmPursuitWaves; ++w) greedy_better(bs, bi, shS[w], shI[w]);
+}
+
+// |y|^2 in every thread, a fixed-order sum (shS [kTmPursuitWaves], *shE: LDS)
+template <class T>
+__device__ __forceinline__ real_t<T> tm_pursuit_ynorm2(const T* __restrict__ y, long N, real_t<T>* shS, real_t<T>* shE) {
+    real_t<T> acc = 0;
+    for (long n = threadIdx.x; n < N; n += kTmPursuitThreads) acc += abs2(y[n]);
+    const real_t<T> tot = block_sum_256<kTmPursuitWaves>(acc, shS);
+    if (threadIdx.x == 0) *shE = tot;
+    __syncthreads();
+    return *shE;
+}
+
+// [ca, cb]: the c' of the atoms within dh of c, the only ones an atom at c overlaps
+__device__ __forceinline__ void tm_pursuit_window(const TmGeom& g, int c, int& ca, int& cb) {
+    const int C = (int)g.C;
+    ca = c - g.dh > 0 ? (int)(c - g.dh) : 0;
+    cb = c + g.dh < C - 1 ? (int)(c + g.dh) : C - 1;
+}
+
+// every tap of an atom at c lies inside the signal
+__device__ __forceinline__ bool tm_pursuit_inside(const TmGeom& g, int c) {
+    const long bj = g.s * c - g.Q;   // first sample of its taps
+    return bj >= 0 && bj + g.S - 1 <= g.N - 1;
+}
+
+// acc + a conj(b) with the rounding of every product fixed: a * conj(b) as one rounded product and one fused
+// multiply-add per part, then the sum.  The compiler's own contraction of a complex multiply-add depends on the
+// surrounding code (which product it fuses changes the bits), and every caller of tm_pursuit_gram must form the same
+// ones.  Which product is rounded is what both kernels had before they shared this sum, kept so that their results
+// stay what they were: in the real part it is a.re b.re in c64 and a.im b.im in c128.
+DCP_HD float  tm_madd_conj(float acc, float a, float b)    { return fmaf(a, b, acc); }
+DCP_HD double tm_madd_conj(double acc, double a, double b) { return fma(a, b, acc); }
+DCP_HD c64 tm_madd_conj(c64 acc, c64 a, c64 b) {
+    return c64{acc.re + fmaf(a.im, b.im, a.re * b.re), acc.im + fmaf(a.im, b.re, -(a.re * b.im))};
+}
+DCP_HD c128 tm_madd_conj(c128 acc, c128 a, c128 b) {
+    return c128{acc.re + fma(a.re, b.re, a.im * b.im), acc.im + fma(a.im, b.re, -(a.re * b.im))};
+}
+
+// G[(t, c), (tp, cp)] = A_(t,c) . A_(tp,cp)^H over the samples inside [0, N): Corr when atom (t, c) lies inside the
+// signal (inside = tm_pursuit_inside(g, c), hoisted by the caller), else the explicit sum; an exact zero when the
+// atoms do not overlap
+template <class T>
+__device__ __forceinline__ T tm_pursuit_gram(const T* __restrict__ D, const T* __restrict__ corr, const TmGeom& g, int t,
+                                             int c, bool inside, int tp, int cp) {
+    const long m = g.s * ((long)c - cp);   // sum_k D[t, k] conj(D[tp, k + m])
+    if (m > g.S - 1 || m < -(g.S - 1)) return zero_of<T>();
+    if (inside) return corr[((long)t * g.T + tp) * (2 * g.S - 1) + m + g.S - 1];
+    const long bj = g.s * c - g.Q;
+    long k0 = m < 0 ? -m : 0, k1 = m > 0 ? g.S - 1 - m : g.S - 1;
+    if (k0 < -bj) k0 = -bj;
+    if (k1 > g.N - 1 - bj) k1 = g.N - 1 - bj;
+    T G = zero_of<T>();
+    for (long k = k0; k <= k1; ++k) G = tm_madd_conj(G, D[t * g.S + k], D[tp * g.S + k + m]);
+    return G;
 }
 
 // grid: B workgroups of kTmPursuitThreads threads.  alpha0 [B, K] (K = T C < 2^31): read, and in the global tier
@@ -155,10 +218,9 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_pursuit_kernel(const T* 
     __shared__ R shS[NW];
     __shared__ int shI[NW];
     __shared__ R shE;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, wave = tid >> 6;
     const long b = blockIdx.x;
     const int C = (int)g.C, Tn = (int)g.T, K = Tn * C, nseg = (K + kTmPursuitSeg - 1) / kTmPursuitSeg;
-    const long W = 2 * g.S - 1;
     T* al;
     TmBest<T>* tab;
     if constexpr (LDS) {
@@ -171,36 +233,17 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_pursuit_kernel(const T* 
     }
     T* x = X + b * K;
     for (int i = tid; i < K; i += NT) x[i] = zero_of<T>();
-    R E;
-    {   // |y|^2, a fixed-order sum
-        R acc = 0;
-        for (long n = tid; n < g.N; n += NT) acc += abs2(Y[b * g.N + n]);
-        const R tot = block_sum_256<NW>(acc, shS);
-        if (tid == 0) shE = tot;
-        __syncthreads();
-        E = shE;
-    }
-    for (int seg = wave; seg < nseg; seg += NW) tm_pursuit_segment(al, rho2, K, seg, positive, tab);
+    R E = tm_pursuit_ynorm2(Y + b * g.N, g.N, shS, &shE);
+    for (int seg = wave; seg < nseg; seg += NW) tm_pursuit_segment(al, rho2, K, seg, positive, false, tab);
     __syncthreads();
 
     const bool use_tol = tol >= R(0);
     int steps = 0;
     for (long it = 0; it < n_steps; ++it) {
         if (use_tol && E <= tol) break;
-        // ---- the table's best atom ----
-        R bs = R(-1);
-        int bi = 0x7fffffff;
-        for (int j = tid; j < nseg; j += NT) tm_pursuit_better(bs, bi, tab[j].s, tab[j].i);
-        tm_pursuit_wave_best(bs, bi);
-        if (lane == 0) {
-            shS[wave] = bs;
-            shI[wave] = bi;
-        }
-        __syncthreads();
-        bs = shS[0];
-        bi = shI[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) tm_pursuit_better(bs, bi, shS[w], shI[w]);
+        R bs;
+        int bi;
+        tm_pursuit_table_best(tab, nseg, shS, shI, bs, bi);
         if (!(bs > R(0))) break;
         // ---- take it (its alpha and rho2 came along in the table) ----
         const T a = div_real(tab[bi / kTmPursuitSeg].a, tab[bi / kTmPursuitSeg].r2);
@@ -208,28 +251,16 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_pursuit_kernel(const T* 
         E -= bs;
         ++steps;
         // ---- alpha -= a G over the atoms within dh of c* ----
-        const long bj = g.s * cs - g.Q;                  // first sample of the taken atom's taps
-        const bool inside = bj >= 0 && bj + g.S - 1 <= g.N - 1;
-        const int ca = cs - g.dh > 0 ? (int)(cs - g.dh) : 0;
-        const int cb = cs + g.dh < C - 1 ? (int)(cs + g.dh) : C - 1;
+        const bool inside = tm_pursuit_inside(g, cs);
+        int ca, cb;
+        tm_pursuit_window(g, cs, ca, cb);
         const int nc = cb - ca + 1, total = Tn * nc;
         const int dq = NT / nc, dr = NT - dq * nc;       // q += NT moves (t', c' - ca) by (dq, dr), with a carry
         int tp = tid / nc, off = tid - tp * nc;
         for (int q = tid; q < total; q += NT) {
             const int cp = ca + off;
-            const long m = g.s * (cs - cp);              // G = sum_k D[t*, k] conj(D[t', k + m]) over n inside
-            T G;
-            if (inside) {
-                G = corr[((long)ts * Tn + tp) * W + m + g.S - 1];
-            } else {
-                long k0 = m < 0 ? -m : 0, k1 = m > 0 ? g.S - 1 - m : g.S - 1;
-                if (k0 < -bj) k0 = -bj;
-                if (k1 > g.N - 1 - bj) k1 = g.N - 1 - bj;
-                G = zero_of<T>();
-                for (long k = k0; k <= k1; ++k) G = madd(G, D[ts * g.S + k], conj_of(D[tp * g.S + k + m]));
-            }
             const int i = tp * C + cp;
-            al[i] = fmsub(al[i], a, G);
+            al[i] = fmsub(al[i], a, tm_pursuit_gram(D, corr, g, ts, cs, inside, tp, cp));
             tp += dq;
             off += dr;
             if (off >= nc) {
@@ -246,7 +277,7 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_pursuit_kernel(const T* 
             const int f0 = (tq * C + ca) / kTmPursuitSeg, f1 = (tq * C + cb) / kTmPursuitSeg;
             // the previous template's last segment is refreshed as that template's
             const bool dup = p == 0 && tq > 0 && ((tq - 1) * C + cb) / kTmPursuitSeg == f0;
-            if (f0 + p <= f1 && !dup) tm_pursuit_segment(al, rho2, K, f0 + p, positive, tab);
+            if (f0 + p <= f1 && !dup) tm_pursuit_segment(al, rho2, K, f0 + p, positive, false, tab);
         }
         __syncthreads();
     }
@@ -280,6 +311,25 @@ inline int tm_pursuit_prepare(dcp_handle* h, const T* Y, const T* D, const TmGeo
     return DCP_OK;
 }
 
+// One workgroup per signal on the chosen tier: KernLds with `bytes` of dynamic LDS (above 64 KiB the kernel's limit is
+// raised first, once per instantiation and device, to `most`: what its largest problem asks for), else KernGlobal.
+template <auto KernLds, auto KernGlobal, class... Args>
+inline hipError_t tm_pursuit_launch(hipStream_t st, long B, bool lds, size_t bytes, size_t most, Args... args) {
+    if (lds && bytes > 65536) {
+        static DynLdsRaised raised;   // per instantiation
+        std::atomic<bool>& done = raised.on_current_device();
+        if (!done) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KernLds),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
+            if (e != hipSuccess) return e;
+            done = true;
+        }
+    }
+    if (lds) hipLaunchKernelGGL(KernLds, dim3(B), dim3(kTmPursuitThreads), bytes, st, args...);
+    else hipLaunchKernelGGL(KernGlobal, dim3(B), dim3(kTmPursuitThreads), bytes, st, args...);
+    return hipGetLastError();
+}
+
 // Y [B, N], D [T, S] -> X [B, T, C]; *it_out = the largest number of steps a signal took.  Synchronises the stream.
 template <class T>
 inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
@@ -302,25 +352,10 @@ inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const T
     }));
     DCP_TRY(tm_pursuit_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev));
     const R t = tol >= 0.0 ? (R)tol : R(-1);
-    if (lds) {
-        const size_t bytes = tm_pursuit_lds_bytes<T>(K);
-        if (bytes > 65536) {
-            static DynLdsRaised raised;   // per instantiation
-            std::atomic<bool>& done = raised.on_current_device();
-            if (!done) {
-                DCP_LAUNCH_OK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&tm_pursuit_kernel<T, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)tm_pursuit_lds_bytes<T>(tm_pursuit_lds_atoms<T>())));
-                done = true;
-            }
-        }
-        hipLaunchKernelGGL((tm_pursuit_kernel<T, true>), dim3(g.B), dim3(kTmPursuitThreads), bytes, st, Y, D,
-                           (const T*)corr, (const R*)rho2, alpha0, tab, X, g, (long)n_steps, t, positive, it_dev);
-    } else {
-        hipLaunchKernelGGL((tm_pursuit_kernel<T, false>), dim3(g.B), dim3(kTmPursuitThreads), 0, st, Y, D,
-                           (const T*)corr, (const R*)rho2, alpha0, tab, X, g, (long)n_steps, t, positive, it_dev);
-    }
-    DCP_LAUNCH_OK(h, hipGetLastError());
+    DCP_LAUNCH_OK(h, (tm_pursuit_launch<&tm_pursuit_kernel<T, true>, &tm_pursuit_kernel<T, false>>(
+                         st, g.B, lds, lds ? tm_pursuit_lds_bytes<T>(K) : 0,
+                         tm_pursuit_lds_bytes<T>(tm_pursuit_lds_atoms<T>()), Y, D, (const T*)corr, (const R*)rho2, alpha0,
+                         tab, X, g, (long)n_steps, t, positive, it_dev)));
     return read_scalar(h, (const int*)it_dev, it_out);
 }
 

@@ -115,6 +115,30 @@ def test_full_support_is_least_squares(dt):
     assert err <= bound
 
 
+@pytest.mark.parametrize('dt', DTYPES)
+def test_sparsity_at_the_cap(dt):
+    """s = 64 real / 32 complex, K = 70, F = 80, N = 67 (the problem of test_gpu_omp_mask's test of this name, without
+    the mask): the factor at its full size.  The reference takes s steps in every row; the properties only."""
+    from decomp_amd import omp
+    dt = np.dtype(dt)
+    cplx = dt.kind == 'c'
+    precision = 'single' if dt.itemsize == (8 if cplx else 4) else 'double'
+    s = 32 if cplx else 64
+    rng = np.random.RandomState(41)
+    N, F, K = 67, 80, 70
+    y, A = omp_ref.single_exact(_random(rng, cplx, N, F), _random(rng, cplx, K, F) * (0.5 + rng.rand(K, 1)))
+    an = omp_ref.Analysis(y, A, s)
+    assert np.all(an.steps == s)
+    it, x = omp.solve(y.astype(dt), A.astype(dt), n_nonzero_coefs=s)
+    nnz = np.count_nonzero(x, axis=1)
+    orth = float(omp_ref.row_metrics(x, y, A)[1].max())
+    b_orth = an.bounds(precision, np.ones(N, dtype=bool))[1]
+    print('s = %d %s: steps %s, orthogonality %.3g (bound %.3g)' % (s, dt.name, sorted(set(nnz.tolist())), orth, b_orth))
+    assert np.all(np.isfinite(x))
+    assert np.all(nnz == s) and it == s
+    assert orth <= b_orth
+
+
 # ---- the greedy kernel alone ---------------------------------------------------------------------------------
 @pytest.mark.parametrize('dt', DTYPES)
 def test_duplicate_zero_atom_and_zero_row(dt):
