@@ -2,11 +2,12 @@
 // product (fp32 MFMA, gemm_mfma_f32.hpp; fp64 MFMA, gemm_mfma_f64.hpp; generic LDS-tiled VALU,
 // gemm_generic.hpp), under which real image a complex product runs, the dimensions the core sees
 // and the tile that is launched.  gemm() launches what the route says, plan_splits() counts tiles
-// by it.  Epilogue functors (below) fuse the per-element update rules of the solvers into the GEMM
-// that produces their last operand.
+// by it.  Epilogue functors (epilogue.hpp) fuse the per-element update rules of the solvers into the
+// GEMM that produces their last operand.
 #pragma once
 #include <type_traits>
 
+#include "epilogue.hpp"
 #include "gemm_generic.hpp"
 #include "gemm_mfma_bf16x6.hpp"
 #include "gemm_mfma_f32.hpp"
@@ -670,448 +671,5 @@ inline hipError_t gemm_bf16x6(hipStream_t stream, const GemmArgs<float>& a, cons
         return hipErrorInvalidValue;
     }
 }
-
-// ------------------------------------------------------------------ epilogues ----
-// All are called as epi(row, col, acc, split).
-
-inline bool al16_ptr(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
-template <class T>
-struct EpiStore {  // C[row, col] = acc
-    // 16-byte epilogue available but OFF (interleaved in-process A/B, tools/vec_ab.py): x.D 16384x4096x256
-    // 0.326 ms with it, 0.318 without: for a pure store the quad transposes cost as much VALU issue as the
-    // narrower stores save.  It pays where the epilogue also LOADS per element (EpiMuNum: 1.045 -> 1.010 ms
-    // on the dominant kernel).
-    static constexpr bool kVec4 = false;
-    T* C;
-    long ldc;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        C[(long)r * ldc + c] = v;
-    }
-    bool vec_ok() const { return al16_ptr(C) && (ldc % 4) == 0; }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(C) + (long)r * ldc + c0) = v;
-    }
-};
-
-template <class T>
-struct EpiStoreSub {  // C[row, col] = acc - sub  (the HALS x sweep's C = Y D^T - l1 under an L1 penalty)
-    static constexpr bool kVec4 = false;
-    T* C;
-    long ldc;
-    T sub;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        C[(long)r * ldc + c] = v - sub;
-    }
-};
-
-template <class T>
-struct EpiSlab {  // split-K partial: slab[split][row, col] = acc
-    static constexpr bool kVec4 = false;   // neutral in the A/B (1.134 vs 1.130 ms on x^T.Y): off
-    T* slab;
-    long ldc;
-    long slab_stride;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int s) const {
-        slab[(long)s * slab_stride + (long)r * ldc + c] = v;
-    }
-    bool vec_ok() const { return al16_ptr(slab) && (ldc % 4) == 0 && (slab_stride % 4) == 0; }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int s) const {
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(slab) + (long)s * slab_stride + (long)r * ldc + c0) = v;
-    }
-    // pair schedule of the fp32 MFMA core (TileCfg PIPE = 3): two adjacent columns in one 8-byte store
-    static constexpr bool kVec2 = std::is_same<T, float>::value;
-    bool vec2_ok() const {
-        return (reinterpret_cast<uintptr_t>(slab) & 7) == 0 && (ldc % 2) == 0 && (slab_stride % 2) == 0;
-    }
-    __device__ __forceinline__ void store2(int r, int c0, float v0, float v1, int s) const {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<f32x2*>(reinterpret_cast<float*>(slab) + (long)s * slab_stride + (long)r * ldc + c0) =
-            f32x2{v0, v1};
-    }
-};
-
-// out = cur * max(acc, 0) / max(den, 1e-15): acc is the POSITIVE gradient part
-// (grads.py:84 with grad_pos produced by this GEMM).  den: full matrix (ld_den > 0)
-// or one value per column (ld_den == 0), e.g. KL's colsum(D).
-template <class T>
-struct EpiMuNum {
-    static constexpr bool kVec4 = std::is_same<T, float>::value;
-    const T* cur;
-    long ld_cur;
-    const T* den;
-    long ld_den;
-    T* out;
-    long ld_out;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const T d = den[(long)r * ld_den + c];
-        out[(long)r * ld_out + c] = cur[(long)r * ld_cur + c] * max_np(v, T(0)) /
-                                    max_np(d, T(1.0e-15));
-    }
-    // (ld_den == 0: one denominator per column, read as 4 consecutive values of the vector)
-    bool vec_ok() const {
-        return al16_ptr(cur) && al16_ptr(den) && al16_ptr(out) && (ld_cur % 4) == 0 && (ld_den % 4) == 0 &&
-               (ld_out % 4) == 0;
-    }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        const f32x4 d = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(den) + (long)r * ld_den + c0);
-        const f32x4 x = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(cur) + (long)r * ld_cur + c0);
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = x[e] * max_np(v[e], 0.0f) / max_np(d[e], 1.0e-15f);
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + (long)r * ld_out + c0) = o;
-    }
-};
-
-// EpiMuNum with the L1/L2 penalty on the codes: out = cur * max(acc, 0) / max(den + l1 + l2 cur, 1e-15).
-// A type of its own, so that the unpenalised instantiations stay exactly as they are; l1 / l2 are uniform
-// kernel arguments (SGPRs).
-template <class T>
-struct EpiMuNumPen : EpiMuNum<T> {
-    T l1, l2;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const T d = this->den[(long)r * this->ld_den + c];
-        const T x = this->cur[(long)r * this->ld_cur + c];
-        this->out[(long)r * this->ld_out + c] = x * max_np(v, T(0)) / max_np(d + l1 + l2 * x, T(1.0e-15));
-    }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        const f32x4 d =
-            *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(this->den) + (long)r * this->ld_den + c0);
-        const f32x4 x =
-            *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(this->cur) + (long)r * this->ld_cur + c0);
-        const float a1 = (float)l1, a2 = (float)l2;
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = x[e] * max_np(v[e], 0.0f) / max_np(d[e] + a1 + a2 * x[e], 1.0e-15f);
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(this->out) + (long)r * this->ld_out + c0) = o;
-    }
-};
-
-// EpiMuNum / EpiMuNumPen whose denominator cur . gram is formed by the product's own workgroup (the denominator
-// tail of the 256 x 256 split-bf16 NT kernel, gemm_mfma_bf16x6.hpp) and never stored:
-//   out = cur * max(acc, 0) / max(den, 1e-15),   den = (cur . gram)[r, c]  (+ l1 + l2 cur with PEN)
-// The quotient is EpiMuNum::vec4's expression, so out is bitwise what the two-kernel path gives.
-template <bool PEN>
-struct EpiMuGramDen {
-    static constexpr bool kVec4 = true;
-    static constexpr bool kDenTail = true;
-    const float* cur;
-    long ld_cur;
-    const float* gram;   // [depth, depth]
-    long ld_gram;
-    int depth;
-    float* out;
-    long ld_out;
-    float l1 = 0.0f, l2 = 0.0f;
-    bool vec_ok() const {
-        return al16_ptr(cur) && al16_ptr(gram) && al16_ptr(out) && (ld_cur % 4) == 0 && (ld_gram % 4) == 0 &&
-               (ld_out % 4) == 0;
-    }
-    __device__ __forceinline__ void quot4(int r, int c0, f32x4 v, f32x4 d) const {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(cur + (long)r * ld_cur + c0);
-        const float a1 = l1, a2 = l2;
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if constexpr (PEN) o[e] = x[e] * max_np(v[e], 0.0f) / max_np(d[e] + a1 + a2 * x[e], 1.0e-15f);
-            else o[e] = x[e] * max_np(v[e], 0.0f) / max_np(d[e], 1.0e-15f);
-        }
-        *reinterpret_cast<f32x4*>(out + (long)r * ld_out + c0) = o;
-    }
-};
-
-// out = cur * max(num, 0) / max(acc, 1e-15): acc is the NEGATIVE gradient part.
-template <class T>
-struct EpiMuDen {
-    const T* cur;
-    long ld_cur;
-    const T* num;
-    long ld_num;
-    T* out;
-    long ld_out;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const T nu = num[(long)r * ld_num + c];
-        out[(long)r * ld_out + c] = cur[(long)r * ld_cur + c] * max_np(nu, T(0)) /
-                                    max_np(v, T(1.0e-15));
-    }
-};
-
-// Split-K numerator: out = cur * max(sum_s slab_s, 0) / max(acc, 1e-15).  acc is the NEGATIVE part (x.G);
-// the positive part (Y.D^T) arrives as S ordered split-K partials, summed here in the fixed order
-// 0..S-1 (slab_sum, as mu_quotient_slabs_kernel does).  With few rows per GPU the Y.D^T product splits its
-// reduction; the quotient then rides on the x.G product (16-byte epilogue) instead of a pass of its own.
-// PEN: the L1/L2 penalty on the codes, out = cur * max(sum slabs, 0) / max(acc + l1 + l2 cur, 1e-15); without it
-// l1 and l2 are not read.
-template <class T, bool PEN>
-struct EpiMuDenSlabs {
-    static constexpr bool kVec4 = std::is_same<T, float>::value;
-    const T* cur;
-    long ld_cur;
-    const T* slabs;      // [S][rows, ld_slab]
-    long ld_slab;
-    long slab_stride;
-    int S;
-    T* out;
-    long ld_out;
-    T l1 = T(0), l2 = T(0);
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const T nu = slab_sum(slabs, slab_stride, S, (long)r * ld_slab + c);
-        const T x = cur[(long)r * ld_cur + c];
-        if constexpr (PEN) v = v + l1 + l2 * x;
-        out[(long)r * ld_out + c] = x * max_np(nu, T(0)) / max_np(v, T(1.0e-15));
-    }
-    bool vec_ok() const {
-        return al16_ptr(cur) && al16_ptr(slabs) && al16_ptr(out) && (ld_cur % 4) == 0 && (ld_slab % 4) == 0 &&
-               (slab_stride % 4) == 0 && (ld_out % 4) == 0;
-    }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        if constexpr (std::is_same<T, float>::value) {
-            const f32x4 nu = slab_sum(reinterpret_cast<const f32x4*>(slabs + (long)r * ld_slab + c0), slab_stride / 4, S, 0L);
-            const f32x4 x = *reinterpret_cast<const f32x4*>(cur + (long)r * ld_cur + c0);
-            f32x4 q;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float d = v[e];
-                if constexpr (PEN) d = d + l1 + l2 * x[e];
-                q[e] = x[e] * max_np(nu[e], 0.0f) / max_np(d, 1.0e-15f);
-            }
-            *reinterpret_cast<f32x4*>(out + (long)r * ld_out + c0) = q;
-        }
-    }
-};
-
-// out = acc * mask  (f = (x.D) o M, grads.py:113,123)
-template <class T>
-struct EpiMulMask {
-    const real_t<T>* mask;
-    long ld_mask;
-    T* out;
-    long ld_out;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        out[(long)r * ld_out + c] = scale(v, mask[(long)r * ld_mask + c]);
-    }
-    static constexpr bool kVec4 = std::is_same<T, float>::value;   // one load per element: 16-byte form
-    bool vec_ok() const { return al16_ptr(mask) && al16_ptr(out) && (ld_mask % 4) == 0 && (ld_out % 4) == 0; }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        if constexpr (std::is_same<T, float>::value) {
-            const f32x4 m = *reinterpret_cast<const f32x4*>(mask + (long)r * ld_mask + c0);
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = v[e] * m[e];
-            *reinterpret_cast<f32x4*>(out + (long)r * ld_out + c0) = o;
-        }
-    }
-};
-
-// out = acc * mask for a BINARY mask handed over as row bits (see epi_rowbits in gemm_mfma_f32.hpp):
-// the factor is exactly 1.0f or 0.0f and the product is formed as in EpiMulMask (so NaN / Inf / -0
-// behave as the reference's  f * mask).  float only (the fp32 MFMA core implements the protocol).
-struct EpiMulMaskBits {
-    static constexpr bool kRowBits = true;
-    const uint32_t* bits;   // [(rows + 31) / 32][ld_bits]
-    long ld_bits;
-    float* out;
-    long ld_out;
-    __device__ __forceinline__ uint32_t load_bits(int row0, int col) const {
-        return bits[(long)(row0 >> 5) * ld_bits + col];
-    }
-    __device__ __forceinline__ void with_bit(int r, int c, float v, uint32_t bit, int) const {
-        out[(long)r * ld_out + c] = v * (bit ? 1.0f : 0.0f);
-    }
-    __device__ __forceinline__ void operator()(int, int, float, int) const {}
-};
-
-// out = w y + (1 - w) acc,  w = mask in [0, 1]: the data with its missing part filled in from the current model
-// (the E step of em-hals, nmf_hals.hip).  Formed as one multiply (1 - w) acc and one fma with w y, so that for
-// finite operands w == 1 returns y and w == 0 returns acc bit for bit.  No select: every element loads y and w
-// and runs the same two operations.
-__device__ __forceinline__ float fma_np(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_np(double a, double b, double c) { return __builtin_fma(a, b, c); }
-template <class T>
-struct EpiImpute {
-    const T* y;      // y, mask and out are [rows, ld] with one leading dimension: one offset per element
-    const T* mask;
-    T* out;
-    long ld;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const long o = (long)r * ld + c;
-        const T w = mask[o];
-        const T yy = y[o];
-        const T t = (T(1) - w) * v;
-        out[o] = fma_np(w, yy, t);
-    }
-    static constexpr bool kVec4 = std::is_same<T, float>::value;   // two loads per element: 16-byte form
-    bool vec_ok() const { return al16_ptr(y) && al16_ptr(mask) && al16_ptr(out) && (ld % 4) == 0; }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        if constexpr (std::is_same<T, float>::value) {
-            const long o = (long)r * ld + c0;
-            const f32x4 w = *reinterpret_cast<const f32x4*>(mask + o);
-            const f32x4 yy = *reinterpret_cast<const f32x4*>(y + o);
-            f32x4 q;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float t = (1.0f - w[e]) * v[e];
-                q[e] = fma_np(w[e], yy[e], t);
-            }
-            *reinterpret_cast<f32x4*>(out + o) = q;
-        }
-    }
-};
-
-// KL ratio: out = (y [* mask]) / (acc + 1e-15)   (grads.py:145-149,154-158)
-template <class T>
-struct EpiKlRatio {
-    const T* y;
-    long ld_y;
-    const T* mask;  // nullable
-    long ld_mask;
-    T* out;
-    long ld_out;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        T yy = y[(long)r * ld_y + c];
-        if (mask != nullptr) yy = yy * mask[(long)r * ld_mask + c];
-        out[(long)r * ld_out + c] = yy / (v + T(1.0e-15));
-    }
-    static constexpr bool kVec4 = std::is_same<T, float>::value;
-    bool vec_ok() const {
-        return al16_ptr(y) && al16_ptr(out) && (ld_y % 4) == 0 && (ld_out % 4) == 0 &&
-               (mask == nullptr || (al16_ptr(mask) && (ld_mask % 4) == 0));
-    }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        if constexpr (std::is_same<T, float>::value) {
-            f32x4 yy = *reinterpret_cast<const f32x4*>(y + (long)r * ld_y + c0);
-            if (mask != nullptr) {
-                const f32x4 m = *reinterpret_cast<const f32x4*>(mask + (long)r * ld_mask + c0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) yy[e] = yy[e] * m[e];
-            }
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = yy[e] / (v[e] + 1.0e-15f);
-            *reinterpret_cast<f32x4*>(out + (long)r * ld_out + c0) = o;
-        }
-    }
-};
-
-// ---- beta-divergence (DCP_LIK_BETA) ------------------------------------------------------------------
-// Exponent forms of the two parts R1 = (Y o M) o V^(beta-2), R2 = M o V^(beta-1), V = acc + 1e-15: closed
-// forms for the common betas, one log2 + one exp2 per element otherwise.
-enum BetaMode { BETA_0 = 0, BETA_HALF = 1, BETA_1 = 2, BETA_3HALF = 3, BETA_2 = 4, BETA_3 = 5, BETA_GEN = 6 };
-inline int beta_mode(double b) {
-    return b == 0.0 ? BETA_0 : b == 0.5 ? BETA_HALF : b == 1.0 ? BETA_1 : b == 1.5 ? BETA_3HALF
-         : b == 2.0 ? BETA_2 : b == 3.0 ? BETA_3 : BETA_GEN;
-}
-__device__ __forceinline__ float beta_rsqrt(float v) { return rsqrtf(v); }
-__device__ __forceinline__ double beta_rsqrt(double v) { return rsqrt(v); }
-__device__ __forceinline__ float beta_pow(float v, float e) { return exp2f(e * log2f(v)); }
-__device__ __forceinline__ double beta_pow(double v, double e) { return exp(e * log(v)); }
-
-template <class T>
-__device__ __forceinline__ void beta_parts(int mode, T e, T acc, T ym, T m, T& r1, T& r2) {
-    const T v = acc + T(1.0e-15);
-    switch (mode) {
-    case BETA_0: { const T r = T(1) / v; r1 = ym * r * r; r2 = m * r; break; }
-    case BETA_HALF: { const T s = beta_rsqrt(v); r1 = ym * (s * s * s); r2 = m * s; break; }
-    case BETA_1: { r1 = ym / v; r2 = m; break; }
-    case BETA_3HALF: { const T s = beta_rsqrt(v); r1 = ym * s; r2 = m * (s * v); break; }
-    case BETA_2: { r1 = ym; r2 = m * v; break; }
-    case BETA_3: { r1 = ym * v; r2 = m * (v * v); break; }
-    default: { const T p = beta_pow(v, e); r1 = ym * p; r2 = m * (p * v); break; }
-    }
-}
-
-// Forward product of a beta step: both gradient operands in one pass over x.D.
-//   r1 = (Y o M) o V^(beta-2),  r2 = M o V^(beta-1)       (M = 1 without a mask)
-// ym is Y o M (the caller's pre-masked Y); mode = beta_mode(beta), e = beta - 2.
-template <class T>
-struct EpiBetaParts {
-    static constexpr bool kVec4 = std::is_same<T, float>::value;
-    const T* ym;
-    long ld_y;
-    const T* mask;  // nullable
-    long ld_mask;
-    int mode;
-    T e;
-    T* r1;
-    T* r2;
-    long ld_out;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const T m = mask != nullptr ? mask[(long)r * ld_mask + c] : T(1);
-        T a, b;
-        beta_parts<T>(mode, e, v, ym[(long)r * ld_y + c], m, a, b);
-        r1[(long)r * ld_out + c] = a;
-        r2[(long)r * ld_out + c] = b;
-    }
-    bool vec_ok() const {
-        return al16_ptr(ym) && al16_ptr(r1) && al16_ptr(r2) && (ld_y % 4) == 0 && (ld_out % 4) == 0 &&
-               (mask == nullptr || (al16_ptr(mask) && (ld_mask % 4) == 0));
-    }
-    __device__ __forceinline__ void vec4(int r, int c0, f32x4 v, int) const {
-        if constexpr (std::is_same<T, float>::value) {
-            const f32x4 yy = *reinterpret_cast<const f32x4*>(ym + (long)r * ld_y + c0);
-            f32x4 m = {1.0f, 1.0f, 1.0f, 1.0f};
-            if (mask != nullptr) m = *reinterpret_cast<const f32x4*>(mask + (long)r * ld_mask + c0);
-            f32x4 a, b;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float ai, bi;
-                beta_parts<float>(mode, e, v[i], yy[i], m[i], ai, bi);
-                a[i] = ai;
-                b[i] = bi;
-            }
-            *reinterpret_cast<f32x4*>(r1 + (long)r * ld_out + c0) = a;
-            *reinterpret_cast<f32x4*>(r2 + (long)r * ld_out + c0) = b;
-        }
-    }
-};
-
-// d_beta(y | v) in double (Fevotte & Idier 2011):
-//   beta = 0: y/v - log(y/v) - 1     beta = 1: y log(y/v) - y + v  (0 log 0 = 0)
-//   otherwise (y^beta + (beta-1) v^beta - beta y v^(beta-1)) / (beta (beta-1))
-__device__ __forceinline__ double beta_divergence_elem(double beta, double y, double v) {
-    if (beta == 0.0) {
-        const double q = y / v;
-        return q - log(q) - 1.0;
-    }
-    if (beta == 1.0) return (y > 0.0 ? y * log(y / v) : 0.0) - y + v;
-    if (beta == 2.0) {
-        const double d = y - v;
-        return 0.5 * d * d;
-    }
-    return (pow(y, beta) + (beta - 1.0) * pow(v, beta) - beta * y * pow(v, beta - 1.0)) / (beta * (beta - 1.0));
-}
-
-// out = M o d_beta(Y | acc + 1e-15), an entry with M == 0 contributing exactly 0 (reduced by reduce_partial_kernel: SumOp over MapValue)
-template <class T>
-struct EpiBetaDivergence {
-    const T* y;
-    long ld_y;
-    const T* mask;  // nullable
-    long ld_mask;
-    double beta;
-    T* out;
-    long ld_out;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        const double m = mask != nullptr ? (double)mask[(long)r * ld_mask + c] : 1.0;
-        double d = 0.0;
-        if (m != 0.0) d = m * beta_divergence_elem(beta, (double)y[(long)r * ld_y + c], (double)v + 1.0e-15);
-        out[(long)r * ld_out + c] = (T)d;
-    }
-};
-
-// Residual: out = (y - acc) [* mask]   (parity metric; reduced by reduce_partial_kernel: SumOp over MapAbs2)
-template <class T>
-struct EpiResidual {
-    const T* y;
-    long ld_y;
-    const real_t<T>* mask;  // nullable
-    long ld_mask;
-    T* out;
-    long ld_out;
-    __device__ __forceinline__ void operator()(int r, int c, T v, int) const {
-        T d = sub(y[(long)r * ld_y + c], v);
-        if (mask != nullptr) d = scale(d, mask[(long)r * ld_mask + c]);
-        out[(long)r * ld_out + c] = d;
-    }
-};
 
 }  // namespace dcp

@@ -37,9 +37,10 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "scalar.hpp"   // f32x4
+
 namespace dcp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum { KMAJOR = 0, XMAJOR = 1 };

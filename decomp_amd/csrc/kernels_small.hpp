@@ -3,6 +3,7 @@
 // sign scans.  All are deterministic (no float atomics).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "epilogue.hpp"   // mu_quotient
 #include "reduce.hpp"
 #include "scalar.hpp"
 
@@ -177,8 +178,7 @@ __global__ void __launch_bounds__(256) mu_quotient_kernel(const T* __restrict__ 
         const long r = i / cols, c = i - r * cols;
         const T d = den_bcast == 0 ? den[r * ld_den + c] : (den_bcast == 1 ? den[r] : den[c]);
         const T nu = num[r * ld_num + c];
-        out[r * ld_out + c] =
-            cur[r * ld_cur + c] * max_np(nu, T(0)) / max_np(d, T(1.0e-15));
+        out[r * ld_out + c] = mu_quotient(cur[r * ld_cur + c], nu, d);
     }
 }
 
@@ -196,10 +196,9 @@ __global__ void __launch_bounds__(256) mu_quotient_slabs_kernel(const T* __restr
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
         const T nu = slab_sum(slabs, stride, S, i);
         const long r = i / cols, c = i - r * cols;
-        T d = den[r * ld_den + c];
+        const T d = den[r * ld_den + c];
         const T x = cur[i];
-        if constexpr (PEN) d = d + l1 + l2 * x;
-        out[i] = x * max_np(nu, T(0)) / max_np(d, T(1.0e-15));
+        out[i] = mu_quotient_if<PEN>(x, nu, d, l1, l2);
     }
 }
 
@@ -215,11 +214,8 @@ __global__ void __launch_bounds__(256) mu_quotient_stacked_kernel(const T* __res
         const long at[2] = {i, count + i};
         T sum[2];
         slab_sums(slabs, stride, S, at, sum);
-        T de = sum[0];
-        const T nu = sum[1];
         const T x = cur[i];
-        if constexpr (PEN) de = de + l1 + l2 * x;
-        out[i] = x * max_np(nu, T(0)) / max_np(de, T(1.0e-15));
+        out[i] = mu_quotient_if<PEN>(x, sum[1], sum[0], l1, l2);
     }
 }
 

@@ -91,18 +91,15 @@ struct EpiProxStep {
     // float32: the same step on 4 consecutive columns of a row (16-byte loads of y.A^H, v, x_prev and
     // stores of x_new / v_next: the epilogue reads three arrays per element, see epi_vec4)
     static constexpr bool kVec4 = std::is_same<T, float>::value;
-    bool vec_ok() const {
-        return al16_ptr(yAt) && al16_ptr(v) && al16_ptr(xprev) && al16_ptr(xnew) && al16_ptr(alpha) &&
-               al16_ptr(tolk) && (vnext == nullptr || al16_ptr(vnext)) && (ld % 4) == 0;
-    }
+    bool vec_ok() const { return aligned16(yAt, v, xprev, xnew, alpha, tolk, vnext, ld); }
     __device__ __forceinline__ void vec4(int r, int c0, f32x4 back, int) const {
         if constexpr (std::is_same<T, float>::value) {
             const long i = (long)r * ld + c0;
             const float li = Linv[0];
-            const f32x4 y4 = *reinterpret_cast<const f32x4*>(yAt + i);
-            const f32x4 v4 = *reinterpret_cast<const f32x4*>(v + i);
-            const f32x4 p4 = *reinterpret_cast<const f32x4*>(xprev + i);
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(alpha + c0);
+            const f32x4 y4 = load4(yAt + i);
+            const f32x4 v4 = load4(v + i);
+            const f32x4 p4 = load4(xprev + i);
+            const f32x4 a4 = load4(alpha + c0);
             const float rs = rowscale != nullptr ? rowscale[r] : 1.0f;
             f32x4 xn, vn;
             bool viol = false;
@@ -116,24 +113,21 @@ struct EpiProxStep {
                 vn[e] = xn[e] + d * coef;
                 if (check && !((fabsf(d) - tolk[c0 + e]) < 0.0f)) viol = true;
             }
-            *reinterpret_cast<f32x4*>(xnew + i) = xn;
-            if (vnext != nullptr) *reinterpret_cast<f32x4*>(vnext + i) = vn;
+            store4(xnew + i, xn);
+            if (vnext != nullptr) store4(vnext + i, vn);
             if (viol) *flag = 1;
         }
     }
     // complex64: two consecutive columns of a row (16 bytes) per call, see CplxColEpi
     static constexpr bool kCVec2 = std::is_same<T, c64>::value;
-    bool cvec_ok() const {
-        return al16_ptr(yAt) && al16_ptr(v) && al16_ptr(xprev) && al16_ptr(xnew) &&
-               (vnext == nullptr || al16_ptr(vnext)) && (ld % 2) == 0;
-    }
+    bool cvec_ok() const { return aligned16<2>(yAt, v, xprev, xnew, vnext, ld); }
     __device__ __forceinline__ void cvec2(int r, int c0, f32x4 back, int) const {
         if constexpr (std::is_same<T, c64>::value) {
             const long i = (long)r * ld + c0;
             const float li = Linv[0];
-            const f32x4 y4 = *reinterpret_cast<const f32x4*>(yAt + i);
-            const f32x4 v4 = *reinterpret_cast<const f32x4*>(v + i);
-            const f32x4 p4 = *reinterpret_cast<const f32x4*>(xprev + i);
+            const f32x4 y4 = load4(yAt + i);
+            const f32x4 v4 = load4(v + i);
+            const f32x4 p4 = load4(xprev + i);
             const float rs = rowscale != nullptr ? rowscale[r] : 1.0f;
             f32x4 xn4, vn4;
             bool viol = false;
@@ -150,8 +144,8 @@ struct EpiProxStep {
                 vn4[2 * e] = vn.re; vn4[2 * e + 1] = vn.im;
                 if (check && !((absval(d) - tolk[c0 + e]) < 0.0f)) viol = true;
             }
-            *reinterpret_cast<f32x4*>(xnew + i) = xn4;
-            if (vnext != nullptr) *reinterpret_cast<f32x4*>(vnext + i) = vn4;
+            store4(xnew + i, xn4);
+            if (vnext != nullptr) store4(vnext + i, vn4);
             if (viol) *flag = 1;
         }
     }
@@ -202,29 +196,27 @@ struct EpiProxStepH {
     }
     static constexpr bool kVec4 = std::is_same<T, float>::value;
     bool vec_ok() const {
-        return al16_ptr(rs) && al16_ptr(xprev) && al16_ptr(xnew) && al16_ptr(alpha) && al16_ptr(tolk) &&
-               (vnext == nullptr || al16_ptr(vnext)) && (xfinal == nullptr || (al16_ptr(xfinal) && al16_ptr(sdiv))) &&
-               (ld % 4) == 0;
+        return aligned16(rs, xprev, xnew, alpha, tolk, vnext, ld) && (xfinal == nullptr || aligned16(xfinal, sdiv));
     }
     __device__ __forceinline__ void vec4(int r, int c0, f32x4 back, int) const {
         if constexpr (std::is_same<T, float>::value) {
             const long i = (long)r * ld + c0;
             const float li = Linv[0];
-            const f32x4 r4 = *reinterpret_cast<const f32x4*>(rs + i);
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(alpha + c0);
+            const f32x4 r4 = load4(rs + i);
+            const f32x4 a4 = load4(alpha + c0);
             f32x4 xn;
 #pragma unroll
             for (int e = 0; e < 4; ++e) xn[e] = prox_apply<PROX>(back[e] + r4[e], li * a4[e]);
-            *reinterpret_cast<f32x4*>(xnew + i) = xn;
+            store4(xnew + i, xn);
             if (xfinal != nullptr) {
-                const f32x4 s4 = *reinterpret_cast<const f32x4*>(sdiv + c0);
+                const f32x4 s4 = load4(sdiv + c0);
                 f32x4 xf;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) xf[e] = xn[e] / s4[e];
-                *reinterpret_cast<f32x4*>(xfinal + i) = xf;
+                store4(xfinal + i, xf);
             }
             if (need_prev) {
-                const f32x4 p4 = *reinterpret_cast<const f32x4*>(xprev + i);
+                const f32x4 p4 = load4(xprev + i);
                 f32x4 vn;
                 bool viol = false;
 #pragma unroll
@@ -233,21 +225,18 @@ struct EpiProxStepH {
                     vn[e] = xn[e] + d * coef;
                     if (check && !((fabsf(d) - tolk[c0 + e]) < 0.0f)) viol = true;
                 }
-                if (vnext != nullptr) *reinterpret_cast<f32x4*>(vnext + i) = vn;
+                if (vnext != nullptr) store4(vnext + i, vn);
                 if (viol) *flag = 1;
             }
         }
     }
     static constexpr bool kCVec2 = std::is_same<T, c64>::value;
-    bool cvec_ok() const {
-        return al16_ptr(rs) && al16_ptr(xprev) && al16_ptr(xnew) && (vnext == nullptr || al16_ptr(vnext)) &&
-               (xfinal == nullptr || al16_ptr(xfinal)) && (ld % 2) == 0;
-    }
+    bool cvec_ok() const { return aligned16<2>(rs, xprev, xnew, vnext, xfinal, ld); }
     __device__ __forceinline__ void cvec2(int r, int c0, f32x4 back, int) const {
         if constexpr (std::is_same<T, c64>::value) {
             const long i = (long)r * ld + c0;
             const float li = Linv[0];
-            const f32x4 r4 = *reinterpret_cast<const f32x4*>(rs + i);
+            const f32x4 r4 = load4(rs + i);
             f32x4 xn4;
             c64 xn[2];
 #pragma unroll
@@ -256,13 +245,14 @@ struct EpiProxStepH {
                 xn[e] = prox_apply<PROX>(z, li * alpha[c0 + e]);
                 xn4[2 * e] = xn[e].re; xn4[2 * e + 1] = xn[e].im;
             }
-            *reinterpret_cast<f32x4*>(xnew + i) = xn4;
+            store4(xnew + i, xn4);
             if (xfinal != nullptr) {
                 const float s0 = sdiv[c0], s1 = sdiv[c0 + 1];
-                *reinterpret_cast<f32x4*>(xfinal + i) = f32x4{xn4[0] / s0, xn4[1] / s0, xn4[2] / s1, xn4[3] / s1};
+                const f32x4 xf = {xn4[0] / s0, xn4[1] / s0, xn4[2] / s1, xn4[3] / s1};
+                store4(xfinal + i, xf);
             }
             if (need_prev) {
-                const f32x4 p4 = *reinterpret_cast<const f32x4*>(xprev + i);
+                const f32x4 p4 = load4(xprev + i);
                 f32x4 vn4;
                 bool viol = false;
 #pragma unroll
@@ -272,7 +262,7 @@ struct EpiProxStepH {
                     vn4[2 * e] = vn.re; vn4[2 * e + 1] = vn.im;
                     if (check && !((absval(d) - tolk[c0 + e]) < 0.0f)) viol = true;
                 }
-                if (vnext != nullptr) *reinterpret_cast<f32x4*>(vnext + i) = vn4;
+                if (vnext != nullptr) store4(vnext + i, vn4);
                 if (viol) *flag = 1;
             }
         }

@@ -1,7 +1,7 @@
 // C ABI: NMF by HALS (exact block coordinate descent, squared loss, no mask), its row-sharded loop and split
 // step, the non-negative coordinate sweep on its own, and em-hals (HALS on the data with its missing entries
 // imputed from the current model: dcp_nmf_impute_*, dcp_nmf_emhals_*).  Contract in include/decomp_hip.h; the
-// sweep kernels in nmf_hals.hpp, the imputing epilogue (EpiImpute) in gemm.hpp.
+// sweep kernels in nmf_hals.hpp, the imputing epilogue (EpiImpute) in epilogue.hpp.
 #include <cmath>
 
 #include "comm.hpp"

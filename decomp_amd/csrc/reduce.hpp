@@ -197,7 +197,6 @@ struct MapAbsDiff {   // |a_i - b_i|
 // largest first: rounds of that many slabs while they last, then one at a time -- one at a time the loop is a chain
 // of L2 round trips (16 us for 64 slabs of a 64 x 64 Gram matrix; eight in flight: 5.9 us).  The order is the same for
 // every DEPTHS.  T: a scalar, cx, or a 16-byte vector of reals (element-wise, so the same bits per element).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 DCP_HD f32x4 add(f32x4 a, f32x4 b) { return a + b; }
 DCP_HD f64x2 add(f64x2 a, f64x2 b) { return a + b; }

@@ -15,6 +15,8 @@ struct cx {
 typedef cx<float> c64;
 typedef cx<double> c128;
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of floats: one load / store per lane
+
 template <class T> struct scalar_traits;
 template <> struct scalar_traits<float>  { typedef float  real; static constexpr bool is_complex = false; };
 template <> struct scalar_traits<double> { typedef double real; static constexpr bool is_complex = false; };
