@@ -373,6 +373,23 @@ inline void launch_tm_max(hipStream_t st, const R* v, long n, R jitter, R* scal)
 }
 
 // ---- dictionary statistics ----------------------------------------------------------------------
+// acc + a b for the statistics' partial sums, with the complex product spelled out:
+//   re = fma(a.re, b.re, -(a.im b.im)),   im = fma(a.im, b.re, a.re b.im).
+// Left as madd's plain expression, which of the two products of a part gets fused into the other is the compiler's
+// choice and differs from kernel to kernel; kernels that must agree bit for bit on the same sum (the dense ones here
+// and those of template_events.hpp) take their terms from this one spelling.
+template <class T>
+DCP_HD T tm_stat_madd(T acc, T a, T b) {
+    if constexpr (scalar_traits<T>::is_complex) {
+        typedef real_t<T> R;
+        const R re = madd(R(-(a.im * b.im)), a.re, b.re);
+        const R im = madd(R(a.re * b.im), a.im, b.re);
+        return T{acc.re + re, acc.im + im};
+    } else {
+        return madd(acc, a, b);
+    }
+}
+
 // mpart[((b T + t) T + t') nd + (d + dh)] = sum_(c in core(d)) x[b, t, c] conj(x[b, t', c + d])
 template <class T>
 __global__ void __launch_bounds__(256) tm_stats_core_kernel(const T* __restrict__ x, TmGeom g, T* __restrict__ mpart) {
@@ -385,7 +402,7 @@ __global__ void __launch_bounds__(256) tm_stats_core_kernel(const T* __restrict_
         long cl, ch, ul, uh;
         g.core(d, &cl, &ch, &ul, &uh);
         T acc = zero_of<T>();
-        for (long c = cl; c <= ch; ++c) acc = madd(acc, xa[c], conj_of(xb[c + d]));
+        for (long c = cl; c <= ch; ++c) acc = tm_stat_madd(acc, xa[c], conj_of(xb[c + d]));
         mpart[((b * g.T + t) * g.T + tp) * nd + j] = acc;
     }
 }
@@ -421,7 +438,8 @@ __global__ void __launch_bounds__(256) tm_stats_yx_kernel(const T* __restrict__ 
         long lo, hi;
         g.window(k, 0, &lo, &hi);
         T acc = zero_of<T>();
-        for (long c = lo; c <= hi; ++c) acc = madd(acc, x[(b * g.T + t) * g.C + c], y[b * g.N + g.s * c - g.Q + k]);
+        for (long c = lo; c <= hi; ++c)
+            acc = tm_stat_madd(acc, x[(b * g.T + t) * g.C + c], y[b * g.N + g.s * c - g.Q + k]);
         yxpart[(b * g.T + t) * g.S + k] = acc;
     }
 }
@@ -660,68 +678,96 @@ inline long tm_hmax(const TmGeom& g) {
     return hm;
 }
 
-// Statistics of x (written, or added as stat / acc_it to the running sums XXt [TS, TS], yX [TS]) and the
-// D update D <- l2(D + (yX - XXt D) / (Gershgorin(XXt) + 1e-15)); *maxdiff = max |D - D_new|.
+// The workspace of a dictionary step: the partial statistics and the D update's vectors.
 template <class T>
-inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
-                    double* maxdiff) {
+struct TmDstepWs {
+    T *mpart = nullptr, *eh = nullptr, *et = nullptr, *yxpart = nullptr, *step = nullptr, *U = nullptr, *Dn = nullptr;
+    real_t<T>*colabs = nullptr, *rowmax = nullptr, *scal = nullptr;
+};
+
+template <class T>
+inline void tm_dstep_layout(WsLayout& a, TmDstepWs<T>& w, const TmGeom& g, long hmax) {
+    const long nd = g.nd(), TS = g.T * g.S;
+    a.take(w.mpart, g.B * g.T * g.T * nd);
+    a.take(w.eh, g.T * g.T * nd * hmax);
+    a.take(w.et, g.T * g.T * nd * hmax);
+    a.take(w.yxpart, g.B * TS);
+    a.take(w.colabs, TS);
+    a.take(w.step, TS);
+    a.take(w.U, TS);
+    a.take(w.Dn, TS);
+    a.take(w.rowmax, g.T);
+    a.take(w.scal, 4);
+}
+
+// A dictionary step around its partial sums: `partials()` enqueues whatever fills mpart and yxpart; then the edge
+// terms, the assembly of XXt / yX (written, or added as stat / acc_it to the running sums), the D update
+// D <- l2(D + (yX - XXt D) / (Gershgorin(XXt) + 1e-15)) and the step's one synchronisation; *maxdiff = max |D - D_new|.
+// Timed under DCP_PROF_STATS up to the assembly, the partial sums alone under DCP_PROF_MISC as well.
+template <class T, class Partials>
+inline int tm_dstep_around(dcp_handle* h, const TmDstepWs<T>& w, const T* X, T* D, T* XXt, T* yX, const TmGeom& g,
+                           long hmax, int acc_it, double* maxdiff, Partials&& partials) {
     typedef real_t<T> R;
     hipStream_t st = h->stream;
-    const long nd = g.nd(), TS = g.T * g.S, hmax = tm_hmax(g);
-    T *mpart = nullptr, *eh = nullptr, *et = nullptr, *yxpart = nullptr, *step = nullptr, *U = nullptr, *Dn = nullptr;
-    R *colabs = nullptr, *rowmax = nullptr, *scal = nullptr;
-    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) {
-        a.take(mpart, g.B * g.T * g.T * nd);
-        a.take(eh, g.T * g.T * nd * hmax);
-        a.take(et, g.T * g.T * nd * hmax);
-        a.take(yxpart, g.B * TS);
-        a.take(colabs, TS);
-        a.take(step, TS);
-        a.take(U, TS);
-        a.take(Dn, TS);
-        a.take(rowmax, g.T);
-        a.take(scal, 4);
-    }));
+    const long TS = g.T * g.S;
     {
         ProfScope ps(h, DCP_PROF_STATS);
-        hipLaunchKernelGGL((tm_stats_core_kernel<T>), dim3(g.T, g.T, g.B), dim3(256), 0, st, X, g, mpart);
+        {
+            ProfScope pp(h, DCP_PROF_MISC);
+            DCP_TRY(partials());
+        }
+        hipLaunchKernelGGL((tm_stats_edge_kernel<T>), dim3(g.T, g.T), dim3(256), 0, st, X, g, hmax, w.eh, w.et);
         DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((tm_stats_edge_kernel<T>), dim3(g.T, g.T), dim3(256), 0, st, X, g, hmax, eh, et);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((tm_stats_yx_kernel<T>), dim3(g.T, g.B), dim3(256), 0, st, Y, X, g, yxpart);
-        DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((tm_stats_assemble_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)mpart, (const T*)eh,
-                           (const T*)et, (const T*)yxpart, g, hmax, acc_it, XXt, yX);
+        hipLaunchKernelGGL((tm_stats_assemble_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)w.mpart,
+                           (const T*)w.eh, (const T*)w.et, (const T*)w.yxpart, g, hmax, acc_it, XXt, yX);
         DCP_LAUNCH_OK(h, hipGetLastError());
     }
     hipLaunchKernelGGL((tm_dupdate_rows_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)XXt, (const T*)yX,
-                       (const T*)D, TS, colabs, step);
+                       (const T*)D, TS, w.colabs, w.step);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    launch_tm_max<R>(st, colabs, TS, R(1.0e-15), scal);
+    launch_tm_max<R>(st, w.colabs, TS, R(1.0e-15), w.scal);
     DCP_LAUNCH_OK(h, hipGetLastError());
     hipLaunchKernelGGL((tm_dupdate_apply_kernel<T>), dim3(tm_grid(TS)), dim3(256), 0, st, (const T*)D,
-                       (const T*)step, (const R*)scal, TS, U);
+                       (const T*)w.step, (const R*)w.scal, TS, w.U);
     DCP_LAUNCH_OK(h, hipGetLastError());
     // D_new = l2(U) (normalize.py:2-10) into its own buffer (the kernel's ref and out are restrict), rowmax[t] =
     // max |D - D_new| over the row; then D <- D_new
-    hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(g.T), dim3(256), 0, st, (const T*)U, g.S, g.S, 0, (const T*)D,
-                       g.S, Dn, g.S, rowmax);
+    hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(g.T), dim3(256), 0, st, (const T*)w.U, g.S, g.S, 0,
+                       (const T*)D, g.S, w.Dn, g.S, w.rowmax);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    DCP_HIP_OK(h, hipMemcpyAsync(D, Dn, (size_t)TS * sizeof(T), hipMemcpyDeviceToDevice, st));
-    launch_tm_max<R>(st, rowmax, g.T, R(0), scal + 2);
+    DCP_HIP_OK(h, hipMemcpyAsync(D, w.Dn, (size_t)TS * sizeof(T), hipMemcpyDeviceToDevice, st));
+    launch_tm_max<R>(st, w.rowmax, g.T, R(0), w.scal + 2);
     DCP_LAUNCH_OK(h, hipGetLastError());
     void* hostv = nullptr;
     DCP_TRY(host_scratch(h, 64, &hostv));
-    DCP_HIP_OK(h, hipMemcpyAsync(hostv, scal + 3, sizeof(R), hipMemcpyDeviceToHost, st));
+    DCP_HIP_OK(h, hipMemcpyAsync(hostv, w.scal + 3, sizeof(R), hipMemcpyDeviceToHost, st));
     DCP_HIP_OK(h, hipStreamSynchronize(st));
     *maxdiff = (double)*reinterpret_cast<R*>(hostv);
     return DCP_OK;
+}
+
+// Statistics of x and the D update (tm_dstep_around), the partial sums over all C coefficients of every row.
+template <class T>
+inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
+                    double* maxdiff) {
+    hipStream_t st = h->stream;
+    const long hmax = tm_hmax(g);
+    TmDstepWs<T> w;
+    DCP_TRY(ws_lay_out(h, [&](WsLayout& a) { tm_dstep_layout(a, w, g, hmax); }));
+    return tm_dstep_around<T>(h, w, X, D, XXt, yX, g, hmax, acc_it, maxdiff, [&]() -> int {
+        hipLaunchKernelGGL((tm_stats_core_kernel<T>), dim3(g.T, g.T, g.B), dim3(256), 0, st, X, g, w.mpart);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        hipLaunchKernelGGL((tm_stats_yx_kernel<T>), dim3(g.T, g.B), dim3(256), 0, st, Y, X, g, w.yxpart);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        return DCP_OK;
+    });
 }
 
 }  // namespace dcp
 
 #include "template_pursuit.hpp"   // matching pursuit on the same operator
 #include "template_omp.hpp"       // orthogonal (re-fitting) pursuit on the same operator
+#include "template_events.hpp"    // the dictionary step from event lists, for the codes of those two
 
 // ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip) ------------------------------
 #define DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding)                                    \
@@ -802,6 +848,17 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
         if (acc_it < 0) return dcp::fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");                           \
         return dcp::tm_dstep<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt, (TYPE*)yX, g,      \
                                    acc_it, maxdiff);                                                           \
+    }                                                                                                          \
+    extern "C" int dcp_tm_dstep_events_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, \
+                                              void* yX, int64_t B, int64_t T_, int64_t S, int64_t N,          \
+                                              int64_t stride, int padding, int acc_it, int64_t max_events,    \
+                                              double* maxdiff) {                                               \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        if (!Y || !X || !D || !XXt || !yX || !maxdiff) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
+        if (acc_it < 0) return dcp::fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");                           \
+        if (max_events < 1) return dcp::fail(h, DCP_ERR_INVALID, "max_events must be >= 1");                   \
+        return dcp::tm_dstep_events<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt, (TYPE*)yX, \
+                                          g, acc_it, max_events, maxdiff);                                     \
     }                                                                                                          \
     extern "C" int dcp_tm_gather_windows_##SFX(dcp_handle* h, const void* Y, const void* X,                   \
                                                 const int64_t* idx_b, const int64_t* idx_n, int64_t m,        \

@@ -15,7 +15,11 @@ size is formed on the hot path (include/decomp_hip.h ``dcp_tm_*``, decomp_amd/cs
     up to date from the lag correlations of the templates (decomp_amd/csrc/template_pursuit.hpp);
   * ``orthogonal_pursuit`` (not in the reference) is its re-fitting form, batch OMP on the same operator: the Gram
     entries of the support are single reads of the lag correlations, the factor an s x s Cholesky per signal
-    (decomp_amd/csrc/template_omp.hpp).
+    (decomp_amd/csrc/template_omp.hpp);
+  * ``solve(alpha=0, lasso_method='omp' | 'mp' | 'mp_pos', lasso_iter=s, lasso_tol=tol)`` learns the templates for
+    the codes of those two coders: the coder replaces the LASSO step, and the dictionary step sums its statistics over
+    per-row lists of the non-zero coefficients instead of all C of them, bit for bit the dense step's result
+    (``dcp_tm_dstep_events_*``, decomp_amd/csrc/template_events.hpp).
 
 'cd', 'parallel_cd' and 'admm' have no structured form: for them ``_temp2mat`` is materialised on the
 device and the dense ``dcp_lasso_*`` solvers of decomp_amd.lasso run on it.  That path is correct but
@@ -37,6 +41,8 @@ from .utils.data import minibatch_index
 _JITTER = 1.0e-15
 _STRUCTURED = ('ista', 'acc_ista', 'fista')
 _DENSE = ('cd', 'parallel_cd', 'admm')
+# lasso_method -> (the coder's dcp_tm_<name>_*, its flags after tol)
+_GREEDY = {'omp': ('omp', ()), 'mp': ('pursuit', (0,)), 'mp_pos': ('pursuit', (1,))}
 
 
 def solve(y, D, alpha, stride=1, padding='SAME', x=None, tol=1.0e-4,
@@ -52,9 +58,17 @@ def solve(y, D, alpha, stride=1, padding='SAME', x=None, tol=1.0e-4,
     with C = _coef_size(S, N, stride, padding).  float or complex, all of one dtype.
     minibatch: number of windows of ``size_of_minibatch`` samples drawn per iteration
     (RandomState(random_seed)); None solves on the whole batch.
+    lasso_method 'omp', 'mp' or 'mp_pos' solves the sparsity-constrained problem instead,
+        argmin_{x, D} |y - x * D|^2   s.t. |x_b|_0 <= lasso_iter, |D_t|^2 <= 1,
+    with ``orthogonal_pursuit``, ``pursuit`` or ``pursuit(positive=True)`` as the coder: alpha must be 0, lasso_iter is
+    the coder's n_nonzero_coefs (per signal, or per window with minibatch) and lasso_tol its tol, the residual energy
+    at which a signal stops (None: none) -- the convention of dictionary_learning.solve(lasso_method='omp').  The
+    coders start from zero, so an ``x`` passed in is not read.  y must be finite.
     Returns (it, D, x) as the reference does.  NumPy in -> NumPy out; torch GPU tensors stay on the device.
     """
     get_array_module(y, D, x)                                         # template_matching.py:48
+    if lasso_method in _GREEDY:                                       # (the rest of its checks: solve_fastpath)
+        stride, _ = _geometry(int(D.shape[0]), int(D.shape[-1]), int(y.shape[-1]), stride, padding)
     rng = np.random.RandomState(random_seed)
     x_given = x
     if x is None:
@@ -87,6 +101,10 @@ def solve_fastpath(y, D, alpha, x, stride, padding, tol,
     if mask is not None:
         raise NotImplementedError('Template matching with mask is not '
                                   'yet implemented.')
+    if lasso_method in _GREEDY:
+        N = y.shape[-1] if minibatch is None else int(size_of_minibatch)
+        _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, D.shape[0], D.shape[1], N, stride, padding,
+                     _arrays.np_dtype(y))
     import torch
     kind = 'torch' if _arrays.is_torch(y) else 'numpy'
     yd = _arrays.to_device(y)
@@ -225,17 +243,10 @@ def pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME', posi
     from . import omp
     kind, stride, T, S, N, C = _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding)
     tol_c = omp.check_tol(tol)
-    if n_nonzero_coefs is None:
-        n_steps = T * C
-    elif not _is_int(n_nonzero_coefs) or not 1 <= int(n_nonzero_coefs) <= T * C:
-        raise ValueError('n_nonzero_coefs must be an integer in [1, T C = {0:d}]. Given {1!r}'.format(
-            T * C, n_nonzero_coefs))
-    else:
-        n_steps = int(n_nonzero_coefs)
+    n_steps = _pursuit_steps(n_nonzero_coefs, T, C)
     if not isinstance(positive, (bool, np.bool_)):
         raise ValueError('positive must be a bool. Given {0!r}'.format(positive))
-    if positive and _arrays.np_dtype(y).kind == 'c':
-        raise ValueError('positive=True needs a real dtype.')
+    _check_positive(positive, _arrays.np_dtype(y))
 
     return _pursuit_call('pursuit', kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c, 1 if positive else 0)
 
@@ -262,17 +273,47 @@ def orthogonal_pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='
     from . import omp
     kind, stride, T, S, N, C = _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding)
     tol_c = omp.check_tol(tol)
-    dt = _arrays.np_dtype(y)
+    n_steps = _orthogonal_steps(n_nonzero_coefs, T, C, _arrays.np_dtype(y))
+    return _pursuit_call('omp', kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c)
+
+
+def _pursuit_steps(n_nonzero_coefs, T, C):
+    """The step limit of ``pursuit``: n_nonzero_coefs in [1, T C] (None: T C)."""
+    if n_nonzero_coefs is None:
+        return T * C
+    if not _is_int(n_nonzero_coefs) or not 1 <= int(n_nonzero_coefs) <= T * C:
+        raise ValueError('n_nonzero_coefs must be an integer in [1, T C = {0:d}]. Given {1!r}'.format(
+            T * C, n_nonzero_coefs))
+    return int(n_nonzero_coefs)
+
+
+def _check_positive(positive, dt):
+    if positive and np.dtype(dt).kind == 'c':
+        raise ValueError('positive=True needs a real dtype.')
+
+
+def _orthogonal_steps(n_nonzero_coefs, T, C, dt):
+    """The step limit of ``orthogonal_pursuit``: n_nonzero_coefs in [1, min(T C, cap)] (None: the largest)."""
+    from . import omp
     most = min(T * C, omp.sparsity_cap(dt))
     if n_nonzero_coefs is None:
-        n_steps = most
-    elif not _is_int(n_nonzero_coefs) or not 1 <= int(n_nonzero_coefs) <= most:
+        return most
+    if not _is_int(n_nonzero_coefs) or not 1 <= int(n_nonzero_coefs) <= most:
         raise ValueError('n_nonzero_coefs must be an integer in [1, min(T C = {0:d}, {1:d})] (the cap is {2:d} for '
                          'real and {3:d} for complex dtypes). Given {4!r}'.format(
                              T * C, omp.sparsity_cap(dt), omp.CAP_REAL, omp.CAP_COMPLEX, n_nonzero_coefs))
-    else:
-        n_steps = int(n_nonzero_coefs)
-    return _pursuit_call('omp', kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c)
+    return int(n_nonzero_coefs)
+
+
+def _geometry(T, S, N, stride, padding):
+    """(stride, C) of templates [T, S] on signals of N samples, or ValueError."""
+    if padding not in ('SAME', 'VALID'):
+        raise ValueError("padding must be 'SAME' or 'VALID'. Given {0!r}".format(padding))
+    if not _is_int(stride) or int(stride) < 1:
+        raise ValueError('stride must be a positive integer. Given {0!r}'.format(stride))
+    if T < 1 or S < 1 or S > N:
+        raise ValueError('templates [{0:d}, {1:d}] need 1 <= T and 1 <= S <= N = {2:d}'.format(T, S, N))
+    return int(stride), _coef_size(S, N, stride=int(stride), padding=padding)
 
 
 def _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding):
@@ -282,18 +323,33 @@ def _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding):
     assertion.assert_ndim('D', D, ndim=2)
     if len(y.shape) < 1:
         raise assertion.DimInvalidError('y must have at least 1 dimension')
-    if padding not in ('SAME', 'VALID'):
-        raise ValueError("padding must be 'SAME' or 'VALID'. Given {0!r}".format(padding))
-    if not _is_int(stride) or int(stride) < 1:
-        raise ValueError('stride must be a positive integer. Given {0!r}'.format(stride))
-    stride = int(stride)
     T, S = int(D.shape[0]), int(D.shape[1])
     N = int(y.shape[-1])
-    if T < 1 or S < 1 or S > N:
-        raise ValueError('templates [{0:d}, {1:d}] need 1 <= T and 1 <= S <= N = {2:d}'.format(T, S, N))
+    stride, C = _geometry(T, S, N, stride, padding)
     if n_nonzero_coefs is None and tol is None:
         raise ValueError('Either n_nonzero_coefs or tol must be given.')
-    return kind, stride, T, S, N, _coef_size(S, N, stride=stride, padding=padding)
+    return kind, stride, T, S, N, C
+
+
+def _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, T, S, N, stride, padding, dt):
+    """``solve`` with a greedy coder (lasso_method in _GREEDY) on signals (or windows) of N samples: alpha must be 0,
+    lasso_iter is the coder's n_nonzero_coefs and lasso_tol its tol, each checked by the coder's own rule.  No GPU
+    call.  Returns (n_steps, tol as the library takes it, max_events of the dictionary step)."""
+    from . import omp
+    if not (isinstance(alpha, (int, float, np.integer, np.floating)) and alpha == 0):
+        raise ValueError('lasso_method={0!r} solves the sparsity-constrained problem, which has no L1 penalty: '
+                         'alpha must be 0. Given {1!r}'.format(lasso_method, alpha))
+    stride, C = _geometry(int(T), int(S), int(N), stride, padding)
+    if lasso_iter is None and lasso_tol is None:
+        raise ValueError('Either lasso_iter (the n_nonzero_coefs of {0!r}) or lasso_tol (its tol) must be '
+                         'given.'.format(lasso_method))
+    tol_c = omp.check_tol(lasso_tol)
+    if lasso_method == 'omp':
+        n_steps = _orthogonal_steps(lasso_iter, T, C, dt)
+    else:
+        n_steps = _pursuit_steps(lasso_iter, T, C)
+        _check_positive(lasso_method == 'mp_pos', dt)
+    return n_steps, tol_c, min(n_steps, C)
 
 
 def _pursuit_call(name, kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c, *flags):
@@ -350,6 +406,44 @@ def _dstep(y, x, D, XXt, yX, stride, padding, acc_it):
     return out.value
 
 
+def _dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events):
+    """``_dstep`` for a sparse x: the statistics are summed over lists of at most ``max_events`` non-zeros per
+    (signal, template) row (a row with more is walked in full).  The same bits as ``_dstep``; y and x finite."""
+    B, N = y.shape
+    T, S = D.shape
+    out = ctypes.c_double(0.0)
+    _call(y, 'dstep_events', y, x, D, XXt, yX,
+          B, T, S, N, stride, _pad_code(padding), int(acc_it), int(max_events), ctypes.byref(out))
+    return out.value
+
+
+def _steps(N, D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol):
+    """The two halves of an outer iteration on signals of N samples, (code(y, D, x), dstep(y, x, D, XXt, yX, acc_it)):
+    the LASSO solver and the dense dictionary step, or for a greedy lasso_method its coder, which writes x entirely,
+    and the dictionary step on event lists."""
+    if lasso_method not in _GREEDY:
+        def code(y, D, x):
+            _lasso(y, D, x, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
+
+        def dstep(y, x, D, XXt, yX, acc_it):
+            return _dstep(y, x, D, XXt, yX, stride, padding, acc_it)
+        return code, dstep
+    T, S = D.shape
+    n_steps, tol_c, max_events = _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, T, S, N, stride, padding,
+                                              _arrays.np_dtype(D))
+    name, flags = _GREEDY[lasso_method]
+    stride = int(stride)
+
+    def code(y, D, x):
+        it = ctypes.c_int(0)
+        _call(y, name, y, D, x, y.shape[0], T, S, N, stride, _pad_code(padding), n_steps, tol_c,
+              *(flags + (ctypes.byref(it),)))
+
+    def dstep(y, x, D, XXt, yX, acc_it):
+        return _dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events)
+    return code, dstep
+
+
 def _device_args(y, D, x):
     assertion.assert_dtypes(y=y, D=D, x=x)
     kind = 'torch' if _arrays.is_torch(y) else 'numpy'
@@ -377,11 +471,13 @@ def solve_batch(y, D, alpha, x, stride, padding, tol, maxiter,
                 lasso_method, lasso_iter, lasso_tol, xp):
     """
     Alternates, on the whole batch y [B, N]:
-      x <- the LASSO solution of y = x * D (lasso_iter iterations of lasso_method from the current x);
+      x <- the LASSO solution of y = x * D (lasso_iter iterations of lasso_method from the current x), or the code
+           of the greedy coder ('omp', 'mp', 'mp_pos': at most lasso_iter events per signal, from zero);
       D <- l2(D + (yX - XXt D) / L), one gradient step on the templates.
     Stops when max|dD| < tol.  D is normalised (strictly) once at entry.
     """
     import torch
+    code, dstep = _steps(y.shape[-1], D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
     kind, y, D, x = _device_args(y, D, x)
     D = normalize.l2_strict(D, axis=-1)
     T, S = D.shape
@@ -390,8 +486,8 @@ def solve_batch(y, D, alpha, x, stride, padding, tol, maxiter,
     for it in range(1, maxiter):
         Dprev = D.clone()
         try:
-            _lasso(y, D, x, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
-            diff = _dstep(y, x, D, XXt, yX, stride, padding, 0)
+            code(y, D, x)
+            diff = dstep(y, x, D, XXt, yX, 0)
             if diff < tol:
                 return it, _arrays.to_caller(D, kind), _arrays.to_caller(x, kind)
         except KeyboardInterrupt:
@@ -450,9 +546,11 @@ def solve_minibatch(y, D, alpha, x, stride, padding, tol,
     window's coefficients are the slice x[b, :, start:start + _coef_size(S, size_of_minibatch)] and
     are written back in draw order (so with stride > 1 a window can run past the coefficients: ValueError,
     as in the reference, see _draw_windows).  The statistics are accumulated as XXt_sum += XXt / it,
-    yX_sum += yX / it (it = 1, 2, ...).  Returns the full x.
+    yX_sum += yX / it (it = 1, 2, ...).  Returns the full x.  A greedy coder codes every window from zero, with at
+    most lasso_iter events per window.
     """
     import torch
+    code, dstep = _steps(int(size_of_minibatch), D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
     kind, y, D, x = _device_args(y, D, x)
     D = normalize.l2_strict(D, axis=-1)
     B, N = y.shape
@@ -473,10 +571,10 @@ def solve_minibatch(y, D, alpha, x, stride, padding, tol,
             inn = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int64)).to(y.device)
             _call(y, 'gather_windows', y, x, ib, inn, m,
                   B, T, S, N, w, stride, _pad_code(padding), yw, xw)
-            _lasso(yw, D, xw, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
+            code(yw, D, xw)
             _call(y, 'scatter_windows', xw, x, ib, inn, m,
                   B, T, S, N, w, stride, _pad_code(padding))
-            diff = _dstep(yw, xw, D, XXt_sum, yX_sum, stride, padding, it)
+            diff = dstep(yw, xw, D, XXt_sum, yX_sum, it)
             if diff < tol:
                 return it, _arrays.to_caller(D, kind), _arrays.to_caller(x, kind)
         except KeyboardInterrupt:

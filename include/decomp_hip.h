@@ -882,6 +882,15 @@ int dcp_tm_dstep_f32(dcp_handle* h, const void* Y, const void* X, void* D, void*
 int dcp_tm_dstep_f64(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, double* maxdiff);
 int dcp_tm_dstep_c64(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, double* maxdiff);
 int dcp_tm_dstep_c128(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, double* maxdiff);
+/* dcp_tm_dstep_* for sparse X (the codes of dcp_tm_pursuit_* / dcp_tm_omp_*): same outputs, same acc_it, same single
+ * synchronisation, bit for bit the same result; the statistics are summed over per-row lists of the non-zeros of X.
+ * max_events >= 1 bounds the list of a (signal, template) row; a row with more non-zeros is walked in full, so the
+ * bound decides the speed, never the result.  X and Y must be finite.  With dcp_profile_* on, both steps time their
+ * statistics kernels under DCP_PROF_STATS and, inside that, the partial sums the lists replace under DCP_PROF_MISC. */
+int dcp_tm_dstep_events_f32(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, int64_t max_events, double* maxdiff);
+int dcp_tm_dstep_events_f64(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, int64_t max_events, double* maxdiff);
+int dcp_tm_dstep_events_c64(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, int64_t max_events, double* maxdiff);
+int dcp_tm_dstep_events_c128(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, int64_t max_events, double* maxdiff);
 int dcp_tm_gather_windows_f32(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
 int dcp_tm_gather_windows_f64(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
 int dcp_tm_gather_windows_c64(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
