@@ -275,6 +275,26 @@ SIGNATURES = {
     'dcp_tm_omp_lds_atoms_f64': (_c_int, []),
     'dcp_tm_omp_lds_atoms_c64': (_c_int, []),
     'dcp_tm_omp_lds_atoms_c128': (_c_int, []),
+    'dcp_tm_mc_pursuit_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_tm_mc_pursuit_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_tm_mc_pursuit_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_tm_mc_pursuit_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
+    'dcp_tm_mc_omp_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
+    'dcp_tm_mc_omp_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
+    'dcp_tm_mc_omp_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
+    'dcp_tm_mc_omp_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
+    'dcp_tm_mc_predict_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
+    'dcp_tm_mc_predict_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
+    'dcp_tm_mc_predict_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
+    'dcp_tm_mc_predict_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
+    'dcp_tm_mc_template_block_f32': (_c_int, []),
+    'dcp_tm_mc_template_block_f64': (_c_int, []),
+    'dcp_tm_mc_template_block_c64': (_c_int, []),
+    'dcp_tm_mc_template_block_c128': (_c_int, []),
+    'dcp_tm_mc_channels_per_pass_f32': (_c_int, [_c_i64, _c_i64]),
+    'dcp_tm_mc_channels_per_pass_f64': (_c_int, [_c_i64, _c_i64]),
+    'dcp_tm_mc_channels_per_pass_c64': (_c_int, [_c_i64, _c_i64]),
+    'dcp_tm_mc_channels_per_pass_c128': (_c_int, [_c_i64, _c_i64]),
 }
 
 _lib = None

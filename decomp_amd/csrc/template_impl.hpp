@@ -34,6 +34,7 @@ DCP_HD long tm_ceil_div(long a, long b) { return -tm_floor_div(-a, b); }
 struct TmGeom {
     long B = 1, T = 0, S = 0, N = 0, C = 0, s = 1, Q = 0;
     long dh = 0;   // largest |lag| in units of c: floor((S - 1) / s)
+    long Ch = 1;   // channels of a template (D [T, Ch, S], y [B, Ch, N]): honoured by the greedy coders' kernels alone
     DCP_HD long nd() const { return 2 * dh + 1; }
     // c of the coefficients whose taps cover sample n: [c_first(n), c_last(n)] (clipped to [0, C))
     DCP_HD long c_first(long n) const { long c = tm_ceil_div(n + Q - S + 1, s); return c < 0 ? 0 : c; }
@@ -765,6 +766,7 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
 
 }  // namespace dcp
 
+#include "template_multichannel.hpp"   // the correlation pass, prepare and predict for templates D [T, Ch, S]
 #include "template_pursuit.hpp"   // matching pursuit on the same operator
 #include "template_omp.hpp"       // orthogonal (re-fitting) pursuit on the same operator
 #include "template_events.hpp"    // the dictionary step from event lists, for the codes of those two
@@ -776,6 +778,13 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
     if (!dcp::tm_geom(g, B, T_, S, N, stride, padding))                                             \
         return dcp::fail(h, DCP_ERR_INVALID, "template geometry: need 0 < S <= N, stride > 0, C > 0"); \
     DCP_HIP_OK(h, hipSetDevice((h)->device))
+
+// the geometry of one channel, then Ch
+#define DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding)                             \
+    DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                        \
+    if ((Ch) < 1 || (Ch) > 0x7fffffffLL)                                                            \
+        return dcp::fail(h, DCP_ERR_INVALID, "multichannel templates: need 1 <= Ch < 2^31");        \
+    g.Ch = (Ch)
 
 #define DCP_TM_DEFINE(SFX, TYPE)                                                                              \
     extern "C" int dcp_tm_temp2mat_##SFX(dcp_handle* h, const void* D, int64_t T_, int64_t S, int64_t N,       \
@@ -840,6 +849,32 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
         return dcp::tm_omp_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol, it_out);    \
     }                                                                                                          \
     extern "C" int dcp_tm_omp_lds_atoms_##SFX(void) { return (int)dcp::tm_omp_lds_atoms<TYPE>(); }            \
+    extern "C" int dcp_tm_mc_pursuit_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,   \
+                                            int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,      \
+                                            int padding, int64_t n_steps, double tol, int positive,            \
+                                            int* it_out) {                                                     \
+        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
+        return dcp::tm_pursuit_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol,         \
+                                         positive, it_out, true);                                              \
+    }                                                                                                          \
+    extern "C" int dcp_tm_mc_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,       \
+                                        int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,          \
+                                        int padding, int64_t n_steps, double tol, int* it_out) {               \
+        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
+        return dcp::tm_omp_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol, it_out,     \
+                                     true);                                                                    \
+    }                                                                                                          \
+    extern "C" int dcp_tm_mc_predict_##SFX(dcp_handle* h, const void* X, const void* D, int64_t B,            \
+                                            int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,      \
+                                            int padding, void* out) {                                          \
+        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
+        if (!X || !D || !out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                            \
+        return dcp::tm_mc_predict<TYPE>(h, (const TYPE*)X, (const TYPE*)D, g, (TYPE*)out);                     \
+    }                                                                                                          \
+    extern "C" int dcp_tm_mc_template_block_##SFX(void) { return dcp::tm_mc_template_block<TYPE>(); }         \
+    extern "C" int dcp_tm_mc_channels_per_pass_##SFX(int64_t S, int64_t stride) {                             \
+        return dcp::tm_mc_channels_per_pass<TYPE>(S, stride);                                                  \
+    }                                                                                                          \
     extern "C" int dcp_tm_dstep_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt,        \
                                        void* yX, int64_t B, int64_t T_, int64_t S, int64_t N, int64_t stride, \
                                        int padding, int acc_it, double* maxdiff) {                             \

@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
     for (int i = tid; i < nseg; i += NT) taken[i] = 0ull;
     T* x = X + b * K;
     for (int i = tid; i < K; i += NT) x[i] = zero_of<T>();
-    const R yn2 = tm_pursuit_ynorm2(Y + b * g.N, g.N, shS, &shE);
+    const R yn2 = tm_pursuit_ynorm2(Y + b * g.Ch * g.N, g.Ch * g.N, shS, &shE);
     int n = 0;   // the support size
     for (int seg = wave; seg < nseg; seg += NW) tm_pursuit_segment(al, rho2, K, seg, 0, tm_omp_taken(taken, seg), tab);
     __syncthreads();
@@ -270,10 +270,11 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_omp_kernel(const T* __re
     if (tid == 0 && n > 0) atomicMax(it_max, n);
 }
 
-// Y [B, N], D [T, S] -> X [B, T, C]; *it_out = the largest support a signal reached.  Synchronises the stream.
+// Y [B, N], D [T, S] (mc: Y [B, Ch, N], D [T, Ch, S]) -> X [B, T, C]; *it_out = the largest support a signal reached.
+// Synchronises the stream.
 template <class T>
 inline int tm_omp_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int n_steps, double tol,
-                        int* it_out) {
+                        int* it_out, bool mc) {
     typedef real_t<T> R;
     hipStream_t st = h->stream;
     const long K = g.T * g.C, nseg = tm_pursuit_nseg(K);
@@ -294,7 +295,7 @@ inline int tm_omp_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeo
         a.take(taken, lds ? 0 : g.B * nseg);
         a.take(it_dev, 4);
     }));
-    DCP_TRY(tm_pursuit_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev));
+    DCP_TRY(tm_pursuit_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev, mc));
     const R t = tol >= 0.0 ? (R)tol : R(-1);
     const size_t bytes = TmOmpCarve<T>(n_steps, K, lds).bytes;
     DCP_LAUNCH_OK(h, (tm_pursuit_launch<&tm_omp_kernel<T, true>, &tm_omp_kernel<T, false>>(
@@ -305,13 +306,13 @@ inline int tm_omp_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeo
 
 template <class T>
 inline int tm_omp_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
-                      int* it_out) {
+                      int* it_out, bool mc = false) {
     if (!Y || !D || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
     const int64_t K = (int64_t)g.T * g.C;
     if (K > 0x7fffff00LL) return fail(h, DCP_ERR_INVALID, "orthogonal pursuit: T C exceeds 2^31 - 257");
     DCP_TRY(omp_check_sparsity(h, K, n_steps, omp_cap<T>(), "orthogonal pursuit: n_steps", "T C"));
     if (tol != tol) return fail(h, DCP_ERR_INVALID, "orthogonal pursuit: tol is NaN");
-    return tm_omp_solve<T>(h, Y, D, X, g, (int)n_steps, tol, it_out);
+    return tm_omp_solve<T>(h, Y, D, X, g, (int)n_steps, tol, it_out, mc);
 }
 
 }  // namespace dcp

@@ -43,6 +43,11 @@
 // The pieces orthogonal pursuit (template_omp.hpp) runs on as well are defined here once: the prepare launches, the
 // segment table with its `excluded` lanes, the table's best atom, |y|^2, the window of an atom, the Gram entry and the
 // launch of a tier.
+//
+// Multichannel templates (D [T, Ch, S], y [B, Ch, N], one coefficient per event for all channels; dcp_tm_mc_*): a step
+// reads y only through alpha0, rho2, Corr, the explicit overlap sum and |y|^2, so TmGeom::Ch (1 everywhere else) adds a
+// channel loop to the last two here, and tm_pursuit_prepare(mc) takes the first three from template_multichannel.hpp.
+// With Ch = 1 every loop is the one it was.
 #pragma once
 #include "greedy.hpp"
 
@@ -185,8 +190,8 @@ DCP_HD c128 tm_madd_conj(c128 acc, c128 a, c128 b) {
 }
 
 // G[(t, c), (tp, cp)] = A_(t,c) . A_(tp,cp)^H over the samples inside [0, N): Corr when atom (t, c) lies inside the
-// signal (inside = tm_pursuit_inside(g, c), hoisted by the caller), else the explicit sum; an exact zero when the
-// atoms do not overlap
+// signal (inside = tm_pursuit_inside(g, c), hoisted by the caller), else the explicit sum, over the g.Ch channels of
+// D [T, Ch, S] (ch ascending, k ascending inside); an exact zero when the atoms do not overlap
 template <class T>
 __device__ __forceinline__ T tm_pursuit_gram(const T* __restrict__ D, const T* __restrict__ corr, const TmGeom& g, int t,
                                              int c, bool inside, int tp, int cp) {
@@ -198,7 +203,10 @@ __device__ __forceinline__ T tm_pursuit_gram(const T* __restrict__ D, const T* _
     if (k0 < -bj) k0 = -bj;
     if (k1 > g.N - 1 - bj) k1 = g.N - 1 - bj;
     T G = zero_of<T>();
-    for (long k = k0; k <= k1; ++k) G = tm_madd_conj(G, D[t * g.S + k], D[tp * g.S + k + m]);
+    for (long ch = 0; ch < g.Ch; ++ch) {
+        const long dt = (t * g.Ch + ch) * g.S, dp = (tp * g.Ch + ch) * g.S + m;
+        for (long k = k0; k <= k1; ++k) G = tm_madd_conj(G, D[dt + k], D[dp + k]);
+    }
     return G;
 }
 
@@ -233,7 +241,7 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_pursuit_kernel(const T* 
     }
     T* x = X + b * K;
     for (int i = tid; i < K; i += NT) x[i] = zero_of<T>();
-    R E = tm_pursuit_ynorm2(Y + b * g.N, g.N, shS, &shE);
+    R E = tm_pursuit_ynorm2(Y + b * g.Ch * g.N, g.Ch * g.N, shS, &shE);
     for (int seg = wave; seg < nseg; seg += NW) tm_pursuit_segment(al, rho2, K, seg, positive, false, tab);
     __syncthreads();
 
@@ -285,10 +293,12 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_pursuit_kernel(const T* 
 }
 
 // The prepare launches of the greedy coders: rho2 [K], the lag correlations corr [T, T, 2 S - 1], alpha0 = y A^H
-// [B, K]; clears *it_dev
+// [B, K]; clears *it_dev.  mc: D is [T, g.Ch, S] and y [B, g.Ch, N], by the kernels of template_multichannel.hpp
+// (for every Ch, 1 included).
 template <class T>
 inline int tm_pursuit_prepare(dcp_handle* h, const T* Y, const T* D, const TmGeom& g, real_t<T>* rho2, T* corr,
-                              T* alpha0, int* it_dev) {
+                              T* alpha0, int* it_dev, bool mc) {
+    if (mc) return tm_mc_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev);
     hipStream_t st = h->stream;
     const long K = g.T * g.C;
     hipLaunchKernelGGL((tm_pursuit_rho2_kernel<T>), dim3(tm_grid(K)), dim3(256), 0, st, D, g, rho2, it_dev);
@@ -296,6 +306,7 @@ inline int tm_pursuit_prepare(dcp_handle* h, const T* Y, const T* D, const TmGeo
     hipLaunchKernelGGL((tm_lagcorr_kernel<T>), dim3(g.T * g.T), dim3(256), 0, st, D, g, corr);
     DCP_LAUNCH_OK(h, hipGetLastError());
     {   // alpha0, the batch in slices of at most 65535 signals (the grid's z extent)
+        ProfScope ps(h, DCP_PROF_XUPDATE);
         const long span = 255 * g.s + g.S;
         size_t bytes = (size_t)(g.S + span) * sizeof(T);
         const int lds_ok = bytes <= kTmLdsBytes;
@@ -330,10 +341,11 @@ inline hipError_t tm_pursuit_launch(hipStream_t st, long B, bool lds, size_t byt
     return hipGetLastError();
 }
 
-// Y [B, N], D [T, S] -> X [B, T, C]; *it_out = the largest number of steps a signal took.  Synchronises the stream.
+// Y [B, N], D [T, S] (mc: Y [B, Ch, N], D [T, Ch, S]) -> X [B, T, C]; *it_out = the largest number of steps a signal
+// took.  Synchronises the stream.
 template <class T>
 inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
-                            int positive, int* it_out) {
+                            int positive, int* it_out, bool mc) {
     typedef real_t<T> R;
     hipStream_t st = h->stream;
     const long K = g.T * g.C, nseg = tm_pursuit_nseg(K);
@@ -350,7 +362,7 @@ inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const T
         a.take(tab, lds ? 0 : g.B * nseg);
         a.take(it_dev, 4);
     }));
-    DCP_TRY(tm_pursuit_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev));
+    DCP_TRY(tm_pursuit_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev, mc));
     const R t = tol >= 0.0 ? (R)tol : R(-1);
     DCP_LAUNCH_OK(h, (tm_pursuit_launch<&tm_pursuit_kernel<T, true>, &tm_pursuit_kernel<T, false>>(
                          st, g.B, lds, lds ? tm_pursuit_lds_bytes<T>(K) : 0,
@@ -361,7 +373,7 @@ inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const T
 
 template <class T>
 inline int tm_pursuit_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
-                          int positive, int* it_out) {
+                          int positive, int* it_out, bool mc = false) {
     if (!Y || !D || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
     const int64_t K = (int64_t)g.T * g.C;
     if (K > 0x7fffff00LL) return fail(h, DCP_ERR_INVALID, "pursuit: T C exceeds 2^31 - 257");
@@ -369,7 +381,7 @@ inline int tm_pursuit_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmG
     if (tol != tol) return fail(h, DCP_ERR_INVALID, "pursuit: tol is NaN");
     if (positive && scalar_traits<T>::is_complex)
         return fail(h, DCP_ERR_INVALID, "pursuit: positive needs a real dtype");
-    return tm_pursuit_solve<T>(h, Y, D, X, g, n_steps, tol, positive, it_out);
+    return tm_pursuit_solve<T>(h, Y, D, X, g, n_steps, tol, positive, it_out, mc);
 }
 
 }  // namespace dcp

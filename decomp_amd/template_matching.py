@@ -19,7 +19,10 @@ size is formed on the hot path (include/decomp_hip.h ``dcp_tm_*``, decomp_amd/cs
   * ``solve(alpha=0, lasso_method='omp' | 'mp' | 'mp_pos', lasso_iter=s, lasso_tol=tol)`` learns the templates for
     the codes of those two coders: the coder replaces the LASSO step, and the dictionary step sums its statistics over
     per-row lists of the non-zero coefficients instead of all C of them, bit for bit the dense step's result
-    (``dcp_tm_dstep_events_*``, decomp_amd/csrc/template_events.hpp).
+    (``dcp_tm_dstep_events_*``, decomp_amd/csrc/template_events.hpp);
+  * ``pursuit``, ``orthogonal_pursuit`` and ``predict`` take multichannel templates D [T, Ch, S] (y [..., Ch, N], one
+    coefficient per event for all channels): every correlation, rho2 and |y|^2 gains a sum over the channels, the
+    correlation pass is a kernel of its own (``dcp_tm_mc_*``, decomp_amd/csrc/template_multichannel.hpp).
 
 'cd', 'parallel_cd' and 'admm' have no structured form: for them ``_temp2mat`` is materialised on the
 device and the dense ``dcp_lasso_*`` solvers of decomp_amd.lasso run on it.  That path is correct but
@@ -200,16 +203,18 @@ def _coef2mat(x_orig, size, template_size, stride, padding, xp=None):
 
 
 def predict(x, D, size, stride=1, padding='SAME'):
-    """The signal x * D: x [..., T, C], D [T, S] -> [..., size] (mixed dtypes compute in the promoted one)."""
+    """The signal x * D: x [..., T, C], D [T, S] -> [..., size], or with multichannel templates D [T, Ch, S]
+    -> [..., Ch, size] (mixed dtypes compute in the promoted one)."""
     import torch
     kind = get_array_module(x, D)
+    Ch = _channels(D)
     xd = _arrays.to_device(x)
     Dd = _arrays.to_device(D, xd.device.index)
     _same_device(xd, Dd)
     # mixed dtypes compute in the promoted one, as the reference's tensordot does
     dt = torch.promote_types(xd.dtype, Dd.dtype)
     xd, Dd = xd.to(dt).contiguous(), Dd.to(dt).contiguous()
-    T, S = Dd.shape
+    T, S = int(Dd.shape[0]), int(Dd.shape[-1])
     C = _coef_size(S, size, stride, padding)
     if tuple(xd.shape[-2:]) != (T, C):
         raise ValueError('shape-mismatch for sum: x%s with templates [%d, %d] over %d samples'
@@ -217,6 +222,11 @@ def predict(x, D, size, stride=1, padding='SAME'):
     lead = tuple(xd.shape[:-2])
     x3 = xd.reshape((-1, T, C))
     B = x3.shape[0]
+    if Ch is not None:
+        out = torch.empty((B, Ch, size), dtype=xd.dtype, device=xd.device)
+        if B > 0:
+            _call(x3, 'mc_predict', x3, Dd, B, T, Ch, S, size, stride, _pad_code(padding), out)
+        return _arrays.to_caller(out.reshape(lead + (Ch, size)), kind)
     out = torch.empty((B, size), dtype=xd.dtype, device=xd.device)
     _call(x3, 'predict', x3, Dd, B, T, S, size, stride, _pad_code(padding),
           out)
@@ -236,19 +246,23 @@ def pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME', posi
     This is matching pursuit, not OMP: there is no re-fit on the support, and an atom may be taken again (its
     coefficient accumulates), so ``n_nonzero_coefs`` bounds the STEPS and hence the non-zeros.  There is no sparsity
     cap; with ``tol`` alone the step limit is T C.
+    Multichannel templates: a 3-D D [T, Ch, S] codes y [..., Ch, N] with one coefficient per event for all Ch channels,
+    y[ch, n] ~ sum x[t, c] D[t, ch, n - stride c + Q]; correlations, rho2 and the residual energy (hence ``tol``) are
+    sums over all channels, everything else is unchanged (``dcp_tm_mc_pursuit_*``, Ch = 1 included).
     Returns (it, x): x [..., T, C] in the layout of ``solve`` / ``predict`` (``predict(x, D, N, stride, padding)`` is
     the approximation), it the largest number of steps any signal took.  NumPy in -> NumPy out; torch GPU tensors
     stay on the device.  Runs in libdecomp_hip.so (``dcp_tm_pursuit_*``, decomp_amd/csrc/template_pursuit.hpp).
     """
     from . import omp
-    kind, stride, T, S, N, C = _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding)
+    kind, stride, T, S, N, C, Ch = _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding)
     tol_c = omp.check_tol(tol)
     n_steps = _pursuit_steps(n_nonzero_coefs, T, C)
     if not isinstance(positive, (bool, np.bool_)):
         raise ValueError('positive must be a bool. Given {0!r}'.format(positive))
     _check_positive(positive, _arrays.np_dtype(y))
 
-    return _pursuit_call('pursuit', kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c, 1 if positive else 0)
+    return _pursuit_call('pursuit', kind, y, D, T, S, N, C, Ch, stride, padding, n_steps, tol_c,
+                         1 if positive else 0)
 
 
 def orthogonal_pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME'):
@@ -265,16 +279,17 @@ def orthogonal_pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='
     or the best atom is numerically in the span of the support (its Cholesky pivot is <= 4096 eps rho2).
     ``n_nonzero_coefs`` is an integer in [1, min(T C, cap)], cap = 64 for real and 32 for complex dtypes (that of
     ``omp.solve``); with ``tol`` alone the limit is min(T C, cap).  Longer recordings are coded in windows.
+    Multichannel templates: a 3-D D [T, Ch, S] codes y [..., Ch, N] as in ``pursuit`` (``dcp_tm_mc_omp_*``).
     Returns (it, x): x [..., T, C] in the layout of ``solve`` / ``predict`` / ``pursuit``, it the largest support any
     signal reached.  NumPy in -> NumPy out; torch GPU tensors stay on the device.  The dense operator and its Gram
     matrix are never formed: the Gram entries are read from the lag correlations of the templates
     (``dcp_tm_omp_*``, decomp_amd/csrc/template_omp.hpp).
     """
     from . import omp
-    kind, stride, T, S, N, C = _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding)
+    kind, stride, T, S, N, C, Ch = _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding)
     tol_c = omp.check_tol(tol)
     n_steps = _orthogonal_steps(n_nonzero_coefs, T, C, _arrays.np_dtype(y))
-    return _pursuit_call('omp', kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c)
+    return _pursuit_call('omp', kind, y, D, T, S, N, C, Ch, stride, padding, n_steps, tol_c)
 
 
 def _pursuit_steps(n_nonzero_coefs, T, C):
@@ -317,18 +332,33 @@ def _geometry(T, S, N, stride, padding):
 
 
 def _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding):
-    """The argument checks the greedy coders share, before any GPU call: (kind, stride, T, S, N, C)."""
+    """The argument checks the greedy coders share, before any GPU call: (kind, stride, T, S, N, C, Ch), Ch None for
+    templates [T, S] and the number of channels for templates [T, Ch, S] (y [..., Ch, N])."""
     kind = get_array_module(y, D)
     assertion.assert_dtypes(y=y, D=D)
-    assertion.assert_ndim('D', D, ndim=2)
-    if len(y.shape) < 1:
-        raise assertion.DimInvalidError('y must have at least 1 dimension')
-    T, S = int(D.shape[0]), int(D.shape[1])
+    Ch = _channels(D)
+    if len(y.shape) < (1 if Ch is None else 2):
+        raise assertion.DimInvalidError('y must have at least %d dimension%s' % ((1, '') if Ch is None else (2, 's')))
+    if Ch is not None and int(y.shape[-2]) != Ch:
+        raise assertion.DimInvalidError('y{0} must be [..., Ch, N] with the Ch = {1:d} channels of the templates '
+                                        'D{2}'.format(tuple(y.shape), Ch, tuple(D.shape)))
+    T, S = int(D.shape[0]), int(D.shape[-1])
     N = int(y.shape[-1])
     stride, C = _geometry(T, S, N, stride, padding)
     if n_nonzero_coefs is None and tol is None:
         raise ValueError('Either n_nonzero_coefs or tol must be given.')
-    return kind, stride, T, S, N, C
+    return kind, stride, T, S, N, C, Ch
+
+
+def _channels(D):
+    """None for templates [T, S], Ch >= 1 for multichannel templates [T, Ch, S]; anything else raises."""
+    if len(D.shape) == 2:
+        return None
+    if len(D.shape) != 3:
+        raise assertion.DimInvalidError('D must have 2 ([T, S]) or 3 ([T, Ch, S]) dimensions, has %d' % len(D.shape))
+    if int(D.shape[1]) < 1:
+        raise ValueError('multichannel templates [T, Ch, S] need Ch >= 1. Given D{0}'.format(tuple(D.shape)))
+    return int(D.shape[1])
 
 
 def _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, T, S, N, stride, padding, dt):
@@ -352,17 +382,26 @@ def _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, T, S, N, stride, pa
     return n_steps, tol_c, min(n_steps, C)
 
 
-def _pursuit_call(name, kind, y, D, T, S, N, C, stride, padding, n_steps, tol_c, *flags):
-    """dcp_tm_<name>_* on the signals of y, flattened to [B, N]: (it, x [..., T, C])."""
+def _pursuit_call(name, kind, y, D, T, S, N, C, Ch, stride, padding, n_steps, tol_c, *flags):
+    """dcp_tm_<name>_* on the signals of y, flattened to [B, N], or with Ch channels (not None) dcp_tm_mc_<name>_* on
+    y flattened to [B, Ch, N]: (it, x [..., T, C])."""
     import torch
     yd = _arrays.to_device(y)
     Dd = _arrays.to_device(D, yd.device.index).contiguous()
     _same_device(yd, Dd)
-    lead = tuple(yd.shape[:-1])
-    y2 = yd.reshape(-1, N).contiguous()
-    B = y2.shape[0]
     it = ctypes.c_int(0)
-    if B > 0:
+    if Ch is None:
+        lead = tuple(yd.shape[:-1])
+        y2 = yd.reshape(-1, N).contiguous()
+    else:
+        lead = tuple(yd.shape[:-2])
+        y2 = yd.reshape(-1, Ch, N).contiguous()
+    B = y2.shape[0]
+    if B > 0 and Ch is not None:
+        xd = torch.empty((B, T, C), dtype=yd.dtype, device=yd.device)
+        _call(y2, 'mc_' + name, y2, Dd, xd, B, T, Ch, S, N, stride, _pad_code(padding), n_steps, tol_c,
+              *(flags + (ctypes.byref(it),)))
+    elif B > 0:
         xd = torch.empty((B, T, C), dtype=yd.dtype, device=yd.device)
         _call(y2, name, y2, Dd, xd, B, T, S, N, stride, _pad_code(padding), n_steps, tol_c, *(flags + (ctypes.byref(it),)))
     else:

@@ -915,6 +915,37 @@ int dcp_tm_omp_lds_atoms_f32(void);
 int dcp_tm_omp_lds_atoms_f64(void);
 int dcp_tm_omp_lds_atoms_c64(void);
 int dcp_tm_omp_lds_atoms_c128(void);
+/* Multichannel templates for the greedy coders: D [T, Ch, S], Y [B, Ch, N], one coefficient X [B, T, C] per event for
+ * all Ch channels: y[b, ch, n] ~ sum_(t, c) x[b, t, c] D[t, ch, n - stride c + Q].  The geometry (C, Q), the steps, the
+ * stop rules, the caps and the argument checks are those of dcp_tm_pursuit_* / dcp_tm_omp_* / dcp_tm_predict_*, with
+ * every correlation, rho2 and |y|^2 (hence tol) summed over the channels; Ch < 1 gives DCP_ERR_INVALID.  Ch = 1 runs
+ * these kernels too.
+ * With dcp_profile_* on, the correlation pass alpha0 = y A^H of dcp_tm_pursuit_*, dcp_tm_omp_* and their mc forms is
+ * timed under DCP_PROF_XUPDATE.
+ *   mc_predict:           out [B, Ch, N].
+ *   mc_template_block:    templates per thread of the correlation kernel.
+ *   mc_channels_per_pass: channels of y that kernel stages in LDS per pass for templates of S taps at this stride
+ *                         (0: one channel's window does not fit and the kernel reads global memory). */
+int dcp_tm_mc_pursuit_f32(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int positive, int* it_out);
+int dcp_tm_mc_pursuit_f64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int positive, int* it_out);
+int dcp_tm_mc_pursuit_c64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int positive, int* it_out);
+int dcp_tm_mc_pursuit_c128(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int positive, int* it_out);
+int dcp_tm_mc_omp_f32(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int* it_out);
+int dcp_tm_mc_omp_f64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int* it_out);
+int dcp_tm_mc_omp_c64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int* it_out);
+int dcp_tm_mc_omp_c128(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol /* < 0: none */, int* it_out);
+int dcp_tm_mc_predict_f32(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_mc_predict_f64(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_mc_predict_c64(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_mc_predict_c128(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, void* out);
+int dcp_tm_mc_template_block_f32(void);
+int dcp_tm_mc_template_block_f64(void);
+int dcp_tm_mc_template_block_c64(void);
+int dcp_tm_mc_template_block_c128(void);
+int dcp_tm_mc_channels_per_pass_f32(int64_t S, int64_t stride);
+int dcp_tm_mc_channels_per_pass_f64(int64_t S, int64_t stride);
+int dcp_tm_mc_channels_per_pass_c64(int64_t S, int64_t stride);
+int dcp_tm_mc_channels_per_pass_c128(int64_t S, int64_t stride);
 
 #ifdef __cplusplus
 }
