@@ -295,6 +295,14 @@ SIGNATURES = {
     'dcp_tm_mc_channels_per_pass_f64': (_c_int, [_c_i64, _c_i64]),
     'dcp_tm_mc_channels_per_pass_c64': (_c_int, [_c_i64, _c_i64]),
     'dcp_tm_mc_channels_per_pass_c128': (_c_int, [_c_i64, _c_i64]),
+    'dcp_tm_mc_dstep_events_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
+    'dcp_tm_mc_dstep_events_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
+    'dcp_tm_mc_dstep_events_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
+    'dcp_tm_mc_dstep_events_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
+    'dcp_tm_mc_gather_windows_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
+    'dcp_tm_mc_gather_windows_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
+    'dcp_tm_mc_gather_windows_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
+    'dcp_tm_mc_gather_windows_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
 }
 
 _lib = None

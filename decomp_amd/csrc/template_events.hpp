@@ -130,10 +130,11 @@ __global__ void __launch_bounds__(256) tm_events_yx_kernel(const T* __restrict__
     }
 }
 
-// tm_dstep with the two partial sums taken from event lists of at most max_events positions per row of X.
-template <class T>
-inline int tm_dstep_events(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
-                           int64_t max_events, double* maxdiff) {
+// tm_dstep with the two partial sums taken from event lists of at most max_events positions per row of X;
+// `yx(cap, ev_c, ev_n, yxpart)` enqueues the kernel that fills yxpart from them.
+template <class T, class YxLaunch>
+inline int tm_dstep_events_with(dcp_handle* h, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
+                                int64_t max_events, double* maxdiff, YxLaunch&& yx) {
     hipStream_t st = h->stream;
     const long hmax = tm_hmax(g), rows = g.B * g.T;
     const long cap = max_events < (int64_t)g.C ? (long)max_events : g.C;
@@ -152,10 +153,19 @@ inline int tm_dstep_events(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, 
         hipLaunchKernelGGL((tm_events_core_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, X, g, cap,
                            (const int*)ev_c, (const int*)ev_n, w.mpart);
         DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((tm_events_yx_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, Y, X, g, cap,
-                           (const int*)ev_c, (const int*)ev_n, w.yxpart);
+        yx(cap, (const int*)ev_c, (const int*)ev_n, w.yxpart);
         DCP_LAUNCH_OK(h, hipGetLastError());
         return DCP_OK;
+    });
+}
+
+template <class T>
+inline int tm_dstep_events(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
+                           int64_t max_events, double* maxdiff) {
+    return tm_dstep_events_with<T>(h, X, D, XXt, yX, g, acc_it, max_events, maxdiff,
+                                   [&](long cap, const int* ev_c, const int* ev_n, T* yxpart) {
+        hipLaunchKernelGGL((tm_events_yx_kernel<T>), dim3((unsigned)(g.B * g.T)), dim3(256), 0, h->stream, Y, X, g,
+                           cap, ev_c, ev_n, yxpart);
     });
 }
 

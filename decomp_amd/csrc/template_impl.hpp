@@ -34,7 +34,8 @@ DCP_HD long tm_ceil_div(long a, long b) { return -tm_floor_div(-a, b); }
 struct TmGeom {
     long B = 1, T = 0, S = 0, N = 0, C = 0, s = 1, Q = 0;
     long dh = 0;   // largest |lag| in units of c: floor((S - 1) / s)
-    long Ch = 1;   // channels of a template (D [T, Ch, S], y [B, Ch, N]): honoured by the greedy coders' kernels alone
+    long Ch = 1;   // channels of a template (D [T, Ch, S], y [B, Ch, N]): honoured by the greedy coders' kernels and by
+                   // the dictionary step on event lists (template_mc_learn.hpp) alone
     DCP_HD long nd() const { return 2 * dh + 1; }
     // c of the coefficients whose taps cover sample n: [c_first(n), c_last(n)] (clipped to [0, C))
     DCP_HD long c_first(long n) const { long c = tm_ceil_div(n + Q - S + 1, s); return c < 0 ? 0 : c; }
@@ -408,13 +409,14 @@ __global__ void __launch_bounds__(256) tm_stats_core_kernel(const T* __restrict_
     }
 }
 
-// Edge terms, summed over the batch in order:  eh[.., e] at c = cl - 1 - e,  et[.., e] at c = ch + 1 + e
+// Edge terms, summed over the batch in order:  eh[.., e] at c = cl - 1 - e,  et[.., e] at c = ch + 1 + e.
+// Grid (T, T, blocks of 256 cells (side, lag, e)): a thread sums one cell over the batch, one signal after the other.
 template <class T>
 __global__ void __launch_bounds__(256) tm_stats_edge_kernel(const T* __restrict__ x, TmGeom g, long hmax,
                                                             T* __restrict__ eh, T* __restrict__ et) {
     const long tp = blockIdx.x, t = blockIdx.y;
     const long nd = g.nd();
-    for (long q = threadIdx.x; q < nd * hmax * 2; q += 256) {
+    for (long q = blockIdx.z * 256L + threadIdx.x; q < nd * hmax * 2; q += (long)gridDim.z * 256L) {
         const long side = q / (nd * hmax), j = (q / hmax) % nd, e = q % hmax;
         const long d = j - g.dh;
         long cl, ch, ul, uh;
@@ -445,12 +447,25 @@ __global__ void __launch_bounds__(256) tm_stats_yx_kernel(const T* __restrict__ 
     }
 }
 
-// One workgroup per row i = (t, k):  XXt[i, :] and yX[i], written (acc_it == 0) or added as stat / acc_it
+// out[i] = sum_b part[b n + i], b ascending from +0: written (acc_it == 0) or added as sum / acc_it.  One thread per
+// cell i, so the reads of a signal's n partial sums coalesce.
 template <class T>
-__global__ void __launch_bounds__(256) tm_stats_assemble_kernel(const T* __restrict__ mpart, const T* __restrict__ eh,
-                                                                const T* __restrict__ et,
-                                                                const T* __restrict__ yxpart, TmGeom g, long hmax,
-                                                                int acc_it, T* __restrict__ XXt, T* __restrict__ yX) {
+__global__ void __launch_bounds__(256) tm_batch_sum_kernel(const T* __restrict__ part, long B, long n, int acc_it,
+                                                           T* __restrict__ out) {
+    typedef real_t<T> R;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
+        T s = zero_of<T>();
+        for (long b = 0; b < B; ++b) s = add(s, part[b * n + i]);
+        out[i] = acc_it ? add(out[i], div_real(s, R(acc_it))) : s;
+    }
+}
+
+// One workgroup per row i = (t, k):  XXt[i, :], written (acc_it == 0) or added as stat / acc_it.  msum [T, T, nd] is
+// mpart summed over the batch (tm_batch_sum_kernel): the S pairs (k, k') of a lag share one number.
+template <class T>
+__global__ void __launch_bounds__(256) tm_stats_assemble_kernel(const T* __restrict__ msum, const T* __restrict__ eh,
+                                                                const T* __restrict__ et, TmGeom g, long hmax,
+                                                                int acc_it, T* __restrict__ XXt) {
     typedef real_t<T> R;
     const long t = blockIdx.x / g.S, k = blockIdx.x % g.S;
     const long TS = g.T * g.S, nd = g.nd();
@@ -466,11 +481,7 @@ __global__ void __launch_bounds__(256) tm_stats_assemble_kernel(const T* __restr
                 const long base = (t * g.T + tp) * nd + j;
                 const long hend = hi < cl - 1 ? hi : cl - 1;
                 for (long c = lo; c <= hend; ++c) val = add(val, eh[base * hmax + (cl - 1 - c)]);
-                if (cl <= ch && lo <= cl && hi >= ch) {
-                    T m = zero_of<T>();
-                    for (long b = 0; b < g.B; ++b) m = add(m, mpart[((b * g.T + t) * g.T + tp) * nd + j]);
-                    val = add(val, m);
-                }
+                if (cl <= ch && lo <= cl && hi >= ch) val = add(val, msum[base]);
                 const long tbeg = lo > ch + 1 ? lo : ch + 1;
                 for (long c = tbeg; c <= hi; ++c) val = add(val, et[base * hmax + (c - ch - 1)]);
             }
@@ -478,34 +489,32 @@ __global__ void __launch_bounds__(256) tm_stats_assemble_kernel(const T* __restr
         const long o = blockIdx.x * TS + jcol;
         XXt[o] = acc_it ? add(XXt[o], div_real(val, R(acc_it))) : val;
     }
-    if (threadIdx.x == 0) {
-        T s = zero_of<T>();
-        for (long b = 0; b < g.B; ++b) s = add(s, yxpart[(b * g.T + t) * g.S + k]);
-        yX[blockIdx.x] = acc_it ? add(yX[blockIdx.x], div_real(s, R(acc_it))) : s;
-    }
 }
 
 // ---- D update -------------------------------------------------------------------------------------
-// Per index j of D_flat: colabs[j] = sum_i |XXt[i, j]|, step[j] = yX[j] - sum_i XXt[j, i] D[i]
+// One workgroup per index j = (t, k) of the n = T S rows of XXt and channel ch = blockIdx.y of D [T, Ch, S]:
+//   colabs[j] = sum_i |XXt[i, j]|  (XXt has no channels: every workgroup forms it, channel 0's stores it),
+//   step[t, ch, k] = yX[t, ch, k] - sum_(i = (t', k')) XXt[j, i] D[t', ch, k']
 template <class T>
 __global__ void __launch_bounds__(256) tm_dupdate_rows_kernel(const T* __restrict__ XXt, const T* __restrict__ yX,
-                                                              const T* __restrict__ D, long n,
+                                                              const T* __restrict__ D, long n, long S, long Ch,
                                                               real_t<T>* __restrict__ colabs, T* __restrict__ step) {
     typedef real_t<T> R;
     __shared__ R sh[4];
-    const long j = blockIdx.x;
+    const long j = blockIdx.x, ch = blockIdx.y;
     R ca = 0, re = 0, im = 0;
     for (long i = threadIdx.x; i < n; i += 256) {
         ca += absval(XXt[i * n + j]);
-        const T p = mul(XXt[j * n + i], D[i]);
+        const T p = mul(XXt[j * n + i], D[((i / S) * Ch + ch) * S + i % S]);
         re += real_part(p);
         im += imag_part(p);
     }
     const R tca = block_sum_256(ca, sh);
     const T dot = block_sum_256_parts<T>(re, im, sh);
     if (threadIdx.x == 0) {
-        colabs[j] = tca;
-        step[j] = sub(yX[j], dot);
+        if (ch == 0) colabs[j] = tca;
+        const long o = ((j / S) * Ch + ch) * S + j % S;
+        step[o] = sub(yX[o], dot);
     }
 }
 
@@ -519,17 +528,17 @@ __global__ void __launch_bounds__(256) tm_dupdate_apply_kernel(const T* __restri
 }
 
 // ---- minibatch windows (template_matching.py:219-253) ---------------------------------------------
-// yw[j, n] = y[ib[j], in[j] + n];  xw[j, t, c] = x[ib[j], t, in[j] + c]
+// yw[j, ch, n] = y[ib[j], ch, in[j] + n] (y [B, Ch, N]; Ch = 1: y [B, N]);  xw[j, t, c] = x[ib[j], t, in[j] + c]
 template <class T>
 __global__ void __launch_bounds__(256) tm_gather_kernel(const T* __restrict__ y, const T* __restrict__ x,
                                                         const int64_t* __restrict__ ib, const int64_t* __restrict__ in,
-                                                        long m, long N, long T_, long C, long w, long cw,
+                                                        long m, long Ch, long N, long T_, long C, long w, long cw,
                                                         T* __restrict__ yw, T* __restrict__ xw) {
-    const long ny = m * w, nx = m * T_ * cw;
+    const long ny = m * Ch * w, nx = m * T_ * cw;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < ny + nx; i += (long)gridDim.x * 256L) {
         if (i < ny) {
-            const long j = i / w, n = i % w;
-            yw[i] = y[ib[j] * N + in[j] + n];
+            const long j = i / (Ch * w), ch = (i / w) % Ch, n = i % w;
+            yw[i] = y[(ib[j] * Ch + ch) * N + in[j] + n];
         } else {
             const long q = i - ny;
             const long j = q / (T_ * cw), t = (q / cw) % T_, c = q % cw;
@@ -682,61 +691,75 @@ inline long tm_hmax(const TmGeom& g) {
 // The workspace of a dictionary step: the partial statistics and the D update's vectors.
 template <class T>
 struct TmDstepWs {
-    T *mpart = nullptr, *eh = nullptr, *et = nullptr, *yxpart = nullptr, *step = nullptr, *U = nullptr, *Dn = nullptr;
+    T *mpart = nullptr, *msum = nullptr, *eh = nullptr, *et = nullptr, *yxpart = nullptr, *step = nullptr, *U = nullptr,
+      *Dn = nullptr;
     real_t<T>*colabs = nullptr, *rowmax = nullptr, *scal = nullptr;
 };
 
 template <class T>
 inline void tm_dstep_layout(WsLayout& a, TmDstepWs<T>& w, const TmGeom& g, long hmax) {
-    const long nd = g.nd(), TS = g.T * g.S;
+    const long nd = g.nd(), TS = g.T * g.S, nD = TS * g.Ch;
     a.take(w.mpart, g.B * g.T * g.T * nd);
+    a.take(w.msum, g.T * g.T * nd);
     a.take(w.eh, g.T * g.T * nd * hmax);
     a.take(w.et, g.T * g.T * nd * hmax);
-    a.take(w.yxpart, g.B * TS);
+    a.take(w.yxpart, g.B * nD);
     a.take(w.colabs, TS);
-    a.take(w.step, TS);
-    a.take(w.U, TS);
-    a.take(w.Dn, TS);
+    a.take(w.step, nD);
+    a.take(w.U, nD);
+    a.take(w.Dn, nD);
     a.take(w.rowmax, g.T);
     a.take(w.scal, 4);
 }
 
-// A dictionary step around its partial sums: `partials()` enqueues whatever fills mpart and yxpart; then the edge
-// terms, the assembly of XXt / yX (written, or added as stat / acc_it to the running sums), the D update
-// D <- l2(D + (yX - XXt D) / (Gershgorin(XXt) + 1e-15)) and the step's one synchronisation; *maxdiff = max |D - D_new|.
+// A dictionary step around its partial sums: `partials()` enqueues whatever fills mpart and yxpart; then their sums
+// over the batch (msum, and yX: written, or added as stat / acc_it to the running sum), the edge terms, the assembly of
+// XXt (likewise), the D update D <- l2(D + (yX - XXt D) / (Gershgorin(XXt) + 1e-15)) and the step's one
+// synchronisation; *maxdiff = max |D - D_new|.  With g.Ch channels D, yX and yxpart's rows are [T, Ch, S], the product
+// XXt D is taken channel by channel (XXt [T S, T S] and its Gershgorin bound are those of one channel: x is shared)
+// and a template is normalised over its Ch S entries.
 // Timed under DCP_PROF_STATS up to the assembly, the partial sums alone under DCP_PROF_MISC as well.
 template <class T, class Partials>
 inline int tm_dstep_around(dcp_handle* h, const TmDstepWs<T>& w, const T* X, T* D, T* XXt, T* yX, const TmGeom& g,
                            long hmax, int acc_it, double* maxdiff, Partials&& partials) {
     typedef real_t<T> R;
     hipStream_t st = h->stream;
-    const long TS = g.T * g.S;
+    const long TS = g.T * g.S, nM = g.T * g.T * g.nd(), F = g.Ch * g.S, nD = g.T * F;
+    if (g.Ch > 65535) return fail(h, DCP_ERR_INVALID, "dictionary step: more than 65535 channels");
     {
         ProfScope ps(h, DCP_PROF_STATS);
         {
             ProfScope pp(h, DCP_PROF_MISC);
             DCP_TRY(partials());
         }
-        hipLaunchKernelGGL((tm_stats_edge_kernel<T>), dim3(g.T, g.T), dim3(256), 0, st, X, g, hmax, w.eh, w.et);
+        hipLaunchKernelGGL((tm_batch_sum_kernel<T>), dim3(tm_grid(nM)), dim3(256), 0, st, (const T*)w.mpart, g.B, nM,
+                           0, w.msum);
         DCP_LAUNCH_OK(h, hipGetLastError());
-        hipLaunchKernelGGL((tm_stats_assemble_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)w.mpart,
-                           (const T*)w.eh, (const T*)w.et, (const T*)w.yxpart, g, hmax, acc_it, XXt, yX);
+        hipLaunchKernelGGL((tm_batch_sum_kernel<T>), dim3(tm_grid(nD)), dim3(256), 0, st, (const T*)w.yxpart, g.B, nD,
+                           acc_it, yX);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        const int eblocks = tm_grid(g.nd() * hmax * 2);
+        hipLaunchKernelGGL((tm_stats_edge_kernel<T>), dim3(g.T, g.T, eblocks < 65535 ? eblocks : 65535), dim3(256),
+                           0, st, X, g, hmax, w.eh, w.et);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        hipLaunchKernelGGL((tm_stats_assemble_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)w.msum,
+                           (const T*)w.eh, (const T*)w.et, g, hmax, acc_it, XXt);
         DCP_LAUNCH_OK(h, hipGetLastError());
     }
-    hipLaunchKernelGGL((tm_dupdate_rows_kernel<T>), dim3(TS), dim3(256), 0, st, (const T*)XXt, (const T*)yX,
-                       (const T*)D, TS, w.colabs, w.step);
+    hipLaunchKernelGGL((tm_dupdate_rows_kernel<T>), dim3(TS, g.Ch), dim3(256), 0, st, (const T*)XXt, (const T*)yX,
+                       (const T*)D, TS, g.S, g.Ch, w.colabs, w.step);
     DCP_LAUNCH_OK(h, hipGetLastError());
     launch_tm_max<R>(st, w.colabs, TS, R(1.0e-15), w.scal);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((tm_dupdate_apply_kernel<T>), dim3(tm_grid(TS)), dim3(256), 0, st, (const T*)D,
-                       (const T*)w.step, (const R*)w.scal, TS, w.U);
+    hipLaunchKernelGGL((tm_dupdate_apply_kernel<T>), dim3(tm_grid(nD)), dim3(256), 0, st, (const T*)D,
+                       (const T*)w.step, (const R*)w.scal, nD, w.U);
     DCP_LAUNCH_OK(h, hipGetLastError());
     // D_new = l2(U) (normalize.py:2-10) into its own buffer (the kernel's ref and out are restrict), rowmax[t] =
     // max |D - D_new| over the row; then D <- D_new
-    hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(g.T), dim3(256), 0, st, (const T*)w.U, g.S, g.S, 0,
-                       (const T*)D, g.S, w.Dn, g.S, w.rowmax);
+    hipLaunchKernelGGL((row_normalize_kernel<T>), dim3(g.T), dim3(256), 0, st, (const T*)w.U, F, F, 0,
+                       (const T*)D, F, w.Dn, F, w.rowmax);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    DCP_HIP_OK(h, hipMemcpyAsync(D, w.Dn, (size_t)TS * sizeof(T), hipMemcpyDeviceToDevice, st));
+    DCP_HIP_OK(h, hipMemcpyAsync(D, w.Dn, (size_t)nD * sizeof(T), hipMemcpyDeviceToDevice, st));
     launch_tm_max<R>(st, w.rowmax, g.T, R(0), w.scal + 2);
     DCP_LAUNCH_OK(h, hipGetLastError());
     void* hostv = nullptr;
@@ -770,6 +793,7 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
 #include "template_pursuit.hpp"   // matching pursuit on the same operator
 #include "template_omp.hpp"       // orthogonal (re-fitting) pursuit on the same operator
 #include "template_events.hpp"    // the dictionary step from event lists, for the codes of those two
+#include "template_mc_learn.hpp"  // that step for templates D [T, Ch, S]
 
 // ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip) ------------------------------
 #define DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding)                                    \
@@ -905,8 +929,35 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
             return dcp::fail(h, DCP_ERR_INVALID, "window geometry");                                           \
         if (!Y || !X || !idx_b || !idx_n || !Yw || !Xw) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
         hipLaunchKernelGGL((dcp::tm_gather_kernel<TYPE>), dim3(dcp::tm_grid(m * (w + g.T * gw.C))), dim3(256), \
-                           0, h->stream, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, (long)m, g.N, g.T, g.C, \
-                           (long)w, gw.C, (TYPE*)Yw, (TYPE*)Xw);                                               \
+                           0, h->stream, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, (long)m, 1L, g.N, g.T,  \
+                           g.C, (long)w, gw.C, (TYPE*)Yw, (TYPE*)Xw);                                          \
+        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
+        return DCP_OK;                                                                                         \
+    }                                                                                                          \
+    extern "C" int dcp_tm_mc_dstep_events_##SFX(dcp_handle* h, const void* Y, const void* X, void* D,         \
+                                                 void* XXt, void* yX, int64_t B, int64_t T_, int64_t Ch,       \
+                                                 int64_t S, int64_t N, int64_t stride, int padding,            \
+                                                 int acc_it, int64_t max_events, double* maxdiff) {            \
+        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
+        if (!Y || !X || !D || !XXt || !yX || !maxdiff) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
+        if (acc_it < 0) return dcp::fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");                           \
+        if (max_events < 1) return dcp::fail(h, DCP_ERR_INVALID, "max_events must be >= 1");                   \
+        return dcp::tm_mc_dstep_events<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt,          \
+                                             (TYPE*)yX, g, acc_it, max_events, maxdiff);                       \
+    }                                                                                                          \
+    extern "C" int dcp_tm_mc_gather_windows_##SFX(dcp_handle* h, const void* Y, const void* X,                \
+                                                   const int64_t* idx_b, const int64_t* idx_n, int64_t m,     \
+                                                   int64_t B, int64_t T_, int64_t Ch, int64_t S, int64_t N,   \
+                                                   int64_t w, int64_t stride, int padding, void* Yw,          \
+                                                   void* Xw) {                                                 \
+        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
+        dcp::TmGeom gw;                                                                                        \
+        if (!dcp::tm_geom(gw, m, T_, S, w, stride, padding) || w > N)                                          \
+            return dcp::fail(h, DCP_ERR_INVALID, "window geometry");                                           \
+        if (!Y || !X || !idx_b || !idx_n || !Yw || !Xw) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
+        hipLaunchKernelGGL((dcp::tm_gather_kernel<TYPE>), dim3(dcp::tm_grid(m * (g.Ch * w + g.T * gw.C))),     \
+                           dim3(256), 0, h->stream, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, (long)m,     \
+                           g.Ch, g.N, g.T, g.C, (long)w, gw.C, (TYPE*)Yw, (TYPE*)Xw);                          \
         DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
         return DCP_OK;                                                                                         \
     }                                                                                                          \

@@ -22,7 +22,11 @@ size is formed on the hot path (include/decomp_hip.h ``dcp_tm_*``, decomp_amd/cs
     (``dcp_tm_dstep_events_*``, decomp_amd/csrc/template_events.hpp);
   * ``pursuit``, ``orthogonal_pursuit`` and ``predict`` take multichannel templates D [T, Ch, S] (y [..., Ch, N], one
     coefficient per event for all channels): every correlation, rho2 and |y|^2 gains a sum over the channels, the
-    correlation pass is a kernel of its own (``dcp_tm_mc_*``, decomp_amd/csrc/template_multichannel.hpp).
+    correlation pass is a kernel of its own (``dcp_tm_mc_*``, decomp_amd/csrc/template_multichannel.hpp);
+  * ``solve`` with one of those greedy coders learns multichannel templates D [T, Ch, S] too: x is shared by the
+    channels, so XXt stays the one-channel [T S, T S], only yX [T, Ch, S] gains the channel axis, the gradient step is
+    XXt times the [T S, Ch] columns of D and a template is normalised over its Ch S entries
+    (``dcp_tm_mc_dstep_events_*``, decomp_amd/csrc/template_mc_learn.hpp).
 
 'cd', 'parallel_cd' and 'admm' have no structured form: for them ``_temp2mat`` is materialised on the
 device and the dense ``dcp_lasso_*`` solvers of decomp_amd.lasso run on it.  That path is correct but
@@ -67,16 +71,21 @@ def solve(y, D, alpha, stride=1, padding='SAME', x=None, tol=1.0e-4,
     the coder's n_nonzero_coefs (per signal, or per window with minibatch) and lasso_tol its tol, the residual energy
     at which a signal stops (None: none) -- the convention of dictionary_learning.solve(lasso_method='omp').  The
     coders start from zero, so an ``x`` passed in is not read.  y must be finite.
+    With a greedy coder the templates may be multichannel, D [T, Ch, S] for y [B, Ch, N] or [Ch, N] (one signal): the
+    model is that of ``pursuit``, y[b, ch, n] ~ sum x[b, t, c] D[t, ch, n - stride c + Q] with x [B, T, C] (or [T, C]),
+    and the constraint |D_t|^2 <= 1 is on the Ch S entries of a template.  Everything else keeps its meaning; the
+    LASSO coders have no multichannel form (NotImplementedError).
     Returns (it, D, x) as the reference does.  NumPy in -> NumPy out; torch GPU tensors stay on the device.
     """
     get_array_module(y, D, x)                                         # template_matching.py:48
+    Ch = _learn_channels(y, D, lasso_method)
     if lasso_method in _GREEDY:                                       # (the rest of its checks: solve_fastpath)
         stride, _ = _geometry(int(D.shape[0]), int(D.shape[-1]), int(y.shape[-1]), stride, padding)
     rng = np.random.RandomState(random_seed)
     x_given = x
     if x is None:
         coef_size = _coef_size(D.shape[-1], y.shape[-1], stride=stride, padding=padding)
-        if len(y.shape) == 2:
+        if len(y.shape) == (2 if Ch is None else 3):
             shape = (y.shape[0], D.shape[0], coef_size)
         else:
             shape = (D.shape[0], coef_size)
@@ -104,14 +113,15 @@ def solve_fastpath(y, D, alpha, x, stride, padding, tol,
     if mask is not None:
         raise NotImplementedError('Template matching with mask is not '
                                   'yet implemented.')
+    Ch = _learn_channels(y, D, lasso_method)
     if lasso_method in _GREEDY:
         N = y.shape[-1] if minibatch is None else int(size_of_minibatch)
-        _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, D.shape[0], D.shape[1], N, stride, padding,
+        _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, D.shape[0], D.shape[-1], N, stride, padding,
                      _arrays.np_dtype(y))
     import torch
     kind = 'torch' if _arrays.is_torch(y) else 'numpy'
     yd = _arrays.to_device(y)
-    one_d = yd.dim() == 1
+    one_d = yd.dim() == (1 if Ch is None else 2)
     y2 = yd.unsqueeze(0) if one_d else yd
     if isinstance(x, lasso._ZerosLike):
         xd = torch.zeros(((1,) if one_d else ()) + tuple(x.shape), dtype=yd.dtype, device=yd.device)
@@ -361,6 +371,24 @@ def _channels(D):
     return int(D.shape[1])
 
 
+def _learn_channels(y, D, lasso_method):
+    """The channels of the templates ``solve`` is given (``_channels``), and for multichannel ones the checks on
+    lasso_method and y [B, Ch, N] / [Ch, N].  No GPU call."""
+    Ch = _channels(D)
+    if Ch is None:
+        return None
+    if lasso_method not in _GREEDY:
+        raise NotImplementedError('multichannel templates D [T, Ch, S] are learnt with lasso_method in {0} only. '
+                                  'Given {1!r}'.format(sorted(_GREEDY), lasso_method))
+    if len(y.shape) not in (2, 3):
+        raise assertion.DimInvalidError('y must be [B, Ch, N] or [Ch, N] for templates D [T, Ch, S], has %d '
+                                        'dimension(s)' % len(y.shape))
+    if int(y.shape[-2]) != Ch:
+        raise assertion.DimInvalidError('y{0} must be [..., Ch, N] with the Ch = {1:d} channels of the templates '
+                                        'D{2}'.format(tuple(y.shape), Ch, tuple(D.shape)))
+    return Ch
+
+
 def _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, T, S, N, stride, padding, dt):
     """``solve`` with a greedy coder (lasso_method in _GREEDY) on signals (or windows) of N samples: alpha must be 0,
     lasso_iter is the coder's n_nonzero_coefs and lasso_tol its tol, each checked by the coder's own rule.  No GPU
@@ -456,10 +484,20 @@ def _dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events):
     return out.value
 
 
+def _mc_dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events):
+    """``_dstep_events`` for y [B, Ch, N], D [T, Ch, S] (updated in place), yX [T Ch S]; XXt [T S, T S]."""
+    B, Ch, N = y.shape
+    T, _, S = D.shape
+    out = ctypes.c_double(0.0)
+    _call(y, 'mc_dstep_events', y, x, D, XXt, yX,
+          B, T, Ch, S, N, stride, _pad_code(padding), int(acc_it), int(max_events), ctypes.byref(out))
+    return out.value
+
+
 def _steps(N, D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol):
     """The two halves of an outer iteration on signals of N samples, (code(y, D, x), dstep(y, x, D, XXt, yX, acc_it)):
     the LASSO solver and the dense dictionary step, or for a greedy lasso_method its coder, which writes x entirely,
-    and the dictionary step on event lists."""
+    and the dictionary step on event lists (their multichannel forms for D [T, Ch, S])."""
     if lasso_method not in _GREEDY:
         def code(y, D, x):
             _lasso(y, D, x, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
@@ -467,11 +505,21 @@ def _steps(N, D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol):
         def dstep(y, x, D, XXt, yX, acc_it):
             return _dstep(y, x, D, XXt, yX, stride, padding, acc_it)
         return code, dstep
-    T, S = D.shape
+    Ch = _channels(D)
+    T, S = int(D.shape[0]), int(D.shape[-1])
     n_steps, tol_c, max_events = _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, T, S, N, stride, padding,
                                               _arrays.np_dtype(D))
     name, flags = _GREEDY[lasso_method]
     stride = int(stride)
+    if Ch is not None:
+        def code(y, D, x):
+            it = ctypes.c_int(0)
+            _call(y, 'mc_' + name, y, D, x, y.shape[0], T, Ch, S, N, stride, _pad_code(padding), n_steps, tol_c,
+                  *(flags + (ctypes.byref(it),)))
+
+        def dstep(y, x, D, XXt, yX, acc_it):
+            return _mc_dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events)
+        return code, dstep
 
     def code(y, D, x):
         it = ctypes.c_int(0)
@@ -481,6 +529,13 @@ def _steps(N, D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol):
     def dstep(y, x, D, XXt, yX, acc_it):
         return _dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events)
     return code, dstep
+
+
+def _normalized_templates(D):
+    """D [T, S] or [T, Ch, S] with every template scaled to unit norm (strictly) over all its entries."""
+    if D.dim() == 2:
+        return normalize.l2_strict(D, axis=-1)
+    return normalize.l2_strict(D.reshape(D.shape[0], -1), axis=-1).reshape(D.shape)
 
 
 def _device_args(y, D, x):
@@ -509,19 +564,20 @@ def _draw_windows(rng, B, N, w, m, C, cw):
 def solve_batch(y, D, alpha, x, stride, padding, tol, maxiter,
                 lasso_method, lasso_iter, lasso_tol, xp):
     """
-    Alternates, on the whole batch y [B, N]:
+    Alternates, on the whole batch y [B, N] (y [B, Ch, N] for multichannel templates D [T, Ch, S], greedy coders):
       x <- the LASSO solution of y = x * D (lasso_iter iterations of lasso_method from the current x), or the code
            of the greedy coder ('omp', 'mp', 'mp_pos': at most lasso_iter events per signal, from zero);
       D <- l2(D + (yX - XXt D) / L), one gradient step on the templates.
-    Stops when max|dD| < tol.  D is normalised (strictly) once at entry.
+    Stops when max|dD| < tol.  D is normalised (strictly) once at entry.  XXt is [T S, T S] whatever the number of
+    channels (x is shared by them), yX has the size of D.
     """
     import torch
     code, dstep = _steps(y.shape[-1], D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
     kind, y, D, x = _device_args(y, D, x)
-    D = normalize.l2_strict(D, axis=-1)
-    T, S = D.shape
+    D = _normalized_templates(D)
+    T, S = D.shape[0], D.shape[-1]
     XXt = torch.empty((T * S, T * S), dtype=D.dtype, device=D.device)
-    yX = torch.empty((T * S,), dtype=D.dtype, device=D.device)
+    yX = torch.empty((D.numel(),), dtype=D.dtype, device=D.device)
     for it in range(1, maxiter):
         Dprev = D.clone()
         try:
@@ -586,30 +642,33 @@ def solve_minibatch(y, D, alpha, x, stride, padding, tol,
     are written back in draw order (so with stride > 1 a window can run past the coefficients: ValueError,
     as in the reference, see _draw_windows).  The statistics are accumulated as XXt_sum += XXt / it,
     yX_sum += yX / it (it = 1, 2, ...).  Returns the full x.  A greedy coder codes every window from zero, with at
-    most lasso_iter events per window.
+    most lasso_iter events per window.  Multichannel templates D [T, Ch, S]: the windows are yw [m, Ch, w].
     """
     import torch
     code, dstep = _steps(int(size_of_minibatch), D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
     kind, y, D, x = _device_args(y, D, x)
-    D = normalize.l2_strict(D, axis=-1)
-    B, N = y.shape
-    T, S = D.shape
+    D = _normalized_templates(D)
+    B, N = y.shape[0], y.shape[-1]
+    T, S = D.shape[0], D.shape[-1]
     C = x.shape[-1]
     w = int(size_of_minibatch)
     cw = _coef_size(S, w, stride=stride, padding=padding)
     m = int(minibatch)
-    yX_sum = torch.zeros((T * S,), dtype=D.dtype, device=D.device)
+    yX_sum = torch.zeros((D.numel(),), dtype=D.dtype, device=D.device)
     XXt_sum = torch.zeros((T * S, T * S), dtype=D.dtype, device=D.device)
-    yw = torch.empty((m, w), dtype=y.dtype, device=y.device)
+    yw = torch.empty((m,) + tuple(y.shape[1:-1]) + (w,), dtype=y.dtype, device=y.device)
     xw = torch.empty((m, T, cw), dtype=y.dtype, device=y.device)
+    if D.dim() == 3:
+        gather = ('mc_gather_windows', (B, T, int(D.shape[1]), S, N, w, stride, _pad_code(padding)))
+    else:
+        gather = ('gather_windows', (B, T, S, N, w, stride, _pad_code(padding)))
     for it in range(1, maxiter):
         Dprev = D.clone()
         try:
             rows, starts = _draw_windows(rng, B, N, w, m, C, cw)
             ib = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(y.device)
             inn = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int64)).to(y.device)
-            _call(y, 'gather_windows', y, x, ib, inn, m,
-                  B, T, S, N, w, stride, _pad_code(padding), yw, xw)
+            _call(y, gather[0], y, x, ib, inn, m, *(gather[1] + (yw, xw)))
             code(yw, D, xw)
             _call(y, 'scatter_windows', xw, x, ib, inn, m,
                   B, T, S, N, w, stride, _pad_code(padding))

@@ -946,6 +946,23 @@ int dcp_tm_mc_channels_per_pass_f32(int64_t S, int64_t stride);
 int dcp_tm_mc_channels_per_pass_f64(int64_t S, int64_t stride);
 int dcp_tm_mc_channels_per_pass_c64(int64_t S, int64_t stride);
 int dcp_tm_mc_channels_per_pass_c128(int64_t S, int64_t stride);
+/* Learning multichannel templates: dcp_tm_dstep_events_* for D [T, Ch, S] (updated in place), Y [B, Ch, N],
+ * X [B, T, C], yX [T Ch S]; XXt [T S, T S] is that of one channel, since X is shared by the channels.
+ *   U[t, ch, k] = D[t, ch, k] + (yX[t, ch, k] - sum_(t', k') XXt[(t, k), (t', k')] D[t', ch, k']) / L,
+ *   L = Gershgorin(XXt) + 1e-15,   D <- U / |U_t| with the norm over the Ch S entries of a template;
+ * *maxdiff = max|dD| over all T Ch S entries.  acc_it, max_events, the single synchronisation, the argument checks and
+ * the profile scopes are those of dcp_tm_dstep_events_*; Ch < 1 gives DCP_ERR_INVALID.  Channel by channel the sums
+ * are the one-channel step's: with Ch = 1 the outputs are dcp_tm_dstep_events_*'s bit for bit.
+ *   mc_gather_windows: Yw [m, Ch, w] = Y[idx_b[j], :, idx_n[j] : + w], Xw as dcp_tm_gather_windows_*; the codes go
+ *              back with dcp_tm_scatter_windows_*. */
+int dcp_tm_mc_dstep_events_f32(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, int64_t max_events, double* maxdiff);
+int dcp_tm_mc_dstep_events_f64(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, int64_t max_events, double* maxdiff);
+int dcp_tm_mc_dstep_events_c64(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, int64_t max_events, double* maxdiff);
+int dcp_tm_mc_dstep_events_c128(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, int acc_it, int64_t max_events, double* maxdiff);
+int dcp_tm_mc_gather_windows_f32(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
+int dcp_tm_mc_gather_windows_f64(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
+int dcp_tm_mc_gather_windows_c64(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
+int dcp_tm_mc_gather_windows_c128(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
 
 #ifdef __cplusplus
 }
