@@ -5,9 +5,15 @@
 // term they add is an exact zero.  Here the non-zeros of every row (b, t) of x are first compacted into a list of
 // positions, in ascending c, and the two statistics are then summed over the listed positions only:
 //   mpart[((b T + t) T + t') nd + (d + dh)] = sum_(events c of row (b, t) in core(d)) x[b, t, c] conj(x[b, t', c + d])
-//   yxpart[(b T + t) S + k]                 = sum_(events c of row (b, t) in window(k, 0)) x[b, t, c] y[b, s c - Q + k]
+//   yxpart[((b T + t) Ch + ch) S + k]       = sum_(events c of row (b, t) in window(k, 0)) x[b, t, c] y[b, ch, s c - Q + k]
 // with the right factors read from the dense x and y.  Everything after these partial sums (edge terms, assembly,
 // the D update) is tm_dstep_around of template_impl.hpp, shared with the dense step.
+//
+// Multichannel templates D [T, Ch, S] (y [B, Ch, N], x [B, T, C]: one coefficient per event for all channels;
+// TmGeom::Ch, 1 for D [T, S]).  x is shared by the channels, so the Gram statistic is the one-channel XXt [T S, T S]:
+// the compaction, tm_events_core_kernel, the edge terms and the assembly do not see Ch.  Only yX gains the channel
+// axis, channel by channel the same sum, and the update of tm_dstep_around takes the product XXt D per channel and
+// normalises a template over its Ch S entries.
 //
 // The result equals the dense step's bit for bit: the terms are added in the same ascending order by the same
 // tm_stat_madd (one spelling of the complex product, so that no two kernels fuse it differently), and a left-out term
@@ -106,7 +112,8 @@ __global__ void __launch_bounds__(256) tm_events_core_kernel(const T* __restrict
     }
 }
 
-// One workgroup per row (b, t); the S taps k go over the threads, 256 at a time.
+// One workgroup per row (b, t) and block of 256 of its Ch S cells (ch, k), k fastest over the lanes: an event is one
+// coalesced read of y per channel, and a workgroup walks the event list once.  grid (B T, ceil(Ch S / 256)).
 template <class T>
 __global__ void __launch_bounds__(256) tm_events_yx_kernel(const T* __restrict__ y, const T* __restrict__ x, TmGeom g,
                                                            long cap, const int* __restrict__ ev_c,
@@ -114,30 +121,32 @@ __global__ void __launch_bounds__(256) tm_events_yx_kernel(const T* __restrict__
     __shared__ int sc[kTmEvChunk];
     __shared__ T sv[kTmEvChunk];
     const long bt = blockIdx.x, b = bt / g.T;
-    const T* xa = x + bt * g.C;
-    const T* yb = y + b * g.N;
-    const long n_all = ev_n[bt];
-    for (long k0 = 0; k0 < g.S; k0 += 256) {
-        const long k = k0 + threadIdx.x;
-        const bool live = k < g.S;
-        long lo, hi;
-        g.window(live ? k : 0, 0, &lo, &hi);
-        T acc = zero_of<T>();
-        tm_events_walk(xa, ev_c + bt * cap, n_all, cap, g.C, sc, sv, [&](long c, T v) {
-            if (live && c >= lo && c <= hi) acc = tm_stat_madd(acc, v, yb[g.s * c - g.Q + k]);
-        });
-        if (live) yxpart[bt * g.S + k] = acc;
-    }
+    const long cells = g.Ch * g.S, q = blockIdx.y * 256L + threadIdx.x;
+    const bool live = q < cells;
+    const long ch = live ? q / g.S : 0, k = live ? q % g.S : 0;
+    const T* yb = y + (b * g.Ch + ch) * g.N;
+    long lo, hi;
+    g.window(k, 0, &lo, &hi);
+    T acc = zero_of<T>();
+    tm_events_walk(x + bt * g.C, ev_c + bt * cap, (long)ev_n[bt], cap, g.C, sc, sv, [&](long c, T v) {
+        if (live && c >= lo && c <= hi) acc = tm_stat_madd(acc, v, yb[g.s * c - g.Q + k]);
+    });
+    if (live) yxpart[bt * cells + q] = acc;
 }
 
-// tm_dstep with the two partial sums taken from event lists of at most max_events positions per row of X;
-// `yx(cap, ev_c, ev_n, yxpart)` enqueues the kernel that fills yxpart from them.
-template <class T, class YxLaunch>
-inline int tm_dstep_events_with(dcp_handle* h, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
-                                int64_t max_events, double* maxdiff, YxLaunch&& yx) {
+// tm_dstep with the two partial sums taken from event lists of at most max_events positions per row of X, for
+// Y [B, Ch, N], D [T, Ch, S], yX [T Ch S] (g.Ch channels; 1: Y [B, N], D [T, S]); XXt [T S, T S].  Both
+// dcp_tm_dstep_events_* and dcp_tm_mc_dstep_events_* are this function after their geometry.
+template <class T>
+inline int tm_dstep_events(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
+                           int64_t max_events, double* maxdiff) {
+    if (!Y || !X || !D || !XXt || !yX || !maxdiff) return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (acc_it < 0) return fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");
+    if (max_events < 1) return fail(h, DCP_ERR_INVALID, "max_events must be >= 1");
     hipStream_t st = h->stream;
-    const long hmax = tm_hmax(g), rows = g.B * g.T;
+    const long hmax = tm_hmax(g), rows = g.B * g.T, blocks = (g.Ch * g.S + 255) / 256;
     const long cap = max_events < (int64_t)g.C ? (long)max_events : g.C;
+    if (blocks > 65535) return fail(h, DCP_ERR_INVALID, "multichannel D step: Ch S exceeds 65535 * 256");
     if (rows > 0x7fffffffL) return fail(h, DCP_ERR_INVALID, "event D step: B T exceeds 2^31 - 1");
     TmDstepWs<T> w;
     int *ev_c = nullptr, *ev_n = nullptr;   // the position lists take no more room than X: cap <= C 32-bit words a row
@@ -153,19 +162,10 @@ inline int tm_dstep_events_with(dcp_handle* h, const T* X, T* D, T* XXt, T* yX, 
         hipLaunchKernelGGL((tm_events_core_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, X, g, cap,
                            (const int*)ev_c, (const int*)ev_n, w.mpart);
         DCP_LAUNCH_OK(h, hipGetLastError());
-        yx(cap, (const int*)ev_c, (const int*)ev_n, w.yxpart);
+        hipLaunchKernelGGL((tm_events_yx_kernel<T>), dim3((unsigned)rows, (unsigned)blocks), dim3(256), 0, st, Y, X, g,
+                           cap, (const int*)ev_c, (const int*)ev_n, w.yxpart);
         DCP_LAUNCH_OK(h, hipGetLastError());
         return DCP_OK;
-    });
-}
-
-template <class T>
-inline int tm_dstep_events(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmGeom& g, int acc_it,
-                           int64_t max_events, double* maxdiff) {
-    return tm_dstep_events_with<T>(h, X, D, XXt, yX, g, acc_it, max_events, maxdiff,
-                                   [&](long cap, const int* ev_c, const int* ev_n, T* yxpart) {
-        hipLaunchKernelGGL((tm_events_yx_kernel<T>), dim3((unsigned)(g.B * g.T)), dim3(256), 0, h->stream, Y, X, g,
-                           cap, ev_c, ev_n, yxpart);
     });
 }
 

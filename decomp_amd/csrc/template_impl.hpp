@@ -35,7 +35,7 @@ struct TmGeom {
     long B = 1, T = 0, S = 0, N = 0, C = 0, s = 1, Q = 0;
     long dh = 0;   // largest |lag| in units of c: floor((S - 1) / s)
     long Ch = 1;   // channels of a template (D [T, Ch, S], y [B, Ch, N]): honoured by the greedy coders' kernels and by
-                   // the dictionary step on event lists (template_mc_learn.hpp) alone
+                   // the dictionary step on event lists (template_events.hpp) alone
     DCP_HD long nd() const { return 2 * dh + 1; }
     // c of the coefficients whose taps cover sample n: [c_first(n), c_last(n)] (clipped to [0, C))
     DCP_HD long c_first(long n) const { long c = tm_ceil_div(n + Q - S + 1, s); return c < 0 ? 0 : c; }
@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(256) tm_corr_step_kernel(const T* __restrict__
 }
 
 // ---- prepare ------------------------------------------------------------------------------------
-// |A_(t,c)|^2 over its taps inside [0, N)
+// |A_(t,c)|^2 over its taps inside [0, N), over the g.Ch channels of D [T, Ch, S] (ch ascending, k ascending inside)
 template <class T>
 __device__ __forceinline__ real_t<T> tm_row_norm2(const T* __restrict__ D, const TmGeom& g, long t, long c) {
     const long base = g.s * c - g.Q;
@@ -240,7 +240,8 @@ __device__ __forceinline__ real_t<T> tm_row_norm2(const T* __restrict__ D, const
     if (k0 < 0) k0 = 0;
     if (k1 > g.S - 1) k1 = g.S - 1;
     real_t<T> acc = 0;
-    for (long k = k0; k <= k1; ++k) acc += abs2(D[t * g.S + k]);
+    for (long ch = 0; ch < g.Ch; ++ch)
+        for (long k = k0; k <= k1; ++k) acc += abs2(D[(t * g.Ch + ch) * g.S + k]);
     return acc;
 }
 
@@ -271,16 +272,19 @@ __global__ void __launch_bounds__(256) tm_scale_kernel(const T* __restrict__ x, 
     }
 }
 
-// corr[(t * T + t') * (2S - 1) + m + S - 1] = sum_k D[t, k] conj(D[t', k + m])
+// corr[(t * T + t') * (2S - 1) + m + S - 1] = sum_ch sum_k D[t, ch, k] conj(D[t', ch, k + m]) over the g.Ch channels
+// of D [T, Ch, S] (ch ascending, k ascending inside)
 template <class T>
 __global__ void __launch_bounds__(256) tm_lagcorr_kernel(const T* __restrict__ D, TmGeom g, T* __restrict__ corr) {
     const long t = blockIdx.x / g.T, tp = blockIdx.x % g.T;
     const long W = 2 * g.S - 1;
     for (long j = threadIdx.x; j < W; j += 256) {
         const long m = j - (g.S - 1);
-        long k0 = m < 0 ? -m : 0, k1 = m > 0 ? g.S - 1 - m : g.S - 1;
+        const long k0 = m < 0 ? -m : 0, k1 = m > 0 ? g.S - 1 - m : g.S - 1;
         T acc = zero_of<T>();
-        for (long k = k0; k <= k1; ++k) acc = madd(acc, D[t * g.S + k], conj_of(D[tp * g.S + k + m]));
+        for (long ch = 0; ch < g.Ch; ++ch)
+            for (long k = k0; k <= k1; ++k)
+                acc = madd(acc, D[(t * g.Ch + ch) * g.S + k], conj_of(D[(tp * g.Ch + ch) * g.S + k + m]));
         corr[blockIdx.x * W + j] = acc;
     }
 }
@@ -787,13 +791,27 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
     });
 }
 
+// The m windows of w samples of a minibatch (tm_gather_kernel): Y [B, Ch, N] -> Yw [m, Ch, w], X [B, T, C] ->
+// Xw [m, T, Cw], g the geometry of the signals with its g.Ch channels.  Both dcp_tm_gather_windows_* and
+// dcp_tm_mc_gather_windows_* are this function after their geometry.
+template <class T>
+inline int tm_gather_windows(dcp_handle* h, const T* Y, const T* X, const int64_t* idx_b, const int64_t* idx_n,
+                             int64_t m, const TmGeom& g, int64_t w, int padding, T* Yw, T* Xw) {
+    TmGeom gw;
+    if (!tm_geom(gw, m, g.T, g.S, w, g.s, padding) || w > g.N) return fail(h, DCP_ERR_INVALID, "window geometry");
+    if (!Y || !X || !idx_b || !idx_n || !Yw || !Xw) return fail(h, DCP_ERR_INVALID, "null pointer");
+    hipLaunchKernelGGL((tm_gather_kernel<T>), dim3(tm_grid(m * (g.Ch * w + g.T * gw.C))), dim3(256), 0, h->stream, Y, X,
+                       idx_b, idx_n, (long)m, g.Ch, g.N, g.T, g.C, (long)w, gw.C, Yw, Xw);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
 }  // namespace dcp
 
-#include "template_multichannel.hpp"   // the correlation pass, prepare and predict for templates D [T, Ch, S]
+#include "template_multichannel.hpp"   // the correlation pass and predict for templates D [T, Ch, S]
 #include "template_pursuit.hpp"   // matching pursuit on the same operator
 #include "template_omp.hpp"       // orthogonal (re-fitting) pursuit on the same operator
 #include "template_events.hpp"    // the dictionary step from event lists, for the codes of those two
-#include "template_mc_learn.hpp"  // that step for templates D [T, Ch, S]
 
 // ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip) ------------------------------
 #define DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding)                                    \
@@ -863,16 +881,8 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
                                          int64_t n_steps, double tol, int positive, int* it_out) {            \
         DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
         return dcp::tm_pursuit_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol,         \
-                                         positive, it_out);                                                    \
+                                         positive, it_out, false);                                             \
     }                                                                                                          \
-    extern "C" int dcp_tm_pursuit_lds_atoms_##SFX(void) { return (int)dcp::tm_pursuit_lds_atoms<TYPE>(); }    \
-    extern "C" int dcp_tm_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,          \
-                                     int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,           \
-                                     int64_t n_steps, double tol, int* it_out) {                              \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        return dcp::tm_omp_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol, it_out);    \
-    }                                                                                                          \
-    extern "C" int dcp_tm_omp_lds_atoms_##SFX(void) { return (int)dcp::tm_omp_lds_atoms<TYPE>(); }            \
     extern "C" int dcp_tm_mc_pursuit_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,   \
                                             int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,      \
                                             int padding, int64_t n_steps, double tol, int positive,            \
@@ -881,6 +891,14 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
         return dcp::tm_pursuit_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol,         \
                                          positive, it_out, true);                                              \
     }                                                                                                          \
+    extern "C" int dcp_tm_pursuit_lds_atoms_##SFX(void) { return (int)dcp::tm_pursuit_lds_atoms<TYPE>(); }    \
+    extern "C" int dcp_tm_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,          \
+                                     int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,           \
+                                     int64_t n_steps, double tol, int* it_out) {                              \
+        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
+        return dcp::tm_omp_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol, it_out,     \
+                                     false);                                                                   \
+    }                                                                                                          \
     extern "C" int dcp_tm_mc_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,       \
                                         int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,          \
                                         int padding, int64_t n_steps, double tol, int* it_out) {               \
@@ -888,6 +906,7 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
         return dcp::tm_omp_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol, it_out,     \
                                      true);                                                                    \
     }                                                                                                          \
+    extern "C" int dcp_tm_omp_lds_atoms_##SFX(void) { return (int)dcp::tm_omp_lds_atoms<TYPE>(); }            \
     extern "C" int dcp_tm_mc_predict_##SFX(dcp_handle* h, const void* X, const void* D, int64_t B,            \
                                             int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,      \
                                             int padding, void* out) {                                          \
@@ -913,9 +932,14 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
                                               int64_t stride, int padding, int acc_it, int64_t max_events,    \
                                               double* maxdiff) {                                               \
         DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        if (!Y || !X || !D || !XXt || !yX || !maxdiff) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
-        if (acc_it < 0) return dcp::fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");                           \
-        if (max_events < 1) return dcp::fail(h, DCP_ERR_INVALID, "max_events must be >= 1");                   \
+        return dcp::tm_dstep_events<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt, (TYPE*)yX, \
+                                          g, acc_it, max_events, maxdiff);                                     \
+    }                                                                                                          \
+    extern "C" int dcp_tm_mc_dstep_events_##SFX(dcp_handle* h, const void* Y, const void* X, void* D,         \
+                                                 void* XXt, void* yX, int64_t B, int64_t T_, int64_t Ch,       \
+                                                 int64_t S, int64_t N, int64_t stride, int padding,            \
+                                                 int acc_it, int64_t max_events, double* maxdiff) {            \
+        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
         return dcp::tm_dstep_events<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt, (TYPE*)yX, \
                                           g, acc_it, max_events, maxdiff);                                     \
     }                                                                                                          \
@@ -924,26 +948,8 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
                                                 int64_t B, int64_t T_, int64_t S, int64_t N, int64_t w,       \
                                                 int64_t stride, int padding, void* Yw, void* Xw) {            \
         DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        dcp::TmGeom gw;                                                                                        \
-        if (!dcp::tm_geom(gw, m, T_, S, w, stride, padding) || w > N)                                          \
-            return dcp::fail(h, DCP_ERR_INVALID, "window geometry");                                           \
-        if (!Y || !X || !idx_b || !idx_n || !Yw || !Xw) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
-        hipLaunchKernelGGL((dcp::tm_gather_kernel<TYPE>), dim3(dcp::tm_grid(m * (w + g.T * gw.C))), dim3(256), \
-                           0, h->stream, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, (long)m, 1L, g.N, g.T,  \
-                           g.C, (long)w, gw.C, (TYPE*)Yw, (TYPE*)Xw);                                          \
-        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
-        return DCP_OK;                                                                                         \
-    }                                                                                                          \
-    extern "C" int dcp_tm_mc_dstep_events_##SFX(dcp_handle* h, const void* Y, const void* X, void* D,         \
-                                                 void* XXt, void* yX, int64_t B, int64_t T_, int64_t Ch,       \
-                                                 int64_t S, int64_t N, int64_t stride, int padding,            \
-                                                 int acc_it, int64_t max_events, double* maxdiff) {            \
-        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
-        if (!Y || !X || !D || !XXt || !yX || !maxdiff) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
-        if (acc_it < 0) return dcp::fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");                           \
-        if (max_events < 1) return dcp::fail(h, DCP_ERR_INVALID, "max_events must be >= 1");                   \
-        return dcp::tm_mc_dstep_events<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt,          \
-                                             (TYPE*)yX, g, acc_it, max_events, maxdiff);                       \
+        return dcp::tm_gather_windows<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, m, g, w, padding, \
+                                            (TYPE*)Yw, (TYPE*)Xw);                                             \
     }                                                                                                          \
     extern "C" int dcp_tm_mc_gather_windows_##SFX(dcp_handle* h, const void* Y, const void* X,                \
                                                    const int64_t* idx_b, const int64_t* idx_n, int64_t m,     \
@@ -951,15 +957,8 @@ inline int tm_dstep(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, 
                                                    int64_t w, int64_t stride, int padding, void* Yw,          \
                                                    void* Xw) {                                                 \
         DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
-        dcp::TmGeom gw;                                                                                        \
-        if (!dcp::tm_geom(gw, m, T_, S, w, stride, padding) || w > N)                                          \
-            return dcp::fail(h, DCP_ERR_INVALID, "window geometry");                                           \
-        if (!Y || !X || !idx_b || !idx_n || !Yw || !Xw) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
-        hipLaunchKernelGGL((dcp::tm_gather_kernel<TYPE>), dim3(dcp::tm_grid(m * (g.Ch * w + g.T * gw.C))),     \
-                           dim3(256), 0, h->stream, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, (long)m,     \
-                           g.Ch, g.N, g.T, g.C, (long)w, gw.C, (TYPE*)Yw, (TYPE*)Xw);                          \
-        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
-        return DCP_OK;                                                                                         \
+        return dcp::tm_gather_windows<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, m, g, w, padding, \
+                                            (TYPE*)Yw, (TYPE*)Xw);                                             \
     }                                                                                                          \
     extern "C" int dcp_tm_scatter_windows_##SFX(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, \
                                                  const int64_t* idx_n, int64_t m, int64_t B, int64_t T_,      \

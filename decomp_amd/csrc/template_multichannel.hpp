@@ -1,5 +1,6 @@
 // Multichannel templates for the greedy coders (template_matching.pursuit / orthogonal_pursuit / predict with a 3-D D,
-// dcp_tm_mc_*).  Included from template_impl.hpp before template_pursuit.hpp, whose prepare step calls tm_mc_prepare.
+// dcp_tm_mc_*): the correlation pass and predict.  Included from template_impl.hpp before template_pursuit.hpp, whose
+// prepare step calls tm_mc_corr_pass.
 //
 // Model: y[b, ch, n] ~ sum_(t, c) x[b, t, c] D[t, ch, n - s c + Q]: the atom of (t, c) is the spatio-temporal waveform
 // A[(t, c), (ch, n)] = D[t, ch, n - s c + Q], one coefficient for all Ch channels.  The geometry (C, Q, dh, the flat
@@ -8,8 +9,11 @@
 //   rho2[t, c]       = sum_ch sum_k |D[t, ch, k]|^2                         over the taps inside [0, N)
 //   Corr[t, t', m]   = sum_ch sum_k D[t, ch, k] conj(D[t', ch, k + m])
 // and |y_b|^2 over the Ch N samples of a signal, so each gains a sum over the channels (TmGeom::Ch) and nothing else
-// in a step changes.  Every sum here runs ch ascending, k ascending inside, which at Ch = 1 is the order of the
-// one-channel kernels.
+// in a step changes.  Every sum runs ch ascending, k ascending inside.  rho2 and Corr come from the kernels every
+// coder uses (tm_pursuit_rho2_kernel, tm_lagcorr_kernel: their channel loop runs once at Ch = 1); alpha0 is the kernel
+// here, for every Ch the dcp_tm_mc_* entries are given, 1 included.  It is not tm_corr_store_kernel with a channel
+// loop: in the complex dtypes the two fuse different products of the multiply-add (tm_mc_madd below against madd), so
+// their bits differ and the entry point decides which one runs.
 //
 // tm_mc_corr_kernel (alpha0, the dominant cost: 2 B T C Ch S flop).  A 256-thread workgroup owns 256 consecutive c of
 // one signal and a block of TB templates; a thread holds TB accumulators.  The channels go in passes of CP: a pass
@@ -113,55 +117,13 @@ __global__ void __launch_bounds__(256) tm_mc_corr_kernel(const T* __restrict__ y
         if (t0 + j < g.T) alpha0[(b * g.T + t0 + j) * g.C + c] = acc[j];
 }
 
-// rho2[t, c] = sum_ch |A_(t,c)|^2 over its taps inside [0, N) (tm_pursuit_rho2_kernel with the channel loop); clears
-// *it_zero
+// alpha0 [B, T C] of the dcp_tm_mc_* coders, the batch in slices of at most 65535 signals (the grid's z extent).  With
+// dcp_profile_* on, the pass is timed under DCP_PROF_XUPDATE (as the one-channel pass is).
 template <class T>
-__global__ void __launch_bounds__(256) tm_mc_rho2_kernel(const T* __restrict__ D, TmGeom g, real_t<T>* __restrict__ rho2,
-                                                         int* __restrict__ it_zero) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *it_zero = 0;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < g.T * g.C; i += (long)gridDim.x * 256L) {
-        const long t = i / g.C, c = i % g.C;
-        const long base = g.s * c - g.Q;
-        long k0 = -base, k1 = g.N - 1 - base;
-        if (k0 < 0) k0 = 0;
-        if (k1 > g.S - 1) k1 = g.S - 1;
-        real_t<T> acc = 0;
-        for (long ch = 0; ch < g.Ch; ++ch)
-            for (long k = k0; k <= k1; ++k) acc += abs2(D[(t * g.Ch + ch) * g.S + k]);
-        rho2[i] = acc;
-    }
-}
-
-// corr[(t T + t') (2 S - 1) + m + S - 1] = sum_ch sum_k D[t, ch, k] conj(D[t', ch, k + m]) (tm_lagcorr_kernel with the
-// channel loop)
-template <class T>
-__global__ void __launch_bounds__(256) tm_mc_lagcorr_kernel(const T* __restrict__ D, TmGeom g, T* __restrict__ corr) {
-    const long t = blockIdx.x / g.T, tp = blockIdx.x % g.T;
-    const long W = 2 * g.S - 1;
-    for (long j = threadIdx.x; j < W; j += 256) {
-        const long m = j - (g.S - 1);
-        const long k0 = m < 0 ? -m : 0, k1 = m > 0 ? g.S - 1 - m : g.S - 1;
-        T acc = zero_of<T>();
-        for (long ch = 0; ch < g.Ch; ++ch)
-            for (long k = k0; k <= k1; ++k)
-                acc = madd(acc, D[(t * g.Ch + ch) * g.S + k], conj_of(D[(tp * g.Ch + ch) * g.S + k + m]));
-        corr[blockIdx.x * W + j] = acc;
-    }
-}
-
-// The prepare launches of the greedy coders on multichannel templates: rho2 [K], corr [T, T, 2 S - 1],
-// alpha0 [B, K]; clears *it_dev.  The batch goes in slices of at most 65535 signals (the grid's z extent).  With
-// dcp_profile_* on, the correlation pass is timed under DCP_PROF_XUPDATE (as the one-channel pass is).
-template <class T>
-inline int tm_mc_prepare(dcp_handle* h, const T* Y, const T* D, const TmGeom& g, real_t<T>* rho2, T* corr, T* alpha0,
-                         int* it_dev) {
+inline int tm_mc_corr_pass(dcp_handle* h, const T* Y, const T* D, const TmGeom& g, T* alpha0) {
     hipStream_t st = h->stream;
     constexpr int TB = tm_mc_template_block<T>();
     const long K = g.T * g.C;
-    hipLaunchKernelGGL((tm_mc_rho2_kernel<T>), dim3(tm_grid(K)), dim3(256), 0, st, D, g, rho2, it_dev);
-    DCP_LAUNCH_OK(h, hipGetLastError());
-    hipLaunchKernelGGL((tm_mc_lagcorr_kernel<T>), dim3(g.T * g.T), dim3(256), 0, st, D, g, corr);
-    DCP_LAUNCH_OK(h, hipGetLastError());
     int CP = tm_mc_channels_per_pass<T>(g.S, g.s);
     if (CP > g.Ch) CP = (int)g.Ch;
     const size_t bytes = (size_t)CP * (size_t)(255 * g.s + g.S) * sizeof(T);

@@ -306,7 +306,7 @@ inline int tm_omp_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeo
 
 template <class T>
 inline int tm_omp_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
-                      int* it_out, bool mc = false) {
+                      int* it_out, bool mc) {
     if (!Y || !D || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
     const int64_t K = (int64_t)g.T * g.C;
     if (K > 0x7fffff00LL) return fail(h, DCP_ERR_INVALID, "orthogonal pursuit: T C exceeds 2^31 - 257");

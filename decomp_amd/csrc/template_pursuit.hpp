@@ -16,7 +16,8 @@
 // explicit sum over the overlap inside [0, N).
 //
 // Kernels.  Prepare: rho2 (tm_pursuit_rho2_kernel), Corr (tm_lagcorr_kernel), alpha0 = y A^H for all (b, t, c)
-// (tm_corr_store_kernel: the correlation pass of the LASSO with a store-only epilogue).  Then tm_pursuit_kernel: one
+// (tm_corr_store_kernel: the correlation pass of the LASSO with a store-only epilogue; the dcp_tm_mc_* entries:
+// tm_mc_corr_kernel of template_multichannel.hpp).  Then tm_pursuit_kernel: one
 // 1024-thread workgroup (16 waves) per signal, the steps of a signal sequential, the signals concurrent; no waiting
 // between workgroups, no float atomics (one integer max per signal for the step count), the loop bounded by n_steps.
 // A step is a chain of dependent latencies, not of work, hence the wide workgroup: every phase is one pass.
@@ -46,8 +47,8 @@
 //
 // Multichannel templates (D [T, Ch, S], y [B, Ch, N], one coefficient per event for all channels; dcp_tm_mc_*): a step
 // reads y only through alpha0, rho2, Corr, the explicit overlap sum and |y|^2, so TmGeom::Ch (1 everywhere else) adds a
-// channel loop to the last two here, and tm_pursuit_prepare(mc) takes the first three from template_multichannel.hpp.
-// With Ch = 1 every loop is the one it was.
+// channel loop to the last four (rho2 and Corr: tm_row_norm2 and tm_lagcorr_kernel of template_impl.hpp), each run once
+// at Ch = 1, and tm_pursuit_prepare(mc) takes alpha0 from the correlation pass of template_multichannel.hpp.
 #pragma once
 #include "greedy.hpp"
 
@@ -293,18 +294,18 @@ __global__ void __launch_bounds__(kTmPursuitThreads) tm_pursuit_kernel(const T* 
 }
 
 // The prepare launches of the greedy coders: rho2 [K], the lag correlations corr [T, T, 2 S - 1], alpha0 = y A^H
-// [B, K]; clears *it_dev.  mc: D is [T, g.Ch, S] and y [B, g.Ch, N], by the kernels of template_multichannel.hpp
-// (for every Ch, 1 included).
+// [B, K]; clears *it_dev.  D is [T, g.Ch, S] and y [B, g.Ch, N].  mc (the dcp_tm_mc_* entries, for every Ch, 1
+// included) takes alpha0 from tm_mc_corr_kernel, else (g.Ch == 1) from tm_corr_store_kernel: the one place that chooses.
 template <class T>
 inline int tm_pursuit_prepare(dcp_handle* h, const T* Y, const T* D, const TmGeom& g, real_t<T>* rho2, T* corr,
                               T* alpha0, int* it_dev, bool mc) {
-    if (mc) return tm_mc_prepare<T>(h, Y, D, g, rho2, corr, alpha0, it_dev);
     hipStream_t st = h->stream;
     const long K = g.T * g.C;
     hipLaunchKernelGGL((tm_pursuit_rho2_kernel<T>), dim3(tm_grid(K)), dim3(256), 0, st, D, g, rho2, it_dev);
     DCP_LAUNCH_OK(h, hipGetLastError());
     hipLaunchKernelGGL((tm_lagcorr_kernel<T>), dim3(g.T * g.T), dim3(256), 0, st, D, g, corr);
     DCP_LAUNCH_OK(h, hipGetLastError());
+    if (mc) return tm_mc_corr_pass<T>(h, Y, D, g, alpha0);
     {   // alpha0, the batch in slices of at most 65535 signals (the grid's z extent)
         ProfScope ps(h, DCP_PROF_XUPDATE);
         const long span = 255 * g.s + g.S;
@@ -373,7 +374,7 @@ inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const T
 
 template <class T>
 inline int tm_pursuit_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
-                          int positive, int* it_out, bool mc = false) {
+                          int positive, int* it_out, bool mc) {
     if (!Y || !D || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
     const int64_t K = (int64_t)g.T * g.C;
     if (K > 0x7fffff00LL) return fail(h, DCP_ERR_INVALID, "pursuit: T C exceeds 2^31 - 257");

@@ -21,12 +21,16 @@ size is formed on the hot path (include/decomp_hip.h ``dcp_tm_*``, decomp_amd/cs
     per-row lists of the non-zero coefficients instead of all C of them, bit for bit the dense step's result
     (``dcp_tm_dstep_events_*``, decomp_amd/csrc/template_events.hpp);
   * ``pursuit``, ``orthogonal_pursuit`` and ``predict`` take multichannel templates D [T, Ch, S] (y [..., Ch, N], one
-    coefficient per event for all channels): every correlation, rho2 and |y|^2 gains a sum over the channels, the
-    correlation pass is a kernel of its own (``dcp_tm_mc_*``, decomp_amd/csrc/template_multichannel.hpp);
+    coefficient per event for all channels): every correlation, rho2 and |y|^2 gains a sum over the channels, in the
+    kernels the one-channel coders run too; only the correlation pass and ``predict`` are kernels of their own
+    (``dcp_tm_mc_*``, decomp_amd/csrc/template_multichannel.hpp);
   * ``solve`` with one of those greedy coders learns multichannel templates D [T, Ch, S] too: x is shared by the
     channels, so XXt stays the one-channel [T S, T S], only yX [T, Ch, S] gains the channel axis, the gradient step is
     XXt times the [T S, Ch] columns of D and a template is normalised over its Ch S entries
-    (``dcp_tm_mc_dstep_events_*``, decomp_amd/csrc/template_mc_learn.hpp).
+    (``dcp_tm_mc_dstep_events_*``, the same step of decomp_amd/csrc/template_events.hpp with Ch channels).
+
+A 2-D D calls the un-prefixed entries and a 3-D D (Ch = 1 included) the ``mc_`` ones; ``_entry`` is the one place that
+says which, and both reach the same C++ functions apart from the correlation pass and ``predict``.
 
 'cd', 'parallel_cd' and 'admm' have no structured form: for them ``_temp2mat`` is materialised on the
 device and the dense ``dcp_lasso_*`` solvers of decomp_amd.lasso run on it.  That path is correct but
@@ -232,15 +236,12 @@ def predict(x, D, size, stride=1, padding='SAME'):
     lead = tuple(xd.shape[:-2])
     x3 = xd.reshape((-1, T, C))
     B = x3.shape[0]
-    if Ch is not None:
-        out = torch.empty((B, Ch, size), dtype=xd.dtype, device=xd.device)
-        if B > 0:
-            _call(x3, 'mc_predict', x3, Dd, B, T, Ch, S, size, stride, _pad_code(padding), out)
-        return _arrays.to_caller(out.reshape(lead + (Ch, size)), kind)
-    out = torch.empty((B, size), dtype=xd.dtype, device=xd.device)
-    _call(x3, 'predict', x3, Dd, B, T, S, size, stride, _pad_code(padding),
-          out)
-    return _arrays.to_caller(out.reshape(lead + (size,)), kind)
+    entry, dims = _entry('predict', T, Ch, S)
+    chs = () if Ch is None else (Ch,)
+    out = torch.empty((B,) + chs + (size,), dtype=xd.dtype, device=xd.device)
+    if B > 0 or Ch is None:                                           # (templates [T, S]: the library refuses B = 0)
+        _call(x3, entry, x3, Dd, B, *(dims + (size, stride, _pad_code(padding), out)))
+    return _arrays.to_caller(out.reshape(lead + chs + (size,)), kind)
 
 
 def pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='SAME', positive=False):
@@ -349,9 +350,7 @@ def _pursuit_geometry(y, D, n_nonzero_coefs, tol, stride, padding):
     Ch = _channels(D)
     if len(y.shape) < (1 if Ch is None else 2):
         raise assertion.DimInvalidError('y must have at least %d dimension%s' % ((1, '') if Ch is None else (2, 's')))
-    if Ch is not None and int(y.shape[-2]) != Ch:
-        raise assertion.DimInvalidError('y{0} must be [..., Ch, N] with the Ch = {1:d} channels of the templates '
-                                        'D{2}'.format(tuple(y.shape), Ch, tuple(D.shape)))
+    _check_y_channels(y, D, Ch)
     T, S = int(D.shape[0]), int(D.shape[-1])
     N = int(y.shape[-1])
     stride, C = _geometry(T, S, N, stride, padding)
@@ -371,6 +370,19 @@ def _channels(D):
     return int(D.shape[1])
 
 
+def _check_y_channels(y, D, Ch):
+    """y [..., Ch, N] (at least 2-D) has the Ch channels of the templates D [T, Ch, S]; Ch None: nothing to check."""
+    if Ch is not None and int(y.shape[-2]) != Ch:
+        raise assertion.DimInvalidError('y{0} must be [..., Ch, N] with the Ch = {1:d} channels of the templates '
+                                        'D{2}'.format(tuple(y.shape), Ch, tuple(D.shape)))
+
+
+def _entry(name, T, Ch, S):
+    """The library entry for templates [T, S] (Ch None) or [T, Ch, S] and the template dimensions it takes:
+    (name, (T, S)) or ('mc_' + name, (T, Ch, S))."""
+    return (name, (T, S)) if Ch is None else ('mc_' + name, (T, Ch, S))
+
+
 def _learn_channels(y, D, lasso_method):
     """The channels of the templates ``solve`` is given (``_channels``), and for multichannel ones the checks on
     lasso_method and y [B, Ch, N] / [Ch, N].  No GPU call."""
@@ -383,9 +395,7 @@ def _learn_channels(y, D, lasso_method):
     if len(y.shape) not in (2, 3):
         raise assertion.DimInvalidError('y must be [B, Ch, N] or [Ch, N] for templates D [T, Ch, S], has %d '
                                         'dimension(s)' % len(y.shape))
-    if int(y.shape[-2]) != Ch:
-        raise assertion.DimInvalidError('y{0} must be [..., Ch, N] with the Ch = {1:d} channels of the templates '
-                                        'D{2}'.format(tuple(y.shape), Ch, tuple(D.shape)))
+    _check_y_channels(y, D, Ch)
     return Ch
 
 
@@ -411,27 +421,22 @@ def _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, T, S, N, stride, pa
 
 
 def _pursuit_call(name, kind, y, D, T, S, N, C, Ch, stride, padding, n_steps, tol_c, *flags):
-    """dcp_tm_<name>_* on the signals of y, flattened to [B, N], or with Ch channels (not None) dcp_tm_mc_<name>_* on
-    y flattened to [B, Ch, N]: (it, x [..., T, C])."""
+    """The coder ``_entry`` names, dcp_tm_<name>_* on the signals of y flattened to [B, N] or, with Ch channels (not
+    None), dcp_tm_mc_<name>_* on y flattened to [B, Ch, N]: (it, x [..., T, C])."""
     import torch
     yd = _arrays.to_device(y)
     Dd = _arrays.to_device(D, yd.device.index).contiguous()
     _same_device(yd, Dd)
     it = ctypes.c_int(0)
-    if Ch is None:
-        lead = tuple(yd.shape[:-1])
-        y2 = yd.reshape(-1, N).contiguous()
-    else:
-        lead = tuple(yd.shape[:-2])
-        y2 = yd.reshape(-1, Ch, N).contiguous()
+    entry, dims = _entry(name, T, Ch, S)
+    sig = (N,) if Ch is None else (Ch, N)                             # the dimensions of one signal
+    lead = tuple(yd.shape[:-len(sig)])
+    y2 = yd.reshape((-1,) + sig).contiguous()
     B = y2.shape[0]
-    if B > 0 and Ch is not None:
+    if B > 0:
         xd = torch.empty((B, T, C), dtype=yd.dtype, device=yd.device)
-        _call(y2, 'mc_' + name, y2, Dd, xd, B, T, Ch, S, N, stride, _pad_code(padding), n_steps, tol_c,
-              *(flags + (ctypes.byref(it),)))
-    elif B > 0:
-        xd = torch.empty((B, T, C), dtype=yd.dtype, device=yd.device)
-        _call(y2, name, y2, Dd, xd, B, T, S, N, stride, _pad_code(padding), n_steps, tol_c, *(flags + (ctypes.byref(it),)))
+        _call(y2, entry, y2, Dd, xd, B, *(dims + (N, stride, _pad_code(padding), n_steps, tol_c) + flags
+                                          + (ctypes.byref(it),)))
     else:
         xd = torch.zeros((0, T, C), dtype=yd.dtype, device=yd.device)
     return it.value, _arrays.to_caller(xd.reshape(lead + (T, C)), kind)
@@ -475,29 +480,22 @@ def _dstep(y, x, D, XXt, yX, stride, padding, acc_it):
 
 def _dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events):
     """``_dstep`` for a sparse x: the statistics are summed over lists of at most ``max_events`` non-zeros per
-    (signal, template) row (a row with more is walked in full).  The same bits as ``_dstep``; y and x finite."""
-    B, N = y.shape
-    T, S = D.shape
+    (signal, template) row (a row with more is walked in full).  The same bits as ``_dstep``; y and x finite.
+    With y [B, Ch, N] and D [T, Ch, S] (updated in place) yX is [T Ch S]; XXt stays [T S, T S]."""
+    entry, dims = _entry('dstep_events', int(D.shape[0]), _channels(D), int(D.shape[-1]))
     out = ctypes.c_double(0.0)
-    _call(y, 'dstep_events', y, x, D, XXt, yX,
-          B, T, S, N, stride, _pad_code(padding), int(acc_it), int(max_events), ctypes.byref(out))
+    _call(y, entry, y, x, D, XXt, yX, y.shape[0], *(dims + (y.shape[-1], stride, _pad_code(padding), int(acc_it),
+                                                            int(max_events), ctypes.byref(out))))
     return out.value
 
 
-def _mc_dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events):
-    """``_dstep_events`` for y [B, Ch, N], D [T, Ch, S] (updated in place), yX [T Ch S]; XXt [T S, T S]."""
-    B, Ch, N = y.shape
-    T, _, S = D.shape
-    out = ctypes.c_double(0.0)
-    _call(y, 'mc_dstep_events', y, x, D, XXt, yX,
-          B, T, Ch, S, N, stride, _pad_code(padding), int(acc_it), int(max_events), ctypes.byref(out))
-    return out.value
+_mc_dstep_events = _dstep_events   # the name tests/test_gpu_tm_mc_learn.py calls the step on a 3-D D by
 
 
 def _steps(N, D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol):
     """The two halves of an outer iteration on signals of N samples, (code(y, D, x), dstep(y, x, D, XXt, yX, acc_it)):
     the LASSO solver and the dense dictionary step, or for a greedy lasso_method its coder, which writes x entirely,
-    and the dictionary step on event lists (their multichannel forms for D [T, Ch, S])."""
+    and the dictionary step on event lists (the entries ``_entry`` names for D [T, S] or D [T, Ch, S])."""
     if lasso_method not in _GREEDY:
         def code(y, D, x):
             _lasso(y, D, x, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol)
@@ -510,21 +508,13 @@ def _steps(N, D, alpha, stride, padding, lasso_method, lasso_iter, lasso_tol):
     n_steps, tol_c, max_events = _greedy_args(lasso_method, alpha, lasso_iter, lasso_tol, T, S, N, stride, padding,
                                               _arrays.np_dtype(D))
     name, flags = _GREEDY[lasso_method]
+    entry, dims = _entry(name, T, Ch, S)
     stride = int(stride)
-    if Ch is not None:
-        def code(y, D, x):
-            it = ctypes.c_int(0)
-            _call(y, 'mc_' + name, y, D, x, y.shape[0], T, Ch, S, N, stride, _pad_code(padding), n_steps, tol_c,
-                  *(flags + (ctypes.byref(it),)))
-
-        def dstep(y, x, D, XXt, yX, acc_it):
-            return _mc_dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events)
-        return code, dstep
 
     def code(y, D, x):
         it = ctypes.c_int(0)
-        _call(y, name, y, D, x, y.shape[0], T, S, N, stride, _pad_code(padding), n_steps, tol_c,
-              *(flags + (ctypes.byref(it),)))
+        _call(y, entry, y, D, x, y.shape[0], *(dims + (N, stride, _pad_code(padding), n_steps, tol_c) + flags
+                                               + (ctypes.byref(it),)))
 
     def dstep(y, x, D, XXt, yX, acc_it):
         return _dstep_events(y, x, D, XXt, yX, stride, padding, acc_it, max_events)
@@ -658,17 +648,14 @@ def solve_minibatch(y, D, alpha, x, stride, padding, tol,
     XXt_sum = torch.zeros((T * S, T * S), dtype=D.dtype, device=D.device)
     yw = torch.empty((m,) + tuple(y.shape[1:-1]) + (w,), dtype=y.dtype, device=y.device)
     xw = torch.empty((m, T, cw), dtype=y.dtype, device=y.device)
-    if D.dim() == 3:
-        gather = ('mc_gather_windows', (B, T, int(D.shape[1]), S, N, w, stride, _pad_code(padding)))
-    else:
-        gather = ('gather_windows', (B, T, S, N, w, stride, _pad_code(padding)))
+    gather, dims = _entry('gather_windows', T, _channels(D), S)
     for it in range(1, maxiter):
         Dprev = D.clone()
         try:
             rows, starts = _draw_windows(rng, B, N, w, m, C, cw)
             ib = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(y.device)
             inn = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int64)).to(y.device)
-            _call(y, gather[0], y, x, ib, inn, m, *(gather[1] + (yw, xw)))
+            _call(y, gather, y, x, ib, inn, m, B, *(dims + (N, w, stride, _pad_code(padding), yw, xw)))
             code(yw, D, xw)
             _call(y, 'scatter_windows', xw, x, ib, inn, m,
                   B, T, S, N, w, stride, _pad_code(padding))

@@ -191,14 +191,21 @@ def test_errors_before_any_gpu_call(no_gpu):
         tm.predict(np.zeros((2, 34), dtype=np.float32), D[:, :0], 30)
 
 
-def test_solve_keeps_refusing_multichannel_templates():
-    from decomp_amd import template_matching as tm
+def test_solve_keeps_refusing_multichannel_templates(monkeypatch):
+    """solve with a 3-D D and a LASSO coder (the default acc_ista, and cd) raises NotImplementedError before any GPU
+    call.  (The greedy coders do learn multichannel templates: test_tm_mc_learn_host.py, test_gpu_tm_mc_learn.py.)"""
+    from decomp_amd import template_matching as tm, _arrays, _hip
+
+    def boom(*a, **k):
+        raise AssertionError('a GPU call was made before the argument check')
+    monkeypatch.setattr(_arrays, 'to_device', boom)
+    monkeypatch.setattr(_hip, 'load', boom)
     rng = np.random.RandomState(0)
     y = rng.randn(4, 3, 30)
     D = rng.randn(2, 3, 5)
-    for kw in (dict(alpha=0.1), dict(alpha=0, lasso_method='omp', lasso_iter=2), dict(alpha=0, lasso_method='mp', lasso_iter=2)):
-        with pytest.raises(Exception):
-            tm.solve(y, D, maxiter=1, **kw)
+    for kw in (dict(), dict(lasso_method='cd')):
+        with pytest.raises(NotImplementedError, match='multichannel'):
+            tm.solve(y, D, 0.1, maxiter=1, **kw)
 
 
 # ---- the C ABI lists the new entries ------------------------------------------------------------------------------

@@ -5,13 +5,13 @@ D [T, Ch, S] -- at the documented template shape,
 and the parts of one outer iteration, all in one process: the coder (dcp_tm_mc_omp_*, 16 events per signal) and the
 dictionary step (dcp_tm_mc_dstep_events_*, max_events = 16), event-timed, median of --runs runs after one warm-up run;
 in a pass of its own, with the library's profile brackets on, the step's split into its partial sums (compaction,
-tm_events_core_kernel, tm_mc_events_yx_kernel: DCP_PROF_MISC), the rest of the statistics (batch sums, edge terms,
+tm_events_core_kernel, tm_events_yx_kernel: DCP_PROF_MISC), the rest of the statistics (batch sums, edge terms,
 assembly: DCP_PROF_STATS less the former) and the update with the read-back (the remainder).  The outer iteration is a
 host clock around solve(maxiter = --iters + 1, tol = 0), which ends in a synchronisation, over --iters.
 The baseline is the only route to the same templates without the multichannel step: the one-channel solve on the
 channel-interleaved signal (y'[n Ch + ch], D'[t, k Ch + ch], stride Ch, 'VALID'), whose XXt is [(T Ch S)^2].
 --route interleaved times that route alone and uses nothing but the 2-D solve, so the same file runs on a tree without
-the multichannel step.  yx_floor_us is the time tm_mc_events_yx_kernel's traffic (every event reads Ch S samples of y,
+the multichannel step.  yx_floor_us is the time tm_events_yx_kernel's traffic (every event reads Ch S samples of y,
 every (signal, template) row writes Ch S partial sums) would take at --copy-tbps (6.29: the measured float4 copy rate
 of the device); its kernel time comes from a kernel trace.  y holds 160 planted events per signal plus noise.
 Prints one line per figure and a JSON summary line.
@@ -85,7 +85,7 @@ def main():
 
                     def step():          # (the step updates D in place: every run starts from the same D)
                         Dw.copy_(D)
-                        tm._mc_dstep_events(Y, X, Dw, XXt, yX, 1, 'VALID', 0, EVENTS)
+                        tm._dstep_events(Y, X, Dw, XXt, yX, 1, 'VALID', 0, EVENTS)
                     ms_c, _ = timed(coder, a.runs)
                     nnz = int((X != 0).sum(dim=(1, 2)).max())
                     ms_s, s_s = timed(step, a.runs)
