@@ -32,278 +32,142 @@ _c_int, _c_i64, _c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
 _c_f32, _c_f64 = ctypes.c_float, ctypes.c_double
 _P = ctypes.POINTER
 
-# name -> (restype, argtypes).  Kept in step with include/decomp_hip.h; the CPU test
-# tests/test_abi.py checks that every symbol the header declares is listed and exported.
-SIGNATURES = {
-    'dcp_create': (_c_int, [_P(_c_vp), _c_int]),
-    'dcp_destroy': (_c_int, [_c_vp]),
-    'dcp_set_stream': (_c_int, [_c_vp, _c_vp]),
-    'dcp_last_error_string': (ctypes.c_char_p, [_c_vp]),
-    'dcp_build_info': (ctypes.c_char_p, []),
-    'dcp_comm_unique_id': (_c_int, [_c_vp, _c_i64]),
-    'dcp_comm_init': (_c_int, [_c_vp, _c_vp, _c_int, _c_int]),
-    'dcp_comm_destroy': (_c_int, [_c_vp]),
-    'dcp_comm_set_external': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int]),
-    'dcp_memcpy': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64]),
-    'dcp_comm_info': (_c_int, [_c_vp, _P(_c_int), _P(_c_int)]),
-    'dcp_comm_allreduce_sum_f32': (_c_int, [_c_vp, _c_vp, _c_i64]),
-    'dcp_comm_allreduce_sum_f64': (_c_int, [_c_vp, _c_vp, _c_i64]),
-    'dcp_nmf_mu_sharded_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                                        _c_int, _c_f32, _c_int, _P(_c_int), _P(_c_f32)]),
-    'dcp_nmf_mu_sharded_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                                        _c_int, _c_f64, _c_int, _P(_c_int), _P(_c_f64)]),
-    'dcp_profile_enable': (_c_int, [_c_vp, _c_int]),
-    'dcp_profile_reset': (_c_int, [_c_vp]),
-    'dcp_profile_select': (_c_int, [_c_vp, ctypes.c_uint]),
-    'dcp_profile_read': (_c_int, [_c_vp, _c_int, _P(_c_f64), _P(_c_i64)]),
-    'dcp_profile_label_name': (ctypes.c_char_p, [_c_int]),
-    'dcp_l2_normalize_f32': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
-    'dcp_l2_normalize_f64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
-    'dcp_l2_normalize_c64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
-    'dcp_l2_normalize_c128': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
-    'dcp_count_negative_f32': (_c_int, [_c_vp, _c_vp, _c_i64, _P(_c_i64)]),
-    'dcp_count_negative_f64': (_c_int, [_c_vp, _c_vp, _c_i64, _P(_c_i64)]),
-    'dcp_gemm_f32': (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                              _c_int, _c_int]),
-    'dcp_gemm_f64': (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                              _c_int, _c_int]),
-    'dcp_gather_rows_bytes': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_scatter_rows_bytes': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_prefetch_rows_bytes': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_set_pcd_order': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64]),
-    'dcp_lasso_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_int, _P(_c_int)]),
-    'dcp_lasso_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_int, _P(_c_int)]),
-    'dcp_lasso_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_int, _P(_c_int)]),
-    'dcp_lasso_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_int, _P(_c_int)]),
-    'dcp_lasso_pcd_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_vp, _c_i64, _P(_c_int)]),
-    'dcp_lasso_admm_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_lasso_pcd_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_vp, _c_i64, _P(_c_int)]),
-    'dcp_lasso_admm_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_lasso_pcd_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_vp, _c_i64, _P(_c_int)]),
-    'dcp_lasso_admm_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_lasso_pcd_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_vp, _c_i64, _P(_c_int)]),
-    'dcp_lasso_admm_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_gram_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_gram_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_gram_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_gram_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_int)]),
-    'dcp_omp_mask_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_omp_mask_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_omp_mask_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_omp_mask_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_ksvd_sweep_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_ksvd_sweep_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_ksvd_sweep_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_ksvd_sweep_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_ksvd_step_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_ksvd_step_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_ksvd_step_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_ksvd_step_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_ksvd_mask_sweep_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_ksvd_mask_sweep_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_ksvd_mask_sweep_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_ksvd_mask_sweep_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_ksvd_mask_step_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int)]),
-    'dcp_ksvd_mask_step_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int)]),
-    'dcp_ksvd_mask_step_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int)]),
-    'dcp_ksvd_mask_step_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int)]),
-    'dcp_ksvd_clean_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_int), _P(_c_int)]),
-    'dcp_ksvd_clean_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_int), _P(_c_int)]),
-    'dcp_ksvd_clean_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_int), _P(_c_int)]),
-    'dcp_ksvd_clean_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_int), _P(_c_int)]),
-    'dcp_ksvd_clean_step_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int), _c_f64, _c_f64, _P(_c_int)]),
-    'dcp_ksvd_clean_step_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int), _c_f64, _c_f64, _P(_c_int)]),
-    'dcp_ksvd_clean_step_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int), _c_f64, _c_f64, _P(_c_int)]),
-    'dcp_ksvd_clean_step_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_int, _P(_c_f64), _P(_c_int), _c_f64, _c_f64, _P(_c_int)]),
-    'dcp_dict_stats_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
-    'dcp_dict_update_f32': (_c_int, [_c_vp, _c_vp, _c_f64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_step_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_dict_step_async_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
-    'dcp_gather_rows_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_stats_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
-    'dcp_dict_update_f64': (_c_int, [_c_vp, _c_vp, _c_f64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_step_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_dict_step_async_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
-    'dcp_gather_rows_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_stats_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
-    'dcp_dict_update_c64': (_c_int, [_c_vp, _c_vp, _c_f64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_step_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_dict_step_async_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
-    'dcp_gather_rows_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_stats_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
-    'dcp_dict_update_c128': (_c_int, [_c_vp, _c_vp, _c_f64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_step_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_dict_step_async_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P(_c_int)]),
-    'dcp_gather_rows_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_dict_mask_step_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_dict_mask_step_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_dict_mask_step_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_dict_mask_step_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_f64, _c_int, _c_int, _c_f64, _P(_c_f64), _P(_c_int)]),
-    'dcp_nmf_grads_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp]),
-    'dcp_nmf_grads_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp]),
-    'dcp_nmf_grad_x_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_nmf_grad_x_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_nmf_gauss_logp_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_f64)]),
-    'dcp_nmf_gauss_logp_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _P(_c_f64)]),
-    'dcp_set_nmf_beta': (_c_int, [_c_vp, _c_f64]),
-    'dcp_set_nmf_penalty': (_c_int, [_c_vp, _c_f64, _c_f64]),
-    'dcp_nmf_beta_divergence_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _P(_c_f64)]),
-    'dcp_nmf_beta_divergence_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _P(_c_f64)]),
-    'dcp_nmf_apply_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_f64, _c_vp, _c_i64, _c_i64, _P(_c_f64)]),
-    'dcp_nmf_apply_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_f64, _c_vp, _c_i64, _c_i64, _P(_c_f64)]),
-    'dcp_axpby_f32': (_c_int, [_c_vp, _c_i64, _c_f64, _c_vp, _c_f64, _c_vp]),
-    'dcp_axpby_f64': (_c_int, [_c_vp, _c_i64, _c_f64, _c_vp, _c_f64, _c_vp]),
-    'dcp_mu_quotient_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_mu_quotient_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_l2_normalize_diff_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_l2_normalize_diff_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int, _P(_c_f64)]),
-    'dcp_gershgorin_f32': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_gershgorin_f64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_gershgorin_c64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_gershgorin_c128': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_inv_f32': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_inv_f64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_inv_c64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_inv_c128': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
-    'dcp_debug_tn_plain': (_c_int, [_c_int]),
-    'dcp_debug_gemm_route': (_c_int, [_c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int,
-                                      _c_int, _c_vp]),
-    'dcp_gemm_bf16x6_f32': (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int]),
-    'dcp_set_f32_product_mode': (_c_int, [_c_vp, _c_int]),
-    'dcp_calib_read_f32': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_gemm_c64': (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                              _c_int, _c_int]),
-    'dcp_gemm_c128': (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                              _c_int, _c_int]),
-    'dcp_nmf_mu_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                                _c_int, _c_f32, _c_int, _P(_c_int), _P(_c_f32), _P(_c_f32)]),
-    'dcp_nmf_mu_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                                _c_int, _c_f64, _c_int, _P(_c_int), _P(_c_f64), _P(_c_f64)]),
-    'dcp_nmf_hals_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f32, _c_int,
-                                  _P(_c_int), _P(_c_f32), _P(_c_f32)]),
-    'dcp_nmf_hals_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int,
-                                  _P(_c_int), _P(_c_f64), _P(_c_f64)]),
-    'dcp_nmf_hals_sharded_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f32, _c_int,
-                                          _P(_c_int), _P(_c_f32)]),
-    'dcp_nmf_hals_sharded_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int,
-                                          _P(_c_int), _P(_c_f64)]),
-    'dcp_nmf_impute_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
-    'dcp_nmf_impute_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
-    'dcp_nmf_emhals_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f32, _c_int,
-                                    _P(_c_int), _P(_c_f32), _P(_c_f32)]),
-    'dcp_nmf_emhals_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64, _c_int,
-                                    _P(_c_int), _P(_c_f64), _P(_c_f64)]),
-    'dcp_nmf_emhals_sharded_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f32,
-                                            _c_int, _P(_c_int), _P(_c_f32)]),
-    'dcp_nmf_emhals_sharded_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_f64,
-                                            _c_int, _P(_c_int), _P(_c_f64)]),
-    'dcp_nmf_hals_stats_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
-    'dcp_nmf_hals_stats_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
-    'dcp_nmf_hals_update_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
-    'dcp_nmf_hals_update_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
-    'dcp_nn_cd_sweep_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
-    'dcp_nn_cd_sweep_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
-    'dcp_nmf_mu_stats_width': (_c_i64, [_c_i64, _c_i64, _c_int, _c_int]),
-    'dcp_nmf_mu_stats_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64,
-                                      _c_i64, _c_int, _c_vp]),
-    'dcp_nmf_mu_stats_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64,
-                                      _c_i64, _c_int, _c_vp]),
-    'dcp_nmf_mask_bits_words': (_c_i64, [_c_i64, _c_i64]),
-    'dcp_nmf_mask_prepare_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _P(_c_int)]),
-    'dcp_nmf_mask_prepare_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _P(_c_int)]),
-    'dcp_nmf_mu_stats_prepared_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64,
-                                               _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_nmf_mu_stats_prepared_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64,
-                                               _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_nmf_mu_update_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int,
-                                       _c_int, _c_vp, _c_vp]),
-    'dcp_nmf_mu_update_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_int,
-                                       _c_int, _c_vp, _c_vp]),
-    'dcp_nmf_residual_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                                      _P(_c_f64)]),
-    'dcp_nmf_residual_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64,
-                                      _P(_c_f64)]),
-    'dcp_tm_temp2mat_f32': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_temp2mat_f64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_temp2mat_c64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_temp2mat_c128': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_coef2mat_f32': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_coef2mat_f64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_coef2mat_c64': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_coef2mat_c128': (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_predict_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_predict_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_predict_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_predict_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_lasso_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_f64, _c_int, _c_int, _c_int, _P(_c_int)]),
-    'dcp_tm_lasso_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_f64, _c_int, _c_int, _c_int, _P(_c_int)]),
-    'dcp_tm_lasso_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_f64, _c_int, _c_int, _c_int, _P(_c_int)]),
-    'dcp_tm_lasso_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f64, _c_f64, _c_int, _c_int, _c_int, _P(_c_int)]),
-    'dcp_tm_dstep_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _P(_c_f64)]),
-    'dcp_tm_dstep_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _P(_c_f64)]),
-    'dcp_tm_dstep_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _P(_c_f64)]),
-    'dcp_tm_dstep_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _P(_c_f64)]),
-    'dcp_tm_dstep_events_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
-    'dcp_tm_dstep_events_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
-    'dcp_tm_dstep_events_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
-    'dcp_tm_dstep_events_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
-    'dcp_tm_gather_windows_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_tm_gather_windows_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_tm_gather_windows_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_tm_gather_windows_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_tm_scatter_windows_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
-    'dcp_tm_scatter_windows_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
-    'dcp_tm_scatter_windows_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
-    'dcp_tm_scatter_windows_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
-    'dcp_tm_pursuit_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_tm_pursuit_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_tm_pursuit_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_tm_pursuit_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_tm_pursuit_lds_atoms_f32': (_c_int, []),
-    'dcp_tm_pursuit_lds_atoms_f64': (_c_int, []),
-    'dcp_tm_pursuit_lds_atoms_c64': (_c_int, []),
-    'dcp_tm_pursuit_lds_atoms_c128': (_c_int, []),
-    'dcp_tm_omp_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
-    'dcp_tm_omp_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
-    'dcp_tm_omp_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
-    'dcp_tm_omp_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
-    'dcp_tm_omp_lds_atoms_f32': (_c_int, []),
-    'dcp_tm_omp_lds_atoms_f64': (_c_int, []),
-    'dcp_tm_omp_lds_atoms_c64': (_c_int, []),
-    'dcp_tm_omp_lds_atoms_c128': (_c_int, []),
-    'dcp_tm_mc_pursuit_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_tm_mc_pursuit_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_tm_mc_pursuit_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_tm_mc_pursuit_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _c_int, _P(_c_int)]),
-    'dcp_tm_mc_omp_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
-    'dcp_tm_mc_omp_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
-    'dcp_tm_mc_omp_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
-    'dcp_tm_mc_omp_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_f64, _P(_c_int)]),
-    'dcp_tm_mc_predict_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_mc_predict_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_mc_predict_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_mc_predict_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
-    'dcp_tm_mc_template_block_f32': (_c_int, []),
-    'dcp_tm_mc_template_block_f64': (_c_int, []),
-    'dcp_tm_mc_template_block_c64': (_c_int, []),
-    'dcp_tm_mc_template_block_c128': (_c_int, []),
-    'dcp_tm_mc_channels_per_pass_f32': (_c_int, [_c_i64, _c_i64]),
-    'dcp_tm_mc_channels_per_pass_f64': (_c_int, [_c_i64, _c_i64]),
-    'dcp_tm_mc_channels_per_pass_c64': (_c_int, [_c_i64, _c_i64]),
-    'dcp_tm_mc_channels_per_pass_c128': (_c_int, [_c_i64, _c_i64]),
-    'dcp_tm_mc_dstep_events_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
-    'dcp_tm_mc_dstep_events_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
-    'dcp_tm_mc_dstep_events_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
-    'dcp_tm_mc_dstep_events_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _P(_c_f64)]),
-    'dcp_tm_mc_gather_windows_f32': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_tm_mc_gather_windows_f64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_tm_mc_gather_windows_c64': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-    'dcp_tm_mc_gather_windows_c128': (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
-}
+# The C ABI by family: (stem, suffixes, argtypes[, restype]).  A family is one prototype of include/decomp_hip.h in the
+# dtypes it exists in (None: a single function without a suffix); restype defaults to int.  The handle and every
+# device array travel as void*.  Where the C type follows the dtype the list names it: _REAL is the float / double
+# scalar of the dtype, _P_REAL a host pointer to it.  tests/test_abi.py parses the header and checks every return
+# type, argument count and argument type of the resulting SIGNATURES against it.
+_ALL = ('f32', 'f64', 'c64', 'c128')
+_REALS = ('f32', 'f64')
+_REAL, _P_REAL = object(), object()
+_REAL_OF = {'f32': _c_f32, 'f64': _c_f64, 'c64': _c_f32, 'c128': _c_f64}
+_P_INT, _P_F64 = _P(_c_int), _P(_c_f64)
+_NFK = [_c_i64] * 3                 # N, F, K
+_TM = [_c_i64] * 5 + [_c_int]       # B, T, S, N, stride, padding
+_TM_MC = [_c_i64] * 6 + [_c_int]    # B, T, Ch, S, N, stride, padding
+_MASKED = [_c_vp] * 3 + [_c_int, _c_vp, _c_vp] + _NFK   # h, Y, mask, mask_ndim, two more arrays, N, F, K
+
+_FAMILIES = [
+    # lifetime, communicator, profile
+    ('dcp_create', None, [_P(_c_vp), _c_int]),
+    ('dcp_destroy', None, [_c_vp]),
+    ('dcp_set_stream', None, [_c_vp, _c_vp]),
+    ('dcp_last_error_string', None, [_c_vp], ctypes.c_char_p),
+    ('dcp_build_info', None, [], ctypes.c_char_p),
+    ('dcp_comm_unique_id', None, [_c_vp, _c_i64]),
+    ('dcp_comm_init', None, [_c_vp, _c_vp, _c_int, _c_int]),
+    ('dcp_comm_destroy', None, [_c_vp]),
+    ('dcp_comm_set_external', None, [_c_vp] * 3 + [_c_int, _c_int]),
+    ('dcp_memcpy', None, [_c_vp] * 3 + [_c_i64]),
+    ('dcp_comm_info', None, [_c_vp, _P_INT, _P_INT]),
+    ('dcp_comm_allreduce_sum', _REALS, [_c_vp, _c_vp, _c_i64]),
+    ('dcp_profile_enable', None, [_c_vp, _c_int]),
+    ('dcp_profile_reset', None, [_c_vp]),
+    ('dcp_profile_select', None, [_c_vp, ctypes.c_uint]),
+    ('dcp_profile_read', None, [_c_vp, _c_int, _P_F64, _P(_c_i64)]),
+    ('dcp_profile_label_name', None, [_c_int], ctypes.c_char_p),
+    # utilities and test hooks
+    ('dcp_l2_normalize', _ALL, [_c_vp, _c_vp, _c_i64, _c_i64, _c_int]),
+    ('dcp_l2_normalize_diff', _REALS, [_c_vp] * 4 + [_c_i64, _c_i64, _c_int, _P_F64]),
+    ('dcp_count_negative', _REALS, [_c_vp, _c_vp, _c_i64, _P(_c_i64)]),
+    ('dcp_gershgorin', _ALL, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
+    ('dcp_inv', _ALL, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
+    ('dcp_mu_quotient', _REALS, [_c_vp] * 4 + [_c_i64, _c_i64, _c_vp]),
+    ('dcp_axpby', _REALS, [_c_vp, _c_i64, _c_f64, _c_vp, _c_f64, _c_vp]),
+    ('dcp_gemm', _ALL, [_c_vp, _c_int] + [_c_vp] * 3 + _NFK + [_c_int, _c_int]),
+    ('dcp_gemm_bf16x6', ('f32',), [_c_vp, _c_int] + [_c_vp] * 3 + _NFK + [_c_int]),
+    ('dcp_set_f32_product_mode', None, [_c_vp, _c_int]),
+    ('dcp_debug_tn_plain', None, [_c_int]),
+    ('dcp_debug_gemm_route', None, [_c_int, _c_int] + [_c_i64] * 4 + [_c_int] * 5 + [_c_vp]),
+    ('dcp_calib_read', ('f32',), [_c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp]),
+    # row movers
+    ('dcp_gather_rows_bytes', None, [_c_vp] * 3 + [_c_i64, _c_i64, _c_vp]),
+    ('dcp_scatter_rows_bytes', None, [_c_vp] * 3 + [_c_i64, _c_i64, _c_vp]),
+    ('dcp_dict_prefetch_rows_bytes', None, [_c_vp] * 3 + [_c_i64, _c_i64, _c_vp]),
+    ('dcp_gather_rows', _ALL, [_c_vp] * 3 + [_c_i64, _c_i64, _c_vp]),
+    # NMF: tol and the host scalars it is compared with are float in f32, double in f64
+    ('dcp_nmf_mu', _REALS, [_c_vp] * 5 + _NFK + [_c_int, _REAL, _c_int, _P_INT, _P_REAL, _P_REAL]),
+    ('dcp_nmf_mu_sharded', _REALS, [_c_vp] * 5 + _NFK + [_c_int, _REAL, _c_int, _P_INT, _P_REAL]),
+    ('dcp_nmf_hals', _REALS, [_c_vp] * 4 + _NFK + [_REAL, _c_int, _P_INT, _P_REAL, _P_REAL]),
+    ('dcp_nmf_hals_sharded', _REALS, [_c_vp] * 4 + _NFK + [_REAL, _c_int, _P_INT, _P_REAL]),
+    ('dcp_nmf_emhals', _REALS, [_c_vp] * 5 + _NFK + [_REAL, _c_int, _P_INT, _P_REAL, _P_REAL]),
+    ('dcp_nmf_emhals_sharded', _REALS, [_c_vp] * 5 + _NFK + [_REAL, _c_int, _P_INT, _P_REAL]),
+    ('dcp_nmf_impute', _REALS, [_c_vp] * 5 + _NFK + [_c_vp]),
+    ('dcp_nmf_hals_stats', _REALS, [_c_vp] * 5 + _NFK + [_c_vp]),
+    ('dcp_nmf_hals_update', _REALS, [_c_vp] * 5 + _NFK + [_c_vp, _c_vp]),
+    ('dcp_nn_cd_sweep', _REALS, [_c_vp] * 5 + [_c_i64, _c_i64, _c_int]),
+    ('dcp_nmf_mu_stats_width', None, [_c_i64, _c_i64, _c_int, _c_int], _c_i64),
+    ('dcp_nmf_mu_stats', _REALS, [_c_vp] * 6 + _NFK + [_c_int, _c_vp]),
+    ('dcp_nmf_mask_bits_words', None, [_c_i64, _c_i64], _c_i64),
+    ('dcp_nmf_mask_prepare', _REALS, [_c_vp] * 3 + [_c_i64, _c_i64, _c_vp, _c_vp, _P_INT]),
+    ('dcp_nmf_mu_stats_prepared', _REALS, [_c_vp] * 7 + _NFK + [_c_int, _c_vp]),
+    ('dcp_nmf_mu_update', _REALS, [_c_vp] * 4 + [_c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp]),
+    ('dcp_nmf_grads', _REALS, [_c_vp] * 5 + _NFK + [_c_int, _c_int, _c_vp, _c_vp]),
+    ('dcp_nmf_grad_x', _REALS, [_c_vp] * 5 + _NFK + [_c_int, _c_vp, _c_vp]),
+    ('dcp_nmf_gauss_logp', _REALS, [_c_vp] * 5 + _NFK + [_c_f64, _P_F64]),
+    ('dcp_set_nmf_beta', None, [_c_vp, _c_f64]),
+    ('dcp_set_nmf_penalty', None, [_c_vp, _c_f64, _c_f64]),
+    ('dcp_nmf_beta_divergence', _REALS, [_c_vp] * 5 + _NFK + [_P_F64]),
+    ('dcp_nmf_apply', _REALS, [_c_vp] * 4 + [_c_f64, _c_vp, _c_i64, _c_i64, _P_F64]),
+    ('dcp_nmf_residual', _REALS, [_c_vp] * 5 + _NFK + [_P_F64]),
+    # LASSO, OMP, K-SVD
+    ('dcp_lasso', _ALL, _MASKED + [_c_f64, _c_f64, _c_int, _c_int, _c_int, _P_INT]),
+    ('dcp_lasso_pcd', _ALL, _MASKED + [_c_f64, _c_f64, _c_int, _c_int, _c_vp, _c_i64, _P_INT]),
+    ('dcp_lasso_admm', _ALL, _MASKED + [_c_f64, _c_f64, _c_int, _c_int, _c_f64, _P_INT]),
+    ('dcp_omp', _ALL, [_c_vp] * 4 + _NFK + [_c_int, _c_f64, _P_INT]),
+    ('dcp_omp_gram', _ALL, [_c_vp] * 5 + [_c_i64, _c_i64, _c_int, _c_f64, _P_INT]),
+    ('dcp_omp_mask', _ALL, _MASKED + [_c_int, _c_f64, _c_int, _P_INT]),
+    ('dcp_ksvd_sweep', _ALL, [_c_vp] * 4 + _NFK + [_c_int, _P_F64]),
+    ('dcp_ksvd_step', _ALL, [_c_vp] * 4 + _NFK + [_c_int, _c_f64, _P_F64, _P_INT]),
+    ('dcp_ksvd_mask_sweep', _ALL, _MASKED + [_c_int, _P_F64]),
+    ('dcp_ksvd_mask_step', _ALL, _MASKED + [_c_int, _c_f64, _c_int, _P_F64, _P_INT]),
+    ('dcp_ksvd_clean', _ALL, _MASKED + [_c_f64, _P_INT, _P_INT]),
+    ('dcp_ksvd_clean_step', _ALL, _MASKED + [_c_int, _c_f64, _c_int, _P_F64, _P_INT, _c_f64, _c_f64, _P_INT]),
+    # dictionary learning
+    ('dcp_dict_set_pcd_order', None, [_c_vp, _c_vp, _c_i64, _c_i64]),
+    ('dcp_dict_stats', _ALL, [_c_vp] * 4 + _NFK + [_c_f64, _c_int, _c_int, _c_f64, _c_vp, _P_INT]),
+    ('dcp_dict_update', _ALL, [_c_vp, _c_vp, _c_f64] + [_c_vp] * 4 + [_c_i64, _c_i64, _c_vp]),
+    ('dcp_dict_step', _ALL, [_c_vp] * 7 + _NFK + [_c_f64, _c_f64, _c_int, _c_int, _c_f64, _P_F64, _P_INT]),
+    ('dcp_dict_step_async', _ALL, [_c_vp] * 7 + _NFK + [_c_f64, _c_f64, _c_int, _c_int, _c_f64, _c_vp, _P_INT]),
+    ('dcp_dict_mask_step', _ALL, [_c_vp] * 8 + _NFK + [_c_f64, _c_f64, _c_int, _c_int, _c_f64, _P_F64, _P_INT]),
+    # template matching; the dcp_tm_mc_* twins carry Ch after T
+    ('dcp_tm_temp2mat', _ALL, [_c_vp, _c_vp] + _TM[1:] + [_c_vp]),
+    ('dcp_tm_coef2mat', _ALL, [_c_vp, _c_vp] + _TM + [_c_vp]),
+    ('dcp_tm_predict', _ALL, [_c_vp] * 3 + _TM + [_c_vp]),
+    ('dcp_tm_mc_predict', _ALL, [_c_vp] * 3 + _TM_MC + [_c_vp]),
+    ('dcp_tm_lasso', _ALL, [_c_vp] * 4 + _TM + [_c_f64, _c_f64, _c_int, _c_int, _c_int, _P_INT]),
+    ('dcp_tm_pursuit', _ALL, [_c_vp] * 4 + _TM + [_c_i64, _c_f64, _c_int, _P_INT]),
+    ('dcp_tm_mc_pursuit', _ALL, [_c_vp] * 4 + _TM_MC + [_c_i64, _c_f64, _c_int, _P_INT]),
+    ('dcp_tm_omp', _ALL, [_c_vp] * 4 + _TM + [_c_i64, _c_f64, _P_INT]),
+    ('dcp_tm_mc_omp', _ALL, [_c_vp] * 4 + _TM_MC + [_c_i64, _c_f64, _P_INT]),
+    ('dcp_tm_pursuit_lds_atoms', _ALL, []),
+    ('dcp_tm_omp_lds_atoms', _ALL, []),
+    ('dcp_tm_mc_template_block', _ALL, []),
+    ('dcp_tm_mc_channels_per_pass', _ALL, [_c_i64, _c_i64]),
+    ('dcp_tm_dstep', _ALL, [_c_vp] * 6 + _TM + [_c_int, _P_F64]),
+    ('dcp_tm_dstep_events', _ALL, [_c_vp] * 6 + _TM + [_c_int, _c_i64, _P_F64]),
+    ('dcp_tm_mc_dstep_events', _ALL, [_c_vp] * 6 + _TM_MC + [_c_int, _c_i64, _P_F64]),
+    # ... m, B, T, [Ch,] S, N, w, stride, padding ...
+    ('dcp_tm_gather_windows', _ALL, [_c_vp] * 5 + [_c_i64] * 7 + [_c_int, _c_vp, _c_vp]),
+    ('dcp_tm_mc_gather_windows', _ALL, [_c_vp] * 5 + [_c_i64] * 8 + [_c_int, _c_vp, _c_vp]),
+    ('dcp_tm_scatter_windows', _ALL, [_c_vp] * 5 + [_c_i64] * 7 + [_c_int]),
+]
+
+
+def _signatures():
+    """name -> (restype, argtypes) for every entry point of every family."""
+    out = {}
+    for stem, suffixes, args, *res in _FAMILIES:
+        for sfx in suffixes or (None,):
+            real = _REAL_OF.get(sfx)
+            of = {_REAL: real, _P_REAL: real and _P(real)}
+            name = stem if sfx is None else '%s_%s' % (stem, sfx)
+            assert name not in out, name
+            out[name] = (res[0] if res else _c_int, [of.get(a, a) for a in args])
+    return out
+
+
+SIGNATURES = _signatures()
 
 _lib = None
 _lock = threading.Lock()

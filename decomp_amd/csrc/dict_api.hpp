@@ -284,7 +284,7 @@ inline int dict_mask_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, T* 
 }
 
 template <class T>
-inline int gather_rows_api(dcp_handle* h, const T* in, const long long* index, int64_t rows, int64_t cols,
+inline int gather_rows_api(dcp_handle* h, const T* in, const int64_t* index, int64_t rows, int64_t cols,
                            T* out) {
     if (!h) return DCP_ERR_INVALID;
     if (!in || !index || !out) return fail(h, DCP_ERR_INVALID, "null pointer");
@@ -292,9 +292,49 @@ inline int gather_rows_api(dcp_handle* h, const T* in, const long long* index, i
     if (rows == 0 || cols == 0) return DCP_OK;
     DCP_HIP_OK(h, hipSetDevice(h->device));
     hipLaunchKernelGGL((gather_rows_kernel<T>), dim3(grid_for((long)rows * cols, 4096)), dim3(256), 0,
-                       h->stream, in, index, (long)rows, (long)cols, out);
+                       h->stream, in, reinterpret_cast<const long long*>(index), (long)rows, (long)cols, out);
     DCP_HIP_OK(h, hipGetLastError());
     return DCP_OK;
 }
 
 }  // namespace dcp
+
+// ---- C ABI: the dictionary-learning step (one expansion per dtype: dict_{f32,f64,c64,c128}.hip; see
+// include/decomp_hip.h; reference decomp/dictionary_learning.py:135-164, decomp/utils/data.py:147-156) ----
+#define DCP_DICT_ABI(SFX, T, P, R)                                                                                   \
+    extern "C" int dcp_dict_stats_##SFX(dcp_handle* h, const P* Y, P* X, const P* D, int64_t Nb, int64_t F,          \
+                                        int64_t K, double alpha, int lasso_method, int lasso_iter,                   \
+                                        double lasso_tol, P* stats, int* lasso_it) {                                 \
+        return dcp::dict_stats_api<T>(h, (const T*)Y, (T*)X, (const T*)D, Nb, F, K, alpha, lasso_method, lasso_iter, \
+                                      lasso_tol, (T*)stats, lasso_it);                                               \
+    }                                                                                                                \
+    extern "C" int dcp_dict_update_##SFX(dcp_handle* h, const P* stats, double beta, P* A, P* B, const P* D,         \
+                                         P* D_new, int64_t F, int64_t K, R* maxdiff_dev) {                           \
+        return dcp::dict_update_api<T>(h, (const T*)stats, beta, (T*)A, (T*)B, (const T*)D, (T*)D_new, F, K,         \
+                                       maxdiff_dev);                                                                 \
+    }                                                                                                                \
+    extern "C" int dcp_dict_step_##SFX(dcp_handle* h, const P* Y, P* X, const P* D, P* D_new, P* A, P* B,            \
+                                       int64_t Nb, int64_t F, int64_t K, double beta, double alpha,                  \
+                                       int lasso_method, int lasso_iter, double lasso_tol, double* maxdiff,          \
+                                       int* lasso_it) {                                                              \
+        return dcp::dict_step_api<T>(h, (const T*)Y, (T*)X, (const T*)D, (T*)D_new, (T*)A, (T*)B, Nb, F, K, beta,    \
+                                     alpha, lasso_method, lasso_iter, lasso_tol, maxdiff, lasso_it);                 \
+    }                                                                                                                \
+    extern "C" int dcp_dict_step_async_##SFX(dcp_handle* h, const P* Y, P* X, const P* D, P* D_new, P* A, P* B,      \
+                                             int64_t Nb, int64_t F, int64_t K, double beta, double alpha,            \
+                                             int lasso_method, int lasso_iter, double lasso_tol, R* maxdiff_dev,     \
+                                             int* lasso_it) {                                                        \
+        return dcp::dict_step_async_api<T>(h, (const T*)Y, (T*)X, (const T*)D, (T*)D_new, (T*)A, (T*)B, Nb, F, K,    \
+                                           beta, alpha, lasso_method, lasso_iter, lasso_tol, maxdiff_dev, lasso_it); \
+    }                                                                                                                \
+    extern "C" int dcp_gather_rows_##SFX(dcp_handle* h, const P* in, const int64_t* index, int64_t rows,             \
+                                         int64_t cols, P* out) {                                                     \
+        return dcp::gather_rows_api<T>(h, (const T*)in, index, rows, cols, (T*)out);                                 \
+    }                                                                                                                \
+    extern "C" int dcp_dict_mask_step_##SFX(dcp_handle* h, const P* Y, const R* mask, P* X, const P* D, P* D_new,    \
+                                            P* A3, P* B, int64_t Nb, int64_t F, int64_t K, double beta,              \
+                                            double alpha, int lasso_method, int lasso_iter, double lasso_tol,        \
+                                            double* maxdiff, int* lasso_it) {                                        \
+        return dcp::dict_mask_step_api<T>(h, (const T*)Y, mask, (T*)X, (const T*)D, (T*)D_new, (T*)A3, (T*)B, Nb, F, \
+                                          K, beta, alpha, lasso_method, lasso_iter, lasso_tol, maxdiff, lasso_it);   \
+    }

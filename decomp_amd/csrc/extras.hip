@@ -3,6 +3,7 @@
 //   decomp/nmf_methods/grads.py:77-93    Likelihood.update_x / update_d quotient (the rule a
 //                                        user-supplied Likelihood inherits)
 //   decomp/math_utils/linalg.py:9-38     inv (batched np.linalg.inv)
+#include "abi.hpp"
 #include "handle.hpp"
 #include "kernels_small.hpp"
 
@@ -195,21 +196,17 @@ int inv_api(dcp_handle* h, const T* X, int64_t batch, int64_t n, T* out) {
 
 }  // namespace
 
+#define DCP_EXTRAS_ABI(SFX, T, P, R)                                                                       \
+    extern "C" int dcp_inv_##SFX(dcp_handle* h, const P* X, int64_t batch, int64_t n, P* out) {            \
+        return inv_api<T>(h, (const T*)X, batch, n, (T*)out);                                              \
+    }                                                                                                      \
+    extern "C" int dcp_gershgorin_##SFX(dcp_handle* h, const P* X, int64_t batch, int64_t n, R* out) {     \
+        return gershgorin_api<T>(h, (const T*)X, batch, n, out);                                           \
+    }
+
+DCP_FOR_EACH_DTYPE(DCP_EXTRAS_ABI)
+
 extern "C" {
-
-int dcp_inv_f32(dcp_handle* h, const float* X, int64_t batch, int64_t n, float* out) {
-    return inv_api<float>(h, X, batch, n, out);
-}
-int dcp_inv_f64(dcp_handle* h, const double* X, int64_t batch, int64_t n, double* out) {
-    return inv_api<double>(h, X, batch, n, out);
-}
-int dcp_inv_c64(dcp_handle* h, const void* X, int64_t batch, int64_t n, void* out) {
-    return inv_api<c64>(h, reinterpret_cast<const c64*>(X), batch, n, reinterpret_cast<c64*>(out));
-}
-int dcp_inv_c128(dcp_handle* h, const void* X, int64_t batch, int64_t n, void* out) {
-    return inv_api<c128>(h, reinterpret_cast<const c128*>(X), batch, n, reinterpret_cast<c128*>(out));
-}
-
 
 int dcp_l2_normalize_diff_f32(dcp_handle* h, const float* U, const float* ref, float* out, int64_t K,
                               int64_t F, int strict, double* maxdiff) {
@@ -218,19 +215,6 @@ int dcp_l2_normalize_diff_f32(dcp_handle* h, const float* U, const float* ref, f
 int dcp_l2_normalize_diff_f64(dcp_handle* h, const double* U, const double* ref, double* out, int64_t K,
                               int64_t F, int strict, double* maxdiff) {
     return normalize_diff_api<double>(h, U, ref, out, K, F, strict, maxdiff);
-}
-
-int dcp_gershgorin_f32(dcp_handle* h, const float* X, int64_t batch, int64_t n, float* out) {
-    return gershgorin_api<float>(h, X, batch, n, out);
-}
-int dcp_gershgorin_f64(dcp_handle* h, const double* X, int64_t batch, int64_t n, double* out) {
-    return gershgorin_api<double>(h, X, batch, n, out);
-}
-int dcp_gershgorin_c64(dcp_handle* h, const void* X, int64_t batch, int64_t n, float* out) {
-    return gershgorin_api<c64>(h, reinterpret_cast<const c64*>(X), batch, n, out);
-}
-int dcp_gershgorin_c128(dcp_handle* h, const void* X, int64_t batch, int64_t n, double* out) {
-    return gershgorin_api<c128>(h, reinterpret_cast<const c128*>(X), batch, n, out);
 }
 
 int dcp_mu_quotient_f32(dcp_handle* h, const float* cur, const float* pos, const float* neg,

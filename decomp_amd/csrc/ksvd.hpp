@@ -633,4 +633,15 @@ inline int ksvd_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask
     return DCP_OK;
 }
 
+// dcp_ksvd_clean_step_*: the step with the cleaning pass behind it; masked is whether a mask was given
+template <class T>
+inline int ksvd_clean_step_api(dcp_handle* h, const T* Y, const real_t<T>* M, int mask_ndim, T* X, T* D, int64_t N,
+                               int64_t F, int64_t K, int n_nonzero, double coef_tol, int rows_per_pass,
+                               double* maxdiff_out, int* it_out, double max_coherence, double stop_tol,
+                               int* n_marked_out) {
+    const KsvdCleanCall clean{max_coherence, stop_tol, n_marked_out};
+    return ksvd_step_api<T>(h, Y, M, mask_ndim, M != nullptr || mask_ndim != 0, X, D, N, F, K, n_nonzero, coef_tol,
+                            rows_per_pass, maxdiff_out, it_out, &clean);
+}
+
 }  // namespace dcp

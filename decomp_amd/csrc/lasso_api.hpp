@@ -1,5 +1,6 @@
 // C-ABI glue for the LASSO solvers: argument checks, workspace layout, prox selection.
 #pragma once
+#include "abi.hpp"
 #include "lasso_impl.hpp"
 
 namespace dcp {
@@ -37,4 +38,49 @@ inline int lasso_api(dcp_handle* h, const T* Y, const real_t<T>* mask, int mask_
     }
 }
 
+// parallel coordinate descent with the host-supplied shuffle table (lasso.py:448-523)
+template <class T>
+inline int lasso_pcd_api(dcp_handle* h, const T* Y, const real_t<T>* mask, int mask_ndim, const T* A, T* X, int64_t N,
+                         int64_t F, int64_t K, double alpha, double tol, int maxiter, int positive,
+                         const int32_t* order, int64_t order_rows, int* it_out) {
+    LassoExtra extra;
+    extra.order = order;
+    extra.order_rows = order_rows;
+    return lasso_api<T>(h, Y, mask, mask_ndim, A, X, N, F, K, alpha, tol, maxiter, DCP_LASSO_PARALLEL_CD, positive,
+                        it_out, extra);
+}
+
+// ADMM with an explicit penalty rho (lasso.py:586-657; solve_fastpath passes rho = 1.0)
+template <class T>
+inline int lasso_admm_api(dcp_handle* h, const T* Y, const real_t<T>* mask, int mask_ndim, const T* A, T* X, int64_t N,
+                          int64_t F, int64_t K, double alpha, double tol, int maxiter, int positive, double rho,
+                          int* it_out) {
+    LassoExtra extra;
+    extra.rho = rho;
+    return lasso_api<T>(h, Y, mask, mask_ndim, A, X, N, F, K, alpha, tol, maxiter, DCP_LASSO_ADMM, positive, it_out,
+                        extra);
+}
+
 }  // namespace dcp
+
+// ---- C ABI: dcp_lasso_*, dcp_lasso_pcd_*, dcp_lasso_admm_* (one expansion per dtype: lasso_{f32,f64,c64,c128}.hip;
+// see include/decomp_hip.h; reference decomp/lasso.py:97-189) ----
+#define DCP_LASSO_ABI(SFX, T, P, R)                                                                                  \
+    extern "C" int dcp_lasso_##SFX(dcp_handle* h, const P* Y, const R* mask, int mask_ndim, const P* A, P* X,        \
+                                   int64_t N, int64_t F, int64_t K, double alpha, double tol, int maxiter,           \
+                                   int method, int positive, int* it_out) {                                          \
+        return dcp::lasso_api<T>(h, (const T*)Y, mask, mask_ndim, (const T*)A, (T*)X, N, F, K, alpha, tol, maxiter,  \
+                                 method, positive, it_out);                                                          \
+    }                                                                                                                \
+    extern "C" int dcp_lasso_pcd_##SFX(dcp_handle* h, const P* Y, const R* mask, int mask_ndim, const P* A, P* X,    \
+                                       int64_t N, int64_t F, int64_t K, double alpha, double tol, int maxiter,       \
+                                       int positive, const int32_t* order, int64_t order_rows, int* it_out) {        \
+        return dcp::lasso_pcd_api<T>(h, (const T*)Y, mask, mask_ndim, (const T*)A, (T*)X, N, F, K, alpha, tol,       \
+                                     maxiter, positive, order, order_rows, it_out);                                  \
+    }                                                                                                                \
+    extern "C" int dcp_lasso_admm_##SFX(dcp_handle* h, const P* Y, const R* mask, int mask_ndim, const P* A, P* X,   \
+                                        int64_t N, int64_t F, int64_t K, double alpha, double tol, int maxiter,      \
+                                        int positive, double rho, int* it_out) {                                     \
+        return dcp::lasso_admm_api<T>(h, (const T*)Y, mask, mask_ndim, (const T*)A, (T*)X, N, F, K, alpha, tol,      \
+                                      maxiter, positive, rho, it_out);                                               \
+    }

@@ -2,4 +2,4 @@
 // reference decomp/template_matching.py).
 #include "template_impl.hpp"
 
-DCP_TM_DEFINE(c128, dcp::c128)
+DCP_DTYPE_c128(DCP_TM_ABI)

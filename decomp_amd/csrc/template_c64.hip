@@ -2,4 +2,4 @@
 // reference decomp/template_matching.py).
 #include "template_impl.hpp"
 
-DCP_TM_DEFINE(c64, dcp::c64)
+DCP_DTYPE_c64(DCP_TM_ABI)

@@ -169,4 +169,12 @@ inline int tm_dstep_events(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, 
     });
 }
 
+template <class T>
+inline int tm_dstep_events_api(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmShape& sh,
+                               int acc_it, int64_t max_events, double* maxdiff) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    return tm_dstep_events<T>(h, Y, X, D, XXt, yX, g, acc_it, max_events, maxdiff);
+}
+
 }  // namespace dcp

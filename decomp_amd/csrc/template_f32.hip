@@ -2,4 +2,4 @@
 // reference decomp/template_matching.py).
 #include "template_impl.hpp"
 
-DCP_TM_DEFINE(f32, float)
+DCP_DTYPE_f32(DCP_TM_ABI)

@@ -2,4 +2,4 @@
 // reference decomp/template_matching.py).
 #include "template_impl.hpp"
 
-DCP_TM_DEFINE(f64, double)
+DCP_DTYPE_f64(DCP_TM_ABI)

@@ -24,6 +24,7 @@
 // interior sum M computed once per lag and at most ~S/s edge terms per side: additions only, no prefix
 // differences, fixed summation order everywhere (two runs are bitwise identical).
 #pragma once
+#include "abi.hpp"
 #include "lasso_impl.hpp"
 
 namespace dcp {
@@ -75,6 +76,26 @@ inline bool tm_geom(TmGeom& g, int64_t B, int64_t T, int64_t S, int64_t N, int64
     g.Q = stride * (g.C - 1) - pad;
     g.dh = (S - 1) / stride;
     return true;
+}
+
+// The shape arguments of a dcp_tm_* entry as its signature lists them; the dcp_tm_mc_* entries add Ch and set mc.
+struct TmShape {
+    int64_t B, T, S, N, stride;
+    int padding;
+    int64_t Ch = 1;
+    bool mc = false;
+};
+
+// What every dcp_tm_* entry does first: the handle, the geometry of one channel, the device, then Ch.
+inline int tm_geom_api(dcp_handle* h, const TmShape& sh, TmGeom& g) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!tm_geom(g, sh.B, sh.T, sh.S, sh.N, sh.stride, sh.padding))
+        return fail(h, DCP_ERR_INVALID, "template geometry: need 0 < S <= N, stride > 0, C > 0");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    if (sh.Ch < 1 || sh.Ch > 0x7fffffffLL)
+        return fail(h, DCP_ERR_INVALID, "multichannel templates: need 1 <= Ch < 2^31");
+    g.Ch = sh.Ch;
+    return DCP_OK;
 }
 
 template <class T>
@@ -806,6 +827,86 @@ inline int tm_gather_windows(dcp_handle* h, const T* Y, const T* X, const int64_
     return DCP_OK;
 }
 
+// ---- the entries of this file's kernels (those of the greedy coders and the event step are in their headers) ----
+template <class T>
+inline int tm_temp2mat_api(dcp_handle* h, const T* D, const TmShape& sh, T* out) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    if (!D || !out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    hipLaunchKernelGGL((tm_temp2mat_kernel<T>), dim3(tm_grid(g.T * g.C * g.N)), dim3(256), 0, h->stream, D, g, out);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
+template <class T>
+inline int tm_coef2mat_api(dcp_handle* h, const T* X, const TmShape& sh, T* out) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    if (!X || !out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    hipLaunchKernelGGL((tm_coef2mat_kernel<T>), dim3(tm_grid(g.B * g.T * g.S * g.N)), dim3(256), 0, h->stream, X, g,
+                       out);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
+template <class T>
+inline int tm_predict_api(dcp_handle* h, const T* X, const T* D, const TmShape& sh, T* out) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    if (!X || !D || !out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    return tm_launch_residual<T>(h, (const T*)nullptr, X, (const real_t<T>*)nullptr, D, g, out);
+}
+
+// The prox is a run-time choice in every dtype (a plain `if`): each dtype's library holds all three step kernels.
+template <class T>
+inline int tm_lasso_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmShape& sh, double alpha, double tol,
+                        int maxiter, int method, int positive, int* it_out) {
+    typedef real_t<T> R;
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    if (!Y || !D || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (method != DCP_LASSO_ISTA && method != DCP_LASSO_ACC_ISTA && method != DCP_LASSO_FISTA)
+        return fail(h, DCP_ERR_INVALID, "structured solver: ista, acc_ista or fista");
+    if (positive && scalar_traits<T>::is_complex)
+        return fail(h, DCP_ERR_INVALID, "positive solvers need a real dtype (lasso.py:92)");
+    if (scalar_traits<T>::is_complex)
+        return tm_lasso_solve<T, PROX_COMPLEX>(h, Y, D, X, g, (R)alpha, (R)tol, maxiter, method, it_out);
+    if (positive) return tm_lasso_solve<T, PROX_POSITIVE>(h, Y, D, X, g, (R)alpha, (R)tol, maxiter, method, it_out);
+    return tm_lasso_solve<T, PROX_REAL>(h, Y, D, X, g, (R)alpha, (R)tol, maxiter, method, it_out);
+}
+
+template <class T>
+inline int tm_dstep_api(dcp_handle* h, const T* Y, const T* X, T* D, T* XXt, T* yX, const TmShape& sh, int acc_it,
+                        double* maxdiff) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    if (!Y || !X || !D || !XXt || !yX || !maxdiff) return fail(h, DCP_ERR_INVALID, "null pointer");
+    if (acc_it < 0) return fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");
+    return tm_dstep<T>(h, Y, X, D, XXt, yX, g, acc_it, maxdiff);
+}
+
+template <class T>
+inline int tm_gather_windows_api(dcp_handle* h, const T* Y, const T* X, const int64_t* idx_b, const int64_t* idx_n,
+                                 int64_t m, const TmShape& sh, int64_t w, T* Yw, T* Xw) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    return tm_gather_windows<T>(h, Y, X, idx_b, idx_n, m, g, w, sh.padding, Yw, Xw);
+}
+
+template <class T>
+inline int tm_scatter_windows_api(dcp_handle* h, const T* Xw, T* X, const int64_t* idx_b, const int64_t* idx_n,
+                                  int64_t m, const TmShape& sh, int64_t w) {
+    TmGeom g, gw;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    if (!tm_geom(gw, m, sh.T, sh.S, w, sh.stride, sh.padding) || w > sh.N)
+        return fail(h, DCP_ERR_INVALID, "window geometry");
+    if (!Xw || !X || !idx_b || !idx_n) return fail(h, DCP_ERR_INVALID, "null pointer");
+    hipLaunchKernelGGL((tm_scatter_kernel<T>), dim3(tm_grid(m * g.T * gw.C)), dim3(256), 0, h->stream, Xw, idx_b,
+                       idx_n, (long)m, g.T, g.C, gw.C, X);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
 }  // namespace dcp
 
 #include "template_multichannel.hpp"   // the correlation pass and predict for templates D [T, Ch, S]
@@ -813,164 +914,100 @@ inline int tm_gather_windows(dcp_handle* h, const T* Y, const T* X, const int64_
 #include "template_omp.hpp"       // orthogonal (re-fitting) pursuit on the same operator
 #include "template_events.hpp"    // the dictionary step from event lists, for the codes of those two
 
-// ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip) ------------------------------
-#define DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding)                                    \
-    dcp::TmGeom g;                                                                                  \
-    if (!(h)) return DCP_ERR_INVALID;                                                               \
-    if (!dcp::tm_geom(g, B, T_, S, N, stride, padding))                                             \
-        return dcp::fail(h, DCP_ERR_INVALID, "template geometry: need 0 < S <= N, stride > 0, C > 0"); \
-    DCP_HIP_OK(h, hipSetDevice((h)->device))
-
-// the geometry of one channel, then Ch
-#define DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding)                             \
-    DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                        \
-    if ((Ch) < 1 || (Ch) > 0x7fffffffLL)                                                            \
-        return dcp::fail(h, DCP_ERR_INVALID, "multichannel templates: need 1 <= Ch < 2^31");        \
-    g.Ch = (Ch)
-
-#define DCP_TM_DEFINE(SFX, TYPE)                                                                              \
-    extern "C" int dcp_tm_temp2mat_##SFX(dcp_handle* h, const void* D, int64_t T_, int64_t S, int64_t N,       \
-                                          int64_t stride, int padding, void* out) {                           \
-        DCP_TM_GEOM_OR_FAIL(h, g, 1, T_, S, N, stride, padding);                                              \
-        if (!D || !out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                                  \
-        hipLaunchKernelGGL((dcp::tm_temp2mat_kernel<TYPE>), dim3(dcp::tm_grid(g.T * g.C * g.N)), dim3(256), 0, \
-                           h->stream, (const TYPE*)D, g, (TYPE*)out);                                         \
-        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
-        return DCP_OK;                                                                                         \
-    }                                                                                                          \
-    extern "C" int dcp_tm_coef2mat_##SFX(dcp_handle* h, const void* X, int64_t B, int64_t T_, int64_t S,      \
-                                          int64_t N, int64_t stride, int padding, void* out) {                \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        if (!X || !out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                                  \
-        hipLaunchKernelGGL((dcp::tm_coef2mat_kernel<TYPE>), dim3(dcp::tm_grid(g.B * g.T * g.S * g.N)),         \
-                           dim3(256), 0, h->stream, (const TYPE*)X, g, (TYPE*)out);                           \
-        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
-        return DCP_OK;                                                                                         \
-    }                                                                                                          \
-    extern "C" int dcp_tm_predict_##SFX(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T_,   \
-                                         int64_t S, int64_t N, int64_t stride, int padding, void* out) {      \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        if (!X || !D || !out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                            \
-        return dcp::tm_launch_residual<TYPE>(h, (const TYPE*)nullptr, (const TYPE*)X,                          \
-                                             (const dcp::real_t<TYPE>*)nullptr, (const TYPE*)D, g,             \
-                                             (TYPE*)out);                                                      \
-    }                                                                                                          \
-    extern "C" int dcp_tm_lasso_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,        \
-                                       int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,         \
-                                       double alpha, double tol, int maxiter, int method, int positive,       \
-                                       int* it_out) {                                                          \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        typedef dcp::real_t<TYPE> R;                                                                           \
-        if (!Y || !D || !X || !it_out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                  \
-        if (method != DCP_LASSO_ISTA && method != DCP_LASSO_ACC_ISTA && method != DCP_LASSO_FISTA)             \
-            return dcp::fail(h, DCP_ERR_INVALID, "structured solver: ista, acc_ista or fista");               \
-        if (positive && dcp::scalar_traits<TYPE>::is_complex)                                                  \
-            return dcp::fail(h, DCP_ERR_INVALID, "positive solvers need a real dtype (lasso.py:92)");          \
-        if (dcp::scalar_traits<TYPE>::is_complex)                                                              \
-            return dcp::tm_lasso_solve<TYPE, dcp::PROX_COMPLEX>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X,  \
-                                                                g, (R)alpha, (R)tol, maxiter, method, it_out); \
-        if (positive)                                                                                          \
-            return dcp::tm_lasso_solve<TYPE, dcp::PROX_POSITIVE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, \
-                                                                 g, (R)alpha, (R)tol, maxiter, method,        \
-                                                                 it_out);                                      \
-        return dcp::tm_lasso_solve<TYPE, dcp::PROX_REAL>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g,       \
-                                                         (R)alpha, (R)tol, maxiter, method, it_out);          \
-    }                                                                                                          \
-    extern "C" int dcp_tm_pursuit_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,      \
-                                         int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,       \
-                                         int64_t n_steps, double tol, int positive, int* it_out) {            \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        return dcp::tm_pursuit_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol,         \
-                                         positive, it_out, false);                                             \
-    }                                                                                                          \
-    extern "C" int dcp_tm_mc_pursuit_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,   \
-                                            int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,      \
-                                            int padding, int64_t n_steps, double tol, int positive,            \
-                                            int* it_out) {                                                     \
-        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
-        return dcp::tm_pursuit_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol,         \
-                                         positive, it_out, true);                                              \
-    }                                                                                                          \
-    extern "C" int dcp_tm_pursuit_lds_atoms_##SFX(void) { return (int)dcp::tm_pursuit_lds_atoms<TYPE>(); }    \
-    extern "C" int dcp_tm_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,          \
-                                     int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,           \
-                                     int64_t n_steps, double tol, int* it_out) {                              \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        return dcp::tm_omp_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol, it_out,     \
-                                     false);                                                                   \
-    }                                                                                                          \
-    extern "C" int dcp_tm_mc_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,       \
-                                        int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,          \
-                                        int padding, int64_t n_steps, double tol, int* it_out) {               \
-        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
-        return dcp::tm_omp_api<TYPE>(h, (const TYPE*)Y, (const TYPE*)D, (TYPE*)X, g, n_steps, tol, it_out,     \
-                                     true);                                                                    \
-    }                                                                                                          \
-    extern "C" int dcp_tm_omp_lds_atoms_##SFX(void) { return (int)dcp::tm_omp_lds_atoms<TYPE>(); }            \
-    extern "C" int dcp_tm_mc_predict_##SFX(dcp_handle* h, const void* X, const void* D, int64_t B,            \
-                                            int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,      \
-                                            int padding, void* out) {                                          \
-        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
-        if (!X || !D || !out) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");                            \
-        return dcp::tm_mc_predict<TYPE>(h, (const TYPE*)X, (const TYPE*)D, g, (TYPE*)out);                     \
-    }                                                                                                          \
-    extern "C" int dcp_tm_mc_template_block_##SFX(void) { return dcp::tm_mc_template_block<TYPE>(); }         \
-    extern "C" int dcp_tm_mc_channels_per_pass_##SFX(int64_t S, int64_t stride) {                             \
-        return dcp::tm_mc_channels_per_pass<TYPE>(S, stride);                                                  \
-    }                                                                                                          \
-    extern "C" int dcp_tm_dstep_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt,        \
-                                       void* yX, int64_t B, int64_t T_, int64_t S, int64_t N, int64_t stride, \
-                                       int padding, int acc_it, double* maxdiff) {                             \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        if (!Y || !X || !D || !XXt || !yX || !maxdiff) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");  \
-        if (acc_it < 0) return dcp::fail(h, DCP_ERR_INVALID, "acc_it must be >= 0");                           \
-        return dcp::tm_dstep<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt, (TYPE*)yX, g,      \
-                                   acc_it, maxdiff);                                                           \
-    }                                                                                                          \
-    extern "C" int dcp_tm_dstep_events_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, \
-                                              void* yX, int64_t B, int64_t T_, int64_t S, int64_t N,          \
-                                              int64_t stride, int padding, int acc_it, int64_t max_events,    \
-                                              double* maxdiff) {                                               \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        return dcp::tm_dstep_events<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt, (TYPE*)yX, \
-                                          g, acc_it, max_events, maxdiff);                                     \
-    }                                                                                                          \
-    extern "C" int dcp_tm_mc_dstep_events_##SFX(dcp_handle* h, const void* Y, const void* X, void* D,         \
-                                                 void* XXt, void* yX, int64_t B, int64_t T_, int64_t Ch,       \
-                                                 int64_t S, int64_t N, int64_t stride, int padding,            \
-                                                 int acc_it, int64_t max_events, double* maxdiff) {            \
-        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
-        return dcp::tm_dstep_events<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, (TYPE*)D, (TYPE*)XXt, (TYPE*)yX, \
-                                          g, acc_it, max_events, maxdiff);                                     \
-    }                                                                                                          \
-    extern "C" int dcp_tm_gather_windows_##SFX(dcp_handle* h, const void* Y, const void* X,                   \
-                                                const int64_t* idx_b, const int64_t* idx_n, int64_t m,        \
-                                                int64_t B, int64_t T_, int64_t S, int64_t N, int64_t w,       \
-                                                int64_t stride, int padding, void* Yw, void* Xw) {            \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        return dcp::tm_gather_windows<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, m, g, w, padding, \
-                                            (TYPE*)Yw, (TYPE*)Xw);                                             \
-    }                                                                                                          \
-    extern "C" int dcp_tm_mc_gather_windows_##SFX(dcp_handle* h, const void* Y, const void* X,                \
-                                                   const int64_t* idx_b, const int64_t* idx_n, int64_t m,     \
-                                                   int64_t B, int64_t T_, int64_t Ch, int64_t S, int64_t N,   \
-                                                   int64_t w, int64_t stride, int padding, void* Yw,          \
-                                                   void* Xw) {                                                 \
-        DCP_TM_MC_GEOM_OR_FAIL(h, g, B, T_, Ch, S, N, stride, padding);                                       \
-        return dcp::tm_gather_windows<TYPE>(h, (const TYPE*)Y, (const TYPE*)X, idx_b, idx_n, m, g, w, padding, \
-                                            (TYPE*)Yw, (TYPE*)Xw);                                             \
-    }                                                                                                          \
-    extern "C" int dcp_tm_scatter_windows_##SFX(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b, \
-                                                 const int64_t* idx_n, int64_t m, int64_t B, int64_t T_,      \
-                                                 int64_t S, int64_t N, int64_t w, int64_t stride,             \
-                                                 int padding) {                                                \
-        DCP_TM_GEOM_OR_FAIL(h, g, B, T_, S, N, stride, padding);                                              \
-        dcp::TmGeom gw;                                                                                        \
-        if (!dcp::tm_geom(gw, m, T_, S, w, stride, padding) || w > N)                                          \
-            return dcp::fail(h, DCP_ERR_INVALID, "window geometry");                                           \
-        if (!Xw || !X || !idx_b || !idx_n) return dcp::fail(h, DCP_ERR_INVALID, "null pointer");              \
-        hipLaunchKernelGGL((dcp::tm_scatter_kernel<TYPE>), dim3(dcp::tm_grid(m * g.T * gw.C)), dim3(256), 0,   \
-                           h->stream, (const TYPE*)Xw, idx_b, idx_n, (long)m, g.T, g.C, gw.C, (TYPE*)X);       \
-        DCP_LAUNCH_OK(h, hipGetLastError());                                                                   \
-        return DCP_OK;                                                                                         \
+// ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip).  Every dtype's signature shows void*; the
+// shape arguments travel as a TmShape {B, T, S, N, stride, padding[, Ch, mc]}. ----
+#define DCP_TM_ABI(SFX, T, P, R)                                                                                     \
+    extern "C" int dcp_tm_temp2mat_##SFX(dcp_handle* h, const void* D, int64_t T_, int64_t S, int64_t N,             \
+                                         int64_t stride, int padding, void* out) {                                   \
+        return dcp::tm_temp2mat_api<T>(h, (const T*)D, {1, T_, S, N, stride, padding}, (T*)out);                     \
+    }                                                                                                                \
+    extern "C" int dcp_tm_coef2mat_##SFX(dcp_handle* h, const void* X, int64_t B, int64_t T_, int64_t S, int64_t N,  \
+                                         int64_t stride, int padding, void* out) {                                   \
+        return dcp::tm_coef2mat_api<T>(h, (const T*)X, {B, T_, S, N, stride, padding}, (T*)out);                     \
+    }                                                                                                                \
+    extern "C" int dcp_tm_predict_##SFX(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T_,          \
+                                        int64_t S, int64_t N, int64_t stride, int padding, void* out) {              \
+        return dcp::tm_predict_api<T>(h, (const T*)X, (const T*)D, {B, T_, S, N, stride, padding}, (T*)out);         \
+    }                                                                                                                \
+    extern "C" int dcp_tm_lasso_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T_,   \
+                                      int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol,   \
+                                      int maxiter, int method, int positive, int* it_out) {                          \
+        return dcp::tm_lasso_api<T>(h, (const T*)Y, (const T*)D, (T*)X, {B, T_, S, N, stride, padding}, alpha, tol,  \
+                                    maxiter, method, positive, it_out);                                              \
+    }                                                                                                                \
+    extern "C" int dcp_tm_pursuit_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,             \
+                                        int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,               \
+                                        int64_t n_steps, double tol, int positive, int* it_out) {                    \
+        return dcp::tm_pursuit_api<T>(h, (const T*)Y, (const T*)D, (T*)X, {B, T_, S, N, stride, padding}, n_steps,   \
+                                      tol, positive, it_out);                                                        \
+    }                                                                                                                \
+    extern "C" int dcp_tm_mc_pursuit_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,          \
+                                           int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride,             \
+                                           int padding, int64_t n_steps, double tol, int positive, int* it_out) {    \
+        return dcp::tm_pursuit_api<T>(h, (const T*)Y, (const T*)D, (T*)X, {B, T_, S, N, stride, padding, Ch, true},  \
+                                      n_steps, tol, positive, it_out);                                               \
+    }                                                                                                                \
+    extern "C" int dcp_tm_pursuit_lds_atoms_##SFX(void) { return (int)dcp::tm_pursuit_lds_atoms<T>(); }              \
+    extern "C" int dcp_tm_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T_,     \
+                                    int64_t S, int64_t N, int64_t stride, int padding, int64_t n_steps, double tol,  \
+                                    int* it_out) {                                                                   \
+        return dcp::tm_omp_api<T>(h, (const T*)Y, (const T*)D, (T*)X, {B, T_, S, N, stride, padding}, n_steps, tol,  \
+                                  it_out);                                                                           \
+    }                                                                                                                \
+    extern "C" int dcp_tm_mc_omp_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T_,  \
+                                       int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding,                \
+                                       int64_t n_steps, double tol, int* it_out) {                                   \
+        return dcp::tm_omp_api<T>(h, (const T*)Y, (const T*)D, (T*)X, {B, T_, S, N, stride, padding, Ch, true},      \
+                                  n_steps, tol, it_out);                                                             \
+    }                                                                                                                \
+    extern "C" int dcp_tm_omp_lds_atoms_##SFX(void) { return (int)dcp::tm_omp_lds_atoms<T>(); }                      \
+    extern "C" int dcp_tm_mc_predict_##SFX(dcp_handle* h, const void* X, const void* D, int64_t B, int64_t T_,       \
+                                           int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding,            \
+                                           void* out) {                                                              \
+        return dcp::tm_mc_predict_api<T>(h, (const T*)X, (const T*)D, {B, T_, S, N, stride, padding, Ch, true},      \
+                                         (T*)out);                                                                   \
+    }                                                                                                                \
+    extern "C" int dcp_tm_mc_template_block_##SFX(void) { return dcp::tm_mc_template_block<T>(); }                   \
+    extern "C" int dcp_tm_mc_channels_per_pass_##SFX(int64_t S, int64_t stride) {                                    \
+        return dcp::tm_mc_channels_per_pass<T>(S, stride);                                                           \
+    }                                                                                                                \
+    extern "C" int dcp_tm_dstep_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt, void* yX,     \
+                                      int64_t B, int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,      \
+                                      int acc_it, double* maxdiff) {                                                 \
+        return dcp::tm_dstep_api<T>(h, (const T*)Y, (const T*)X, (T*)D, (T*)XXt, (T*)yX,                             \
+                                    {B, T_, S, N, stride, padding}, acc_it, maxdiff);                                \
+    }                                                                                                                \
+    extern "C" int dcp_tm_dstep_events_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt,        \
+                                             void* yX, int64_t B, int64_t T_, int64_t S, int64_t N, int64_t stride,  \
+                                             int padding, int acc_it, int64_t max_events, double* maxdiff) {         \
+        return dcp::tm_dstep_events_api<T>(h, (const T*)Y, (const T*)X, (T*)D, (T*)XXt, (T*)yX,                      \
+                                           {B, T_, S, N, stride, padding}, acc_it, max_events, maxdiff);             \
+    }                                                                                                                \
+    extern "C" int dcp_tm_mc_dstep_events_##SFX(dcp_handle* h, const void* Y, const void* X, void* D, void* XXt,     \
+                                                void* yX, int64_t B, int64_t T_, int64_t Ch, int64_t S, int64_t N,   \
+                                                int64_t stride, int padding, int acc_it, int64_t max_events,         \
+                                                double* maxdiff) {                                                   \
+        return dcp::tm_dstep_events_api<T>(h, (const T*)Y, (const T*)X, (T*)D, (T*)XXt, (T*)yX,                      \
+                                           {B, T_, S, N, stride, padding, Ch, true}, acc_it, max_events, maxdiff);   \
+    }                                                                                                                \
+    extern "C" int dcp_tm_gather_windows_##SFX(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b,    \
+                                               const int64_t* idx_n, int64_t m, int64_t B, int64_t T_, int64_t S,    \
+                                               int64_t N, int64_t w, int64_t stride, int padding, void* Yw,          \
+                                               void* Xw) {                                                           \
+        return dcp::tm_gather_windows_api<T>(h, (const T*)Y, (const T*)X, idx_b, idx_n, m,                           \
+                                             {B, T_, S, N, stride, padding}, w, (T*)Yw, (T*)Xw);                     \
+    }                                                                                                                \
+    extern "C" int dcp_tm_mc_gather_windows_##SFX(dcp_handle* h, const void* Y, const void* X,                       \
+                                                  const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B,  \
+                                                  int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t w,           \
+                                                  int64_t stride, int padding, void* Yw, void* Xw) {                 \
+        return dcp::tm_gather_windows_api<T>(h, (const T*)Y, (const T*)X, idx_b, idx_n, m,                           \
+                                             {B, T_, S, N, stride, padding, Ch, true}, w, (T*)Yw, (T*)Xw);           \
+    }                                                                                                                \
+    extern "C" int dcp_tm_scatter_windows_##SFX(dcp_handle* h, const void* Xw, void* X, const int64_t* idx_b,        \
+                                                const int64_t* idx_n, int64_t m, int64_t B, int64_t T_, int64_t S,   \
+                                                int64_t N, int64_t w, int64_t stride, int padding) {                 \
+        return dcp::tm_scatter_windows_api<T>(h, (const T*)Xw, (T*)X, idx_b, idx_n, m,                               \
+                                              {B, T_, S, N, stride, padding}, w);                                    \
     }
+

@@ -205,4 +205,12 @@ inline int tm_mc_predict(dcp_handle* h, const T* X, const T* D, const TmGeom& g,
     return DCP_OK;
 }
 
+template <class T>
+inline int tm_mc_predict_api(dcp_handle* h, const T* X, const T* D, const TmShape& sh, T* out) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
+    if (!X || !D || !out) return fail(h, DCP_ERR_INVALID, "null pointer");
+    return tm_mc_predict<T>(h, X, D, g, out);
+}
+
 }  // namespace dcp

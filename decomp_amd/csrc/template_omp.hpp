@@ -304,15 +304,18 @@ inline int tm_omp_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeo
     return read_scalar(h, (const int*)it_dev, it_out);
 }
 
+// dcp_tm_omp_* and dcp_tm_mc_omp_*
 template <class T>
-inline int tm_omp_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
-                      int* it_out, bool mc) {
+inline int tm_omp_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmShape& sh, int64_t n_steps, double tol,
+                      int* it_out) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
     if (!Y || !D || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
     const int64_t K = (int64_t)g.T * g.C;
     if (K > 0x7fffff00LL) return fail(h, DCP_ERR_INVALID, "orthogonal pursuit: T C exceeds 2^31 - 257");
     DCP_TRY(omp_check_sparsity(h, K, n_steps, omp_cap<T>(), "orthogonal pursuit: n_steps", "T C"));
     if (tol != tol) return fail(h, DCP_ERR_INVALID, "orthogonal pursuit: tol is NaN");
-    return tm_omp_solve<T>(h, Y, D, X, g, (int)n_steps, tol, it_out, mc);
+    return tm_omp_solve<T>(h, Y, D, X, g, (int)n_steps, tol, it_out, sh.mc);
 }
 
 }  // namespace dcp

@@ -372,9 +372,12 @@ inline int tm_pursuit_solve(dcp_handle* h, const T* Y, const T* D, T* X, const T
     return read_scalar(h, (const int*)it_dev, it_out);
 }
 
+// dcp_tm_pursuit_* and dcp_tm_mc_pursuit_*
 template <class T>
-inline int tm_pursuit_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmGeom& g, int64_t n_steps, double tol,
-                          int positive, int* it_out, bool mc) {
+inline int tm_pursuit_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmShape& sh, int64_t n_steps, double tol,
+                          int positive, int* it_out) {
+    TmGeom g;
+    DCP_TRY(tm_geom_api(h, sh, g));
     if (!Y || !D || !X || !it_out) return fail(h, DCP_ERR_INVALID, "null pointer");
     const int64_t K = (int64_t)g.T * g.C;
     if (K > 0x7fffff00LL) return fail(h, DCP_ERR_INVALID, "pursuit: T C exceeds 2^31 - 257");
@@ -382,7 +385,7 @@ inline int tm_pursuit_api(dcp_handle* h, const T* Y, const T* D, T* X, const TmG
     if (tol != tol) return fail(h, DCP_ERR_INVALID, "pursuit: tol is NaN");
     if (positive && scalar_traits<T>::is_complex)
         return fail(h, DCP_ERR_INVALID, "pursuit: positive needs a real dtype");
-    return tm_pursuit_solve<T>(h, Y, D, X, g, n_steps, tol, positive, it_out, mc);
+    return tm_pursuit_solve<T>(h, Y, D, X, g, n_steps, tol, positive, it_out, sh.mc);
 }
 
 }  // namespace dcp

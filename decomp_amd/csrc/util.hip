@@ -1,4 +1,5 @@
 // C ABI: handle lifetime, row normalisation, sign scan, and the GEMM test hook.
+#include "abi.hpp"
 #include "comm.hpp"
 #include "gemm.hpp"
 #include "handle.hpp"
@@ -554,27 +555,11 @@ const char* dcp_build_info(void) {
     return "libdecomp_hip: gfx950, fp32 MFMA 32x32x2 + fp64 MFMA 16x16x4 GEMM cores, HIP " DCP_STR(HIP_VERSION_MAJOR) "." DCP_STR(HIP_VERSION_MINOR);
 }
 
-int dcp_l2_normalize_f32(dcp_handle* h, float* U, int64_t K, int64_t F, int strict) {
-    return l2_normalize_api<float>(h, U, K, F, strict);
-}
-int dcp_l2_normalize_f64(dcp_handle* h, double* U, int64_t K, int64_t F, int strict) {
-    return l2_normalize_api<double>(h, U, K, F, strict);
-}
-int dcp_l2_normalize_c64(dcp_handle* h, void* U, int64_t K, int64_t F, int strict) {
-    return l2_normalize_api<c64>(h, reinterpret_cast<c64*>(U), K, F, strict);
-}
-int dcp_l2_normalize_c128(dcp_handle* h, void* U, int64_t K, int64_t F, int strict) {
-    return l2_normalize_api<c128>(h, reinterpret_cast<c128*>(U), K, F, strict);
-}
 int dcp_count_negative_f32(dcp_handle* h, const float* x, int64_t n, int64_t* count) {
     return count_negative_api<float>(h, x, n, count);
 }
 int dcp_count_negative_f64(dcp_handle* h, const double* x, int64_t n, int64_t* count) {
     return count_negative_api<double>(h, x, n, count);
-}
-int dcp_gemm_f32(dcp_handle* h, int form, const float* A, const float* B, float* C, int64_t M,
-                 int64_t N, int64_t K, int ksplits, int tile) {
-    return gemm_api<float>(h, form, A, B, C, M, N, K, ksplits, tile);
 }
 int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B, float* C, int64_t M, int64_t N,
                         int64_t K, int ksplits) {
@@ -620,20 +605,6 @@ int dcp_set_f32_product_mode(dcp_handle* h, int mode) {
     if (mode >= 0) h->f32_product_mode = mode;
     return prev;
 }
-int dcp_gemm_f64(dcp_handle* h, int form, const double* A, const double* B, double* C, int64_t M,
-                 int64_t N, int64_t K, int ksplits, int tile) {
-    return gemm_api<double>(h, form, A, B, C, M, N, K, ksplits, tile);
-}
-int dcp_gemm_c64(dcp_handle* h, int form, const void* A, const void* B, void* C, int64_t M, int64_t N,
-                 int64_t K, int ksplits, int tile) {
-    return gemm_api<c64>(h, form, reinterpret_cast<const c64*>(A), reinterpret_cast<const c64*>(B),
-                         reinterpret_cast<c64*>(C), M, N, K, ksplits, tile);
-}
-int dcp_gemm_c128(dcp_handle* h, int form, const void* A, const void* B, void* C, int64_t M, int64_t N,
-                  int64_t K, int ksplits, int tile) {
-    return gemm_api<c128>(h, form, reinterpret_cast<const c128*>(A), reinterpret_cast<const c128*>(B),
-                          reinterpret_cast<c128*>(C), M, N, K, ksplits, tile);
-}
 
 int dcp_dict_prefetch_rows_bytes(dcp_handle* h, const void* in, const int64_t* index, int64_t rows,
                                  int64_t row_bytes, void* out) {
@@ -670,3 +641,15 @@ int dcp_dict_set_pcd_order(dcp_handle* h, const int32_t* order, int64_t rows, in
 }
 
 }  // extern "C"
+
+// the entries that exist in all four dtypes (complex: form 0 = A B^H, 1 = A B, 2 = A^H B)
+#define DCP_UTIL_ABI(SFX, T, P, R)                                                                                   \
+    extern "C" int dcp_l2_normalize_##SFX(dcp_handle* h, P* U, int64_t K, int64_t F, int strict) {                   \
+        return l2_normalize_api<T>(h, (T*)U, K, F, strict);                                                          \
+    }                                                                                                                \
+    extern "C" int dcp_gemm_##SFX(dcp_handle* h, int form, const P* A, const P* B, P* C, int64_t M, int64_t N,       \
+                                  int64_t K, int ksplits, int tile) {                                                \
+        return gemm_api<T>(h, form, (const T*)A, (const T*)B, (T*)C, M, N, K, ksplits, tile);                        \
+    }
+
+DCP_FOR_EACH_DTYPE(DCP_UTIL_ABI)
