@@ -136,6 +136,7 @@ _FAMILIES = [
     ('dcp_tm_predict', _ALL, [_c_vp] * 3 + _TM + [_c_vp]),
     ('dcp_tm_mc_predict', _ALL, [_c_vp] * 3 + _TM_MC + [_c_vp]),
     ('dcp_tm_lasso', _ALL, [_c_vp] * 4 + _TM + [_c_f64, _c_f64, _c_int, _c_int, _c_int, _P_INT]),
+    ('dcp_tm_mc_lasso', _ALL, [_c_vp] * 4 + _TM_MC + [_c_f64, _c_f64, _c_int, _c_int, _c_int, _P_INT]),
     ('dcp_tm_pursuit', _ALL, [_c_vp] * 4 + _TM + [_c_i64, _c_f64, _c_int, _P_INT]),
     ('dcp_tm_mc_pursuit', _ALL, [_c_vp] * 4 + _TM_MC + [_c_i64, _c_f64, _c_int, _P_INT]),
     ('dcp_tm_omp', _ALL, [_c_vp] * 4 + _TM + [_c_i64, _c_f64, _P_INT]),

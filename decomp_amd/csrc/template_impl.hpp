@@ -35,8 +35,8 @@ DCP_HD long tm_ceil_div(long a, long b) { return -tm_floor_div(-a, b); }
 struct TmGeom {
     long B = 1, T = 0, S = 0, N = 0, C = 0, s = 1, Q = 0;
     long dh = 0;   // largest |lag| in units of c: floor((S - 1) / s)
-    long Ch = 1;   // channels of a template (D [T, Ch, S], y [B, Ch, N]): honoured by the greedy coders' kernels and by
-                   // the dictionary step on event lists (template_events.hpp) alone
+    long Ch = 1;   // channels of a template (D [T, Ch, S], y [B, Ch, N]): honoured by the greedy coders' kernels, the
+                   // dictionary step on event lists (template_events.hpp) and the Gram-form LASSO (template_mc_lasso.hpp)
     DCP_HD long nd() const { return 2 * dh + 1; }
     // c of the coefficients whose taps cover sample n: [c_first(n), c_last(n)] (clipped to [0, C))
     DCP_HD long c_first(long n) const { long c = tm_ceil_div(n + Q - S + 1, s); return c < 0 ? 0 : c; }
@@ -233,23 +233,33 @@ __device__ __forceinline__ T tm_corr_tile(const T* __restrict__ r, const T* __re
     return acc;
 }
 
+// The proximal step on coefficient (b, t, c < C) from its unscaled gradient grad = (r A^H)[b, t, c]:
+//   z = V + grad rinv / L,  x_new = prox(z, alpha_k / L),  the stop test against P,  the momentum point.
+// The one place that reads and writes the fields of TmStep (this kernel and the Gram-form step of
+// template_mc_lasso.hpp end in it).
 template <class T, int PROX>
-__global__ void __launch_bounds__(256) tm_corr_step_kernel(const T* __restrict__ r, const T* __restrict__ D,
-                                                           TmGeom g, int lds_ok, TmStep<T, PROX> ep) {
+__device__ __forceinline__ void tm_step_epilogue(const TmStep<T, PROX>& ep, const TmGeom& g, T grad, long t, long b,
+                                                 long c) {
     typedef real_t<T> R;
-    const long t = blockIdx.y, b = blockIdx.z;
-    const long c = (long)blockIdx.x * 256 + threadIdx.x;
-    const T acc = tm_corr_tile(r, D, g, lds_ok, t, b, c);
-    if (c >= g.C) return;
     const long tc = t * g.C + c;
     const long i = (b * g.T + t) * g.C + c;
     const R Linv = ep.scal[0];
-    const T z = add(ep.V[i], scale(scale(acc, ep.rinv[tc]), Linv));
+    const T z = add(ep.V[i], scale(scale(grad, ep.rinv[tc]), Linv));
     const T xn = prox_apply<PROX>(z, Linv * ep.alphak[tc]);
     const T d = sub(xn, ep.P[i]);
     if (ep.check && !((absval(d) - ep.tolk[tc]) < R(0))) *ep.flag = 1;
     ep.Nw[i] = xn;
     if (ep.Vn != nullptr) ep.Vn[i] = add(xn, scale(d, ep.coef));
+}
+
+template <class T, int PROX>
+__global__ void __launch_bounds__(256) tm_corr_step_kernel(const T* __restrict__ r, const T* __restrict__ D,
+                                                           TmGeom g, int lds_ok, TmStep<T, PROX> ep) {
+    const long t = blockIdx.y, b = blockIdx.z;
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    const T acc = tm_corr_tile(r, D, g, lds_ok, t, b, c);
+    if (c >= g.C) return;
+    tm_step_epilogue(ep, g, acc, t, b, c);
 }
 
 // ---- prepare ------------------------------------------------------------------------------------
@@ -363,7 +373,9 @@ __global__ void __launch_bounds__(256) tm_gram_colsum_kernel(const T* __restrict
             if (k0 < -bi) k0 = -bi;
             if (k1 > g.N - 1 - bi) k1 = g.N - 1 - bi;
             v = zero_of<T>();
-            for (long k = k0; k <= k1; ++k) v = madd(v, D[t * g.S + k], conj_of(D[tp * g.S + k + m]));
+            for (long ch = 0; ch < g.Ch; ++ch)   // (D [T, Ch, S]: ch ascending, k ascending inside)
+                for (long k = k0; k <= k1; ++k)
+                    v = madd(v, D[(t * g.Ch + ch) * g.S + k], conj_of(D[(tp * g.Ch + ch) * g.S + k + m]));
         }
         acc += absval(v) * rinv[t * g.C + c] * rinv[j];
     }
@@ -623,6 +635,34 @@ inline int tm_launch_step(dcp_handle* h, const T* r, const T* D, const TmGeom& g
     return DCP_OK;
 }
 
+// scal[0] = 1 / Gershgorin(A'A'^H) from the lag correlations and 1 / rho (over the g.Ch channels of D): the Toeplitz
+// columns once per template, the boundary columns one by one.  tsum [T] and colsum [T C] are workspace.
+template <class T>
+inline int tm_gram_bound(dcp_handle* h, const T* D, const T* corr, const real_t<T>* rinv, const TmGeom& g,
+                         real_t<T>* tsum, real_t<T>* colsum, real_t<T>* scal) {
+    typedef real_t<T> R;
+    hipStream_t st = h->stream;
+    long lo, hi;
+    tm_toeplitz_cols(g, &lo, &hi);
+    if (lo <= hi) {
+        hipLaunchKernelGGL((tm_gram_colsum_kernel<T>), dim3(g.T), dim3(256), 0, st, D, corr, rinv, g, lo, hi, 0, tsum,
+                           colsum);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+        hipLaunchKernelGGL((tm_gram_fill_kernel<R>), dim3(tm_grid(g.T * (hi - lo + 1))), dim3(256), 0, st, g, lo, hi,
+                           (const R*)tsum, colsum);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+    }
+    const long nb = lo <= hi ? g.C - (hi - lo + 1) : g.C;
+    if (nb > 0) {
+        hipLaunchKernelGGL((tm_gram_colsum_kernel<T>), dim3(g.T * nb), dim3(256), 0, st, D, corr, rinv, g, lo, hi, 1,
+                           tsum, colsum);
+        DCP_LAUNCH_OK(h, hipGetLastError());
+    }
+    launch_tm_max<R>(st, (const R*)colsum, g.T * g.C, R(0), scal);
+    DCP_LAUNCH_OK(h, hipGetLastError());
+    return DCP_OK;
+}
+
 // Structured solve_fastpath for ista / acc_ista / fista (+ _pos).  Y [B, N], D [T, S], X [B, T, C]
 // (in: initial estimate, out: solution).  The outer loop and its lagged stop test are prox_gradient_loop
 // (prox_loop.hpp), shared with the dense solver.
@@ -665,26 +705,7 @@ inline int tm_lasso_solve(dcp_handle* h, const T* Y, const T* D, T* X, const TmG
     DCP_LAUNCH_OK(h, hipGetLastError());
     hipLaunchKernelGGL((tm_lagcorr_kernel<T>), dim3(g.T * g.T), dim3(256), 0, st, D, g, corr);
     DCP_LAUNCH_OK(h, hipGetLastError());
-    {   // Gershgorin of A'A'^H: the Toeplitz columns once per template, the boundary columns one by one
-        long lo, hi;
-        tm_toeplitz_cols(g, &lo, &hi);
-        if (lo <= hi) {
-            hipLaunchKernelGGL((tm_gram_colsum_kernel<T>), dim3(g.T), dim3(256), 0, st, D, (const T*)corr,
-                               (const R*)rinv, g, lo, hi, 0, tsum, colsum);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-            hipLaunchKernelGGL((tm_gram_fill_kernel<R>), dim3(tm_grid(g.T * (hi - lo + 1))), dim3(256), 0, st, g, lo,
-                               hi, (const R*)tsum, colsum);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-        }
-        const long nb = lo <= hi ? g.C - (hi - lo + 1) : g.C;
-        if (nb > 0) {
-            hipLaunchKernelGGL((tm_gram_colsum_kernel<T>), dim3(g.T * nb), dim3(256), 0, st, D, (const T*)corr,
-                               (const R*)rinv, g, lo, hi, 1, tsum, colsum);
-            DCP_LAUNCH_OK(h, hipGetLastError());
-        }
-    }
-    launch_tm_max<R>(st, colsum, TC, R(0), scal);
-    DCP_LAUNCH_OK(h, hipGetLastError());
+    DCP_TRY(tm_gram_bound<T>(h, D, corr, rinv, g, tsum, colsum, scal));
 
     // ---- one iteration: the residual of V, then correlation + prox step into Nw (and Vn) ----
     auto step = [&](int, T* V, T* P, T* Nw, T* Vn, R coef, int check, bool) -> int {
@@ -913,6 +934,7 @@ inline int tm_scatter_windows_api(dcp_handle* h, const T* Xw, T* X, const int64_
 #include "template_pursuit.hpp"   // matching pursuit on the same operator
 #include "template_omp.hpp"       // orthogonal (re-fitting) pursuit on the same operator
 #include "template_events.hpp"    // the dictionary step from event lists, for the codes of those two
+#include "template_mc_lasso.hpp"  // the proximal-gradient LASSO in Gram form for templates D [T, Ch, S]
 
 // ---- C ABI (one expansion per dtype: template_{f32,f64,c64,c128}.hip).  Every dtype's signature shows void*; the
 // shape arguments travel as a TmShape {B, T, S, N, stride, padding[, Ch, mc]}. ----
@@ -934,6 +956,13 @@ inline int tm_scatter_windows_api(dcp_handle* h, const T* Xw, T* X, const int64_
                                       int maxiter, int method, int positive, int* it_out) {                          \
         return dcp::tm_lasso_api<T>(h, (const T*)Y, (const T*)D, (T*)X, {B, T_, S, N, stride, padding}, alpha, tol,  \
                                     maxiter, method, positive, it_out);                                              \
+    }                                                                                                                \
+    extern "C" int dcp_tm_mc_lasso_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,            \
+                                         int64_t T_, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding,  \
+                                         double alpha, double tol, int maxiter, int method, int positive,            \
+                                         int* it_out) {                                                              \
+        return dcp::tm_mc_lasso_api<T>(h, (const T*)Y, (const T*)D, (T*)X, {B, T_, S, N, stride, padding, Ch, true}, \
+                                       alpha, tol, maxiter, method, positive, it_out);                               \
     }                                                                                                                \
     extern "C" int dcp_tm_pursuit_##SFX(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B,             \
                                         int64_t T_, int64_t S, int64_t N, int64_t stride, int padding,               \

@@ -59,24 +59,23 @@ DCP_HD c128 tm_mc_madd(c128 acc, c128 y, c128 d) {
     return c128{fma(y.im, d.im, fma(y.re, d.re, acc.re)), fma(-y.re, d.im, fma(y.im, d.re, acc.im))};
 }
 
-// grid (ceil(C / 256), ceil(T / TB), B <= 65535); dynamic LDS CP (255 s + S) sizeof(T) when LDS.  y [B, Ch, N],
-// D [T, Ch, S] -> alpha0 [B, T, C]
-template <class T, int TB, bool LDS>
-__global__ void __launch_bounds__(256) tm_mc_corr_kernel(const T* __restrict__ y, const T* __restrict__ D, TmGeom g,
-                                                         int CP, T* __restrict__ alpha0) {
+// The accumulation loop of the correlation kernels, for the workgroup of tm_mc_corr_kernel's grid: acc[j] = the sum of
+// coefficient (t0 + j, c0 + tid) over the g.Ch channels and g.S taps, the samples taken from ld(ch, n), 0 <= n < g.N
+// (y [Ch, N] of a signal there; the Gram-form LASSO step of template_mc_lasso.hpp runs the same loop on the scaled
+// iterate).  The whole workgroup calls it (the staging has barriers).
+template <class T, int TB, bool LDS, class Load>
+__device__ __forceinline__ void tm_mc_corr_accumulate(const Load& ld, const T* __restrict__ D, const TmGeom& g, int CP,
+                                                      long t0, T (&acc)[TB]) {
     extern __shared__ __attribute__((aligned(16))) char tm_smem[];
     T* sY = reinterpret_cast<T*>(tm_smem);
     const int tid = threadIdx.x;
-    const long b = blockIdx.z, t0 = (long)blockIdx.y * TB;
-    const long c0 = (long)blockIdx.x * 256, c = c0 + tid;
+    const long c0 = (long)blockIdx.x * 256;
     const long span = 255 * g.s + g.S;
     const long nlo = g.s * c0 - g.Q;   // the sample of sY[0]; this thread's taps start at sY[off]
     const long off = g.s * tid;
-    const T* yb = y + b * g.Ch * g.N;
     const T* Dt[TB];                   // workgroup-uniform: the taps are scalar operands
 #pragma unroll
     for (int j = 0; j < TB; ++j) Dt[j] = D + (t0 + j < g.T ? t0 + j : g.T - 1) * g.Ch * g.S;
-    T acc[TB];
 #pragma unroll
     for (int j = 0; j < TB; ++j) acc[j] = zero_of<T>();
     const long step = LDS ? CP : g.Ch;
@@ -85,17 +84,15 @@ __global__ void __launch_bounds__(256) tm_mc_corr_kernel(const T* __restrict__ y
         if constexpr (LDS) {
             __syncthreads();
             for (long q = 0; q < np; ++q) {
-                const T* yrow = yb + (p0 + q) * g.N;
                 for (long m = tid; m < span; m += 256) {
                     const long n = nlo + m;
-                    sY[q * span + m] = (n >= 0 && n < g.N) ? yrow[n] : zero_of<T>();
+                    sY[q * span + m] = (n >= 0 && n < g.N) ? ld(p0 + q, n) : zero_of<T>();
                 }
             }
             __syncthreads();
         }
         for (long q = 0; q < np; ++q) {
             const long dch = (p0 + q) * g.S;
-            const T* yrow = yb + (p0 + q) * g.N;
             const T* w = sY + q * span + off;
 #pragma unroll 8
             for (long k = 0; k < g.S; ++k) {
@@ -104,13 +101,32 @@ __global__ void __launch_bounds__(256) tm_mc_corr_kernel(const T* __restrict__ y
                     v = w[k];
                 } else {
                     const long n = nlo + off + k;
-                    v = (n >= 0 && n < g.N) ? yrow[n] : zero_of<T>();
+                    v = (n >= 0 && n < g.N) ? ld(p0 + q, n) : zero_of<T>();
                 }
 #pragma unroll
                 for (int j = 0; j < TB; ++j) acc[j] = tm_mc_madd(acc[j], v, Dt[j][dch + k]);
             }
         }
     }
+}
+
+// sample n of channel ch of one signal y [Ch, N]
+template <class T>
+struct TmMcSignal {
+    const T* yb;
+    long N;
+    __device__ __forceinline__ T operator()(long ch, long n) const { return yb[ch * N + n]; }
+};
+
+// grid (ceil(C / 256), ceil(T / TB), B <= 65535); dynamic LDS CP (255 s + S) sizeof(T) when LDS.  y [B, Ch, N],
+// D [T, Ch, S] -> alpha0 [B, T, C]
+template <class T, int TB, bool LDS>
+__global__ void __launch_bounds__(256) tm_mc_corr_kernel(const T* __restrict__ y, const T* __restrict__ D, TmGeom g,
+                                                         int CP, T* __restrict__ alpha0) {
+    const long b = blockIdx.z, t0 = (long)blockIdx.y * TB;
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    T acc[TB];
+    tm_mc_corr_accumulate<T, TB, LDS>(TmMcSignal<T>{y + b * g.Ch * g.N, g.N}, D, g, CP, t0, acc);
     if (c >= g.C) return;
 #pragma unroll
     for (int j = 0; j < TB; ++j)

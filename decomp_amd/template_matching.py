@@ -27,7 +27,11 @@ size is formed on the hot path (include/decomp_hip.h ``dcp_tm_*``, decomp_amd/cs
   * ``solve`` with one of those greedy coders learns multichannel templates D [T, Ch, S] too: x is shared by the
     channels, so XXt stays the one-channel [T S, T S], only yX [T, Ch, S] gains the channel axis, the gradient step is
     XXt times the [T S, Ch] columns of D and a template is normalised over its Ch S entries
-    (``dcp_tm_mc_dstep_events_*``, the same step of decomp_amd/csrc/template_events.hpp with Ch channels).
+    (``dcp_tm_mc_dstep_events_*``, the same step of decomp_amd/csrc/template_events.hpp with Ch channels);
+  * ``basis_pursuit`` (not in the reference) is the L1 coder of ``solve`` as a call of its own, for fixed templates: for
+    D [T, S] the LASSO step above, for multichannel templates D [T, Ch, S] the same proximal-gradient iteration in
+    Gram form, one kernel per iteration on the lag correlations of the templates, whose cost does not depend on Ch
+    (``dcp_tm_mc_lasso_*``, decomp_amd/csrc/template_mc_lasso.hpp).
 
 A 2-D D calls the un-prefixed entries and a 3-D D (Ch = 1 included) the ``mc_`` ones; ``_entry`` is the one place that
 says which, and both reach the same C++ functions apart from the correlation pass and ``predict``.
@@ -301,6 +305,80 @@ def orthogonal_pursuit(y, D, n_nonzero_coefs=None, tol=None, stride=1, padding='
     tol_c = omp.check_tol(tol)
     n_steps = _orthogonal_steps(n_nonzero_coefs, T, C, _arrays.np_dtype(y))
     return _pursuit_call('omp', kind, y, D, T, S, N, C, Ch, stride, padding, n_steps, tol_c)
+
+
+def basis_pursuit(y, D, alpha, x=None, tol=1.0e-5, maxiter=10, method='acc_ista', stride=1, padding='SAME'):
+    """
+    L1 codes of every signal on the shift-invariant dictionary of the templates,
+        argmin_x 1 / (2 n) |y - x * D|^2 + alpha |x|,
+    the coder ``solve`` runs by default, for fixed templates: it needs no event count in advance.
+
+    y: [..., N]; D: templates [T, S], S <= N, used as given; x: optional initial estimate [..., T, C] (copied, not
+    overwritten; None: zero); float or complex, all of one dtype.  The result is
+    ``lasso.solve(y, A, alpha, x, tol, method, maxiter)`` on the dense operator A[(t, c), n] = D[t, n - stride c + Q],
+    which is never formed for 'ista', 'acc_ista', 'fista' and their '_pos' forms (``dcp_tm_lasso_*``: a residual pass
+    and a correlation pass per iteration); 'cd', 'parallel_cd' and 'admm' run the dense solvers on it.
+    Multichannel templates: a 3-D D [T, Ch, S] codes y [..., Ch, N] with one coefficient per event for all Ch channels
+    (the model of ``pursuit``); the dense operator is A [T C, Ch N], n = Ch N.  The solver is proximal gradient in Gram
+    form (``dcp_tm_mc_lasso_*``, decomp_amd/csrc/template_mc_lasso.hpp, Ch = 1 included): y is read once, by the
+    correlation pass of the greedy coders, and an iteration is one kernel on the lag correlations of the templates whose
+    cost does not depend on Ch.  'ista', 'acc_ista', 'fista' and their '_pos' forms only (NotImplementedError
+    otherwise).  With 'SAME' the Gram entries of the atoms that reach outside the signal are tabulated per call; the
+    library refuses templates so wide that this table exceeds 1 GiB.
+    Returns (it, x): x [..., T, C] in the layout of ``solve`` / ``predict``, it the iteration count as ``lasso.solve``
+    reports it.  NumPy in -> NumPy out; torch GPU tensors stay on the device.
+    """
+    import torch
+    kind = get_array_module(y, D, x)
+    Ch = _channels(D)
+    if len(y.shape) < (1 if Ch is None else 2):
+        raise assertion.DimInvalidError('y must have at least %d dimension%s' % ((1, '') if Ch is None else (2, 's')))
+    _check_y_channels(y, D, Ch)
+    T, S, N = int(D.shape[0]), int(D.shape[-1]), int(y.shape[-1])
+    stride, C = _geometry(T, S, N, stride, padding)
+    sig = (N,) if Ch is None else (Ch, N)                             # the dimensions of one signal
+    lead = tuple(y.shape[:-len(sig)])
+    if x is None:
+        assertion.assert_dtypes(y=y, D=D)
+    else:
+        assertion.assert_dtypes(y=y, D=D, x=x)
+        if tuple(x.shape) != lead + (T, C):
+            raise ValueError('x{0} must be {1}: the batch dimensions of y{2}, then [T, C] = [{3:d}, {4:d}]'.format(
+                tuple(x.shape), lead + (T, C), tuple(y.shape), T, C))
+    if not isinstance(alpha, (int, float, np.integer, np.floating)) or isinstance(alpha, (bool, np.bool_)) \
+            or not alpha >= 0:
+        raise ValueError('alpha must be a non-negative number. Given {0!r}'.format(alpha))
+    if not isinstance(tol, (int, float, np.integer, np.floating)) or isinstance(tol, (bool, np.bool_)) or not tol >= 0:
+        raise ValueError('tol must be a non-negative number. Given {0!r}'.format(tol))
+    if not _is_int(maxiter) or int(maxiter) < 1:
+        raise ValueError('maxiter must be a positive integer. Given {0!r}'.format(maxiter))
+    base = method[:-4] if isinstance(method, str) and method.endswith('_pos') else method
+    if base not in _STRUCTURED + _DENSE:
+        raise ValueError('Available methods are {0} and their _pos forms. Given {1!r}'.format(
+            list(_STRUCTURED + _DENSE), method))
+    _check_positive(base != method, _arrays.np_dtype(y))
+    if Ch is not None and base not in _STRUCTURED:
+        raise NotImplementedError('multichannel templates D [T, Ch, S] are coded with {0} and their _pos forms only. '
+                                  'Given {1!r}'.format(list(_STRUCTURED), method))
+
+    yd = _arrays.to_device(y)
+    Dd = _arrays.to_device(D, yd.device.index).contiguous()
+    y2 = yd.reshape((-1,) + sig).contiguous()
+    B = y2.shape[0]
+    if x is None:
+        xd = torch.zeros((B, T, C), dtype=yd.dtype, device=yd.device)
+    else:
+        xd = _arrays.to_device(x, yd.device.index, copy=True).reshape(B, T, C).contiguous()
+    _same_device(yd, Dd, xd)
+    it = 0
+    if B > 0 and Ch is None:
+        it = _lasso(y2, Dd, xd, alpha, stride, padding, method, int(maxiter), tol)
+    elif B > 0:
+        out = ctypes.c_int(0)
+        _call(y2, 'mc_lasso', y2, Dd, xd, B, T, Ch, S, N, stride, _pad_code(padding), float(alpha), float(tol),
+              int(maxiter), lasso._METHOD_CODE[base], 1 if base != method else 0, ctypes.byref(out))
+        it = out.value
+    return it, _arrays.to_caller(xd.reshape(lead + (T, C)), kind)
 
 
 def _pursuit_steps(n_nonzero_coefs, T, C):

@@ -963,6 +963,17 @@ int dcp_tm_mc_gather_windows_f32(dcp_handle* h, const void* Y, const void* X, co
 int dcp_tm_mc_gather_windows_f64(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
 int dcp_tm_mc_gather_windows_c64(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
 int dcp_tm_mc_gather_windows_c128(dcp_handle* h, const void* Y, const void* X, const int64_t* idx_b, const int64_t* idx_n, int64_t m, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t w, int64_t stride, int padding, void* Yw, void* Xw);
+/* dcp_tm_lasso_* for multichannel templates: Y [B, Ch, N], D [T, Ch, S], X [B, T, C] (in: the initial estimate, out: the
+ * solution), i.e. lasso.solve on the dense operator A [T C, Ch N], A[(t, c), (ch, n)] = D[t, ch, n - stride c + Q].
+ * method, positive, the scaled variables, the stop test, it_out and the argument checks are those of dcp_tm_lasso_*; the
+ * threshold is alpha Ch N / rho.  Proximal gradient in Gram form: one correlation pass over Y per call, then one kernel
+ * per iteration on the lag correlations of the templates, whose cost does not depend on Ch.  The Gram entries of pairs
+ * of atoms that both reach outside the signal are tabulated once per call (none with VALID padding); a table above
+ * 1 GiB gives DCP_ERR_INVALID before anything is launched.  Ch = 1 runs these kernels too. */
+int dcp_tm_mc_lasso_f32(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol, int maxiter, int method, int positive, int* it_out);
+int dcp_tm_mc_lasso_f64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol, int maxiter, int method, int positive, int* it_out);
+int dcp_tm_mc_lasso_c64(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol, int maxiter, int method, int positive, int* it_out);
+int dcp_tm_mc_lasso_c128(dcp_handle* h, const void* Y, const void* D, void* X, int64_t B, int64_t T, int64_t Ch, int64_t S, int64_t N, int64_t stride, int padding, double alpha, double tol, int maxiter, int method, int positive, int* it_out);
 
 #ifdef __cplusplus
 }
