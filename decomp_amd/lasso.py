@@ -138,6 +138,8 @@ def solve_fastpath(y, A, alpha, x, tol, maxiter, method, xp, mask=None, **kwargs
         xd = torch.zeros((N, K), dtype=yd.dtype, device=yd.device)
     else:
         xd = _arrays.to_device(x, dev, copy=True).reshape(N, K)
+    if N == 0:      # an empty batch: nothing to solve (the library takes positive sizes only)
+        return 0, _arrays.to_caller(xd.reshape(batch_shape + (K,)), kind)
     sfx = _arrays.suffix(yd)
     md, mask_ndim = _arrays.mask_to_device(mask, yd, N, F)
     lib, h = _arrays.lib_handle(yd)
