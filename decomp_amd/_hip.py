@@ -76,6 +76,8 @@ _FAMILIES = [
     ('dcp_axpby', _REALS, [_c_vp, _c_i64, _c_f64, _c_vp, _c_f64, _c_vp]),
     ('dcp_gemm', _ALL, [_c_vp, _c_int] + [_c_vp] * 3 + _NFK + [_c_int, _c_int]),
     ('dcp_gemm_bf16x6', ('f32',), [_c_vp, _c_int] + [_c_vp] * 3 + _NFK + [_c_int]),
+    ('dcp_gemm_bf16x6_seg', ('f32',), [_c_vp, _c_int] + [_c_vp] * 4 + [_c_i64] * 4 + [_c_int]),
+    ('dcp_gemm_bf16x6_tier', None, [_c_int] + [_c_i64] * 4 + [_c_int]),
     ('dcp_set_f32_product_mode', None, [_c_vp, _c_int]),
     ('dcp_debug_tn_plain', None, [_c_int]),
     ('dcp_debug_gemm_route', None, [_c_int, _c_int] + [_c_i64] * 4 + [_c_int] * 5 + [_c_vp]),

@@ -646,14 +646,15 @@ inline bool plan_splits_x6_tn(GemmArgs<T>& a, int n1, int max_splits) {
 template <int FORM>
 inline int x6_tier(const GemmArgs<float>& a) {
     if (FORM == FORM_NN) return X6_NONE;
+    constexpr int AL = (FORM == FORM_TN) ? XMAJOR : KMAJOR, BL = (FORM == FORM_NT) ? KMAJOR : XMAJOR;
     const int tier = pick_tier<FORM>(a.M, a.N, a.K, a.tile, a.split_planned, true);
     const GemmProblem p = fill_problem<FORM>(a);
-    if (FORM == FORM_NT && tier == TIER_HUGE && x6_eligible<X6Huge>(p)) return X6_HUGE;
+    if (FORM == FORM_NT && tier == TIER_HUGE && x6_eligible<X6Huge, AL, BL>(p)) return X6_HUGE;
     if (FORM == FORM_TN && tier == TIER_LARGE && x6_huge_tn_shape(a, a.B2 != nullptr ? a.n_b1 : a.N, a.ksplits > 1 ? a.klen : a.K) &&
-        x6_eligible<X6Huge>(p))
+        x6_eligible<X6Huge, AL, BL>(p))
         return X6_HUGE;
     if ((tier == TIER_LARGE || (FORM == FORM_NT && (tier == TIER_MID || tier == TIER_HUGE))) &&
-        x6_eligible<X6Large>(p))
+        x6_eligible<X6Large, AL, BL>(p))
         return X6_LARGE;
     return X6_NONE;
 }

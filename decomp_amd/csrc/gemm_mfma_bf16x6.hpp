@@ -34,9 +34,12 @@
 //     wave leaves it needing its first fragments at once.
 //   256 x 256 tile: a ring of three buffers (3 x 48 KiB; one workgroup per CU either way).  Block kb + 2 is
 //     staged during block kb, the loads run three blocks ahead, and the barrier sits inside the block, after a
-//     wave's last fragment read and before its last 6 TN products.  Nothing but MFMAs lies between a block's
-//     last staging and the next block's first fragment reads, so the waves cross the block boundary staggered
-//     by the matrix pipe instead of aligned by a barrier (the conditions are at the K loop).
+//     wave's last fragment read of the block and its second group's first product.  The waves cross the block
+//     boundary staggered by the matrix pipe instead of aligned by a barrier, and the fragment registers are
+//     refilled one plane at a time as the fixed term order lets them die (group 0: the second group's A
+//     fragments; group 1, behind the barrier: the next block's fragments from the next buffer), so fragment
+//     reads are spread through the MFMA stream and a block starts with only its h planes on the way (the
+//     conditions are at the K loop).
 //   KMAJOR panel (reduction index contiguous): one 16-byte load = 4 k of one row.
 //     LDS image of one plane: [rows][16 k] bf16, 32 bytes per row, two 16-byte chunks (k 0..7, 8..15);
 //     chunk q of row r sits at chunk q ^ ((r >> 3) & 1).  A lane (l31, h) of the 32x32x16 MFMA reads
@@ -58,6 +61,24 @@
 #include <type_traits>
 
 namespace dcp {
+
+// Diagnostic build only (-DDCP_X6_STAMPS on the translation unit that launches the kernel; off by default, so no
+// stamp runs in the shipped kernel): the 256 x 256 K loop reads the shader clock at four places per K block, keeps
+// the sums in scalar registers, and lane 0 of every wave of workgroup 0 stores them once after the loop into
+// x6_stamp_buf[wave][8] = { cycles from the previous block's last MFMA (the first block: from the prologue's
+// fragment reads) to the operands of the block's first MFMA, cycles from the last MFMA of group 0 to the barrier's
+// exit (group 1's first product lies in between), cycles between the first and the last stamped block start,
+// stamped blocks, cost of one stamp }.  Each stamp drains lgkmcnt (s_memtime returns through it), so the build is
+// slower than the real one and only its shares mean anything.  tools/bf16x6_stamps.py reads the buffer.
+#ifdef DCP_X6_STAMPS
+static __device__ unsigned long long x6_stamp_buf[16 * 8];
+#define X6_STAMP(t)                                                                         \
+    do {                                                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                  \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");        \
+        __builtin_amdgcn_sched_barrier(0);                                                  \
+    } while (0)
+#endif
 
 typedef __bf16 x6_bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 x6_bf16x8 __attribute__((ext_vector_type(8)));
@@ -92,20 +113,47 @@ __device__ __forceinline__ void x6_split(f32x4 a, x6_bf16x4& h, x6_bf16x4& m, x6
 }
 
 // G = groups of 4 values per thread per K block (KMAJOR: 4 k of one row; XMAJOR: 4 rows at one k)
-template <int LAY, int ROWS, int NT, int G>
+// SBASE (the 256 x 256 ring, which has no registers to spare): scalar base + 32-bit thread offset, see below.
+template <int LAY, int ROWS, int NT, bool SBASE, int G>
 __device__ __forceinline__ void x6_gload(f32x4 (&r)[G], const float* __restrict__ p, long ld, int row0, int k0,
                                          int tid) {
     static_assert(G * NT * 4 == ROWS * 16, "panel must be a whole number of 4-value groups per thread");
+    if constexpr (!SBASE) {
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int idx = tid + i * NT;
+            if (LAY == KMAJOR) {
+                const int row = idx >> 2, kq = idx & 3;
+                r[i] = *reinterpret_cast<const f32x4*>(p + (long)(row0 + row) * ld + (k0 + 4 * kq));
+            } else {
+                const int g = idx % (ROWS / 4), k = idx / (ROWS / 4);
+                r[i] = *reinterpret_cast<const f32x4*>(p + (long)(k0 + k) * ld + (row0 + 4 * g));
+            }
+        }
+        return;
+    }
+    // The block's part of the address is uniform; the thread's part fits 32 bits (x6_eligible) and is the same
+    // for every K block: one VGPR per load, where a flat address costs a 64-bit pointer and a 64-bit k offset per
+    // panel.  The empty asm keeps the uniform part in SGPRs: without it hipcc adds the two in the other order and
+    // carries the sum in VGPRs through the loop.
+    // These pins (here, on `off` below and in ring_off of the kernel) are what holds the 256 x 256 instantiations at
+    // 127-128 VGPRs, 0 AGPRs, no scratch and no spills (147 456 B LDS, 4 waves per SIMD) with global_load ... v, s[]
+    // loads and no flat_load, read from the ISA of ROCm 7's hipcc: check those figures again after a toolchain
+    // update (-Rpass-analysis=kernel-resource-usage, or the metadata at the end of --save-temps' .s).
+    // (global address space spelled out: behind the asm hipcc no longer infers it and would issue flat loads)
+    typedef const __attribute__((address_space(1))) char* gchar_ptr;
+    typedef const __attribute__((address_space(1))) f32x4* gf32x4_ptr;
+    gchar_ptr base = (gchar_ptr)(p + (LAY == KMAJOR ? (long)row0 * ld + k0 : (long)k0 * ld + row0));
+    asm("" : "+s"(base));
 #pragma unroll
     for (int i = 0; i < G; ++i) {
         const int idx = tid + i * NT;
-        if (LAY == KMAJOR) {
-            const int row = idx >> 2, kq = idx & 3;
-            r[i] = *reinterpret_cast<const f32x4*>(p + (long)(row0 + row) * ld + (k0 + 4 * kq));
-        } else {
-            const int g = idx % (ROWS / 4), k = idx / (ROWS / 4);
-            r[i] = *reinterpret_cast<const f32x4*>(p + (long)(k0 + k) * ld + (row0 + 4 * g));
-        }
+        unsigned off;
+        if (LAY == KMAJOR) off = (unsigned)(idx >> 2) * (unsigned)ld + 4u * (idx & 3);
+        else off = (unsigned)(idx / (ROWS / 4)) * (unsigned)ld + 4u * (idx % (ROWS / 4));
+        off *= 4u;
+        asm("" : "+v"(off));   // (the widening stays beside the load, where hipcc folds it into the instruction)
+        r[i] = *(gf32x4_ptr)(base + off);
     }
 }
 
@@ -147,6 +195,13 @@ __device__ __forceinline__ int x6_frag_off(int r0, int lane) {
     const int q = (lane >> 2) & 3, pq = lane & 3, gh = (lane >> 4) & 1;
     return x6_granule<ROWS>(8 * h + q, (r0 >> 2) + 4 * gh + pq);
 }
+
+// The fragment 32 rows on, from the byte offset of a fragment whose r0 is a multiple of 64 (any plane and buffer
+// base included: they are multiples of 128).  KMAJOR: 32 rows of 32 bytes, and (r >> 3) & 1 is the same.  XMAJOR: 8
+// granules on; bit 3 of the granule index is clear before the swizzle, so the step is a flip of that bit: 64 bytes.
+// One offset per panel then serves both 32-row blocks, where two would each hold a register through the K loop.
+template <int LAY>
+__device__ __forceinline__ int x6_frag_next32(int off) { return LAY == KMAJOR ? off + 32 * 32 : off ^ 64; }
 
 template <int LAY, int ROWS>
 __device__ __forceinline__ x6_bf16x8 x6_frag(const char* plane, int off) {
@@ -372,10 +427,11 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
     // holds block kb, buffer (kb + 1) % 3 holds block kb + 1 (complete) and ra / rb hold block kb + 2's fp32
     // values.  During block kb a wave stages block kb + 2 into buffer (kb + 2) % 3 at the same two places and
     // issues the loads of block kb + 3 behind each store.  The barrier B(kb) sits after the wave's last
-    // fragment read of block kb (the A fragments of the second group) and before that group's MFMAs and B-panel
-    // staging; only MFMAs lie between B(kb) + staging and the first fragment reads of block kb + 1, so the waves
-    // of a SIMD cross the block boundary staggered by the matrix pipe and one wave's fragment reads run under
-    // the others' MFMAs.  Why one barrier is enough:
+    // fragment read of block kb (the second group's fa[h], read behind the first group's last product) and the
+    // second group's first product, before that group's B-panel staging and before any read of block kb + 1
+    // (which the second group issues as its planes die: see the fragment registers below).  The waves of a SIMD
+    // cross the block boundary staggered by the matrix pipe and one wave's fragment reads run under the others'
+    // MFMAs.  Why one barrier is enough:
     //   - a buffer is overwritten only after a barrier that follows every wave's reads of it: buffer
     //     (kb + 2) % 3 = (kb - 1) % 3 was last read in block kb - 1, all of those reads precede B(kb - 1), and
     //     both stagings of block kb follow B(kb - 1);
@@ -390,65 +446,134 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
     static_assert(TM == 2, "one panel's staging per 32-row A block");
     constexpr int STAGES = Cfg::STAGES;
     static_assert(STAGES == 2 || STAGES == 3, "two buffers and a boundary barrier, or a ring of three");
+    constexpr bool REFILL = STAGES == 3;   // fragment registers refilled as their planes die (below)
     f32x4 ra[GA], rb[GB];
     const int nkb = (kend - kbeg) / BK;   // whole K blocks (x6_eligible)
     if (nkb > 0) {
-        x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, kbeg, tid);
-        x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, kbeg, tid);
+        x6_gload<ALAY, BM, NT, REFILL>(ra, p.A, p.lda, m0, kbeg, tid);
+        x6_gload<BLAY, BN, NT, REFILL>(rb, Bp, ldb, nB0, kbeg, tid);
         x6_lds_store<ALAY, BM, NT>(x6_smem, ra, tid);
         x6_lds_store<BLAY, BN, NT>(x6_smem + X6Panel<BM>::BYTES, rb, tid);
         const int k1 = kbeg + min(1, nkb - 1) * BK;
-        x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k1, tid);
-        x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k1, tid);
+        x6_gload<ALAY, BM, NT, REFILL>(ra, p.A, p.lda, m0, k1, tid);
+        x6_gload<BLAY, BN, NT, REFILL>(rb, Bp, ldb, nB0, k1, tid);
         if constexpr (STAGES == 3) {
             x6_lds_store<ALAY, BM, NT>(x6_smem + BUF, ra, tid);
             x6_lds_store<BLAY, BN, NT>(x6_smem + BUF + X6Panel<BM>::BYTES, rb, tid);
             const int k2 = kbeg + min(2, nkb - 1) * BK;
-            x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, k2, tid);
-            x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, k2, tid);
+            x6_gload<ALAY, BM, NT, REFILL>(ra, p.A, p.lda, m0, k2, tid);
+            x6_gload<BLAY, BN, NT, REFILL>(rb, Bp, ldb, nB0, k2, tid);
         }
     }
     __syncthreads();
 
     // fragment byte offsets inside a plane (the same for every K block and buffer)
-    int aoff[TM], boff[TN];
+    static_assert(WM == 64 && WN == 64 && TN == 2, "x6_frag_next32: two 32-row blocks per 64-row wave tile");
+    const int aoff = x6_frag_off<ALAY, BM>(wm * WM, lane), boff = x6_frag_off<BLAY, BN>(wn * WN, lane);
+    // (the two-buffer loop keeps one offset per 32-row block, as it always had)
+    int aoff2[TM], boff2[TN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) aoff[i] = x6_frag_off<ALAY, BM>(wm * WM + i * 32, lane);
+    for (int i = 0; i < TM; ++i) aoff2[i] = REFILL ? 0 : x6_frag_off<ALAY, BM>(wm * WM + i * 32, lane);
 #pragma unroll
-    for (int j = 0; j < TN; ++j) boff[j] = x6_frag_off<BLAY, BN>(wn * WN + j * 32, lane);
+    for (int j = 0; j < TN; ++j) boff2[j] = REFILL ? 0 : x6_frag_off<BLAY, BN>(wn * WN + j * 32, lane);
 
     // products (of six) that go out before a group's staging
     constexpr int STAGE_AFTER = 2;
+    // small terms first, hh last; plane index 0 = h, 1 = m, 2 = l
+    constexpr int TA[6] = {2, 0, 1, 1, 0, 0};
+    constexpr int TB[6] = {0, 2, 1, 0, 1, 0};
+    // Fragment registers.  The term order lets them die one plane at a time: within a group fa[l] is dead after
+    // product 0, fa[m] after product 3, fa[h] after product 5; fb serves both groups and in the second one fb[l]
+    // is dead after product 1, fb[m] after product 4, fb[h] after product 5.
+    //   STAGES == 2: a block reads fb at its start and fa at the start of each group, as the boundary barrier
+    //     demands.
+    //   STAGES == 3 (REFILL): a dead plane's registers take at once the next fragment that will live in them, so
+    //     only MFMAs lie between most fragment reads and their use, and no registers are added (the assignment
+    //     goes to the old array element and sched barriers pin each read behind the last MFMA that reads its
+    //     destination).  Group 0 of block kb reads group 1's A fragments; group 1, after B(kb), reads block
+    //     kb + 1's fragments from buffer (kb + 1) % 3 (NEXT), so a block starts with only the h reads outstanding.
+    //     B(kb) sits behind group 1's first product (fa[l] . fb[h]), which runs while fa[h] lands.  The ring's two
+    //     conditions hold for this position:
+    //       - it follows the wave's last fragment read of block kb (group 1's fa[h], read after group 0's last
+    //         product), so buffer kb % 3 is overwritten (the stagings of block kb + 1) only after every read of it;
+    //       - it precedes block kb's B-panel staging and every read of block kb + 1.  Block kb + 1's A panel was
+    //         staged before B(kb - 1) and its B panel before B(kb) (blocks 0 and 1: before the prologue's barrier),
+    //         so all of its reads follow its writes; all of them still precede B(kb + 1), after which the stagings
+    //         of block kb + 2 overwrite that buffer.
+    //     The prologue reads block 0's fragments; block nkb - 2 reads block nkb - 1's, block nkb - 1 none.
+    x6_bf16x8 fa[3], fb[3][TN];
+    // plane pl of the A fragment at byte offset off (buffer and 32-row block included), of the B fragment of
+    // 32-column block j of the buffer whose first B fragment is at off
+    auto afrag = [&](int off, int pl) { return x6_frag<ALAY, BM>(x6_smem + pl * PA, off); };
+    auto bfrag = [&](int off, int pl, int j) {
+        return x6_frag<BLAY, BN>(x6_smem + X6Panel<BM>::BYTES + pl * PB, j ? x6_frag_next32<BLAY>(off) : off);
+    };
+    // a buffer's first fragment offset, formed where it is used: the empty asm keeps hipcc from carrying the sums
+    // of x6_smem with aoff and boff through the loop beside aoff and boff themselves (the ring has no registers
+    // for that)
+    auto ring_off = [](int buf, int off) {
+        int o = buf + off;
+        asm("" : "+v"(o));
+        return o;
+    };
+#ifdef DCP_X6_STAMPS
+    unsigned long long st_t0 = 0, st_t1 = 0, st_t2 = 0, st_t3 = 0, st_a = 0, st_b = 0, st_first = 0, st_last = 0;
+    unsigned long long st_cost = 0;
+    unsigned st_n = 0;
+    X6_STAMP(st_t1);
+    X6_STAMP(st_t0);
+    st_cost = st_t0 - st_t1;
+#endif
+    if constexpr (REFILL) {
+        // in the order of a block's refills, h last and fb[h] before fa[h], so that the loop's first wait is the
+        // same count from the prologue and from the previous block
+#pragma unroll
+        for (int pl = 2; pl >= 0; --pl) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) fb[pl][j] = bfrag(boff, pl, j);
+            fa[pl] = afrag(aoff, pl);
+        }
+    }
     // One K block: fragments from the buffer at byte offset cur; with STAGE, ra / rb are split and stored into
-    // the buffer at nxt and refilled from K offset knext; with BAR, the block's barrier follows its last
-    // fragment read (the ring of three; the two-buffer loop puts its barrier after the block).
-    auto kblock = [&](int cur, int nxt_off, int knext, auto stage_tag, auto bar_tag) {
+    // the buffer at nxt and refilled from K offset knext; with BAR, the block has its barrier B(kb) (the ring of
+    // three; the two-buffer loop puts its barrier after the block); with NEXT, group 1 reads the next block's
+    // fragments from the buffer at nb.
+    auto kblock = [&](int cur, int nxt_off, int knext, int nb, auto stage_tag, auto bar_tag, auto next_tag) {
         constexpr bool STAGE = decltype(stage_tag)::value;
         constexpr bool BAR = decltype(bar_tag)::value;
-        const char* sA = x6_smem + cur;
-        const char* sB = sA + X6Panel<BM>::BYTES;
+        constexpr bool NEXT = decltype(next_tag)::value;
+        static_assert(REFILL || (!BAR && !NEXT), "the barrier inside the block and the early reads need the ring");
         char* nxt = x6_smem + nxt_off;
-        // B fragments of the block first, then the A fragments of one 32-row block at a time: at four waves
-        // per SIMD (128 VGPRs) all of them at once would spill
-        x6_bf16x8 fb[3][TN];
+#ifdef DCP_X6_STAMPS
+        if constexpr (BAR) {
+            // st_t0: the previous block's last MFMA (or the prologue); here the first MFMA has its operands
+            X6_STAMP(st_t1);
+            st_a += st_t1 - st_t0;
+            if (st_n == 0) st_first = st_t0;
+            st_last = st_t0;
+            ++st_n;
+        }
+#endif
+        if constexpr (!REFILL) {
+            // B fragments of the block first, then the A fragments of one 32-row block at a time: at four waves
+            // per SIMD (128 VGPRs) all of them at once would spill
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
+            for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) fb[pl][j] = x6_frag<BLAY, BN>(sB + pl * PB, boff[j]);
-        // small terms first, hh last; plane index 0 = h, 1 = m, 2 = l
-        constexpr int TA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int TB[6] = {0, 2, 1, 0, 1, 0};
+                for (int j = 0; j < TN; ++j)
+                    fb[pl][j] = x6_frag<BLAY, BN>(x6_smem + cur + X6Panel<BM>::BYTES + pl * PB, boff2[j]);
+        }
         auto group = [&](auto i_tag) {
             constexpr int i = decltype(i_tag)::value;
-            x6_bf16x8 fa[3];
+            if constexpr (!REFILL) {
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) fa[pl] = x6_frag<ALAY, BM>(sA + pl * PA, aoff[i]);
-            if constexpr (BAR && i == 1) {
-                // B(kb): every fragment of the block is on its way to registers; hipcc moves MFMAs across a
-                // barrier that nothing pins
-                __builtin_amdgcn_sched_barrier(0);
-                __syncthreads();
-                __builtin_amdgcn_sched_barrier(0);
+                for (int pl = 0; pl < 3; ++pl) fa[pl] = x6_frag<ALAY, BM>(x6_smem + cur + pl * PA, aoff2[i]);
+            }
+            int roa = 0, rob = 0;   // where this group's refills read
+            if constexpr (REFILL && i == 0) roa = x6_frag_next32<ALAY>(ring_off(cur, aoff));
+            if constexpr (REFILL && i == 1 && NEXT) {
+                roa = ring_off(nb, aoff);
+                rob = ring_off(nb, boff);
             }
             auto mfmas = [&](int t0, int t1) {
 #pragma unroll
@@ -458,23 +583,72 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
                         acc[i][j] =
                             __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[TA[tt]], fb[TB[tt]][j], acc[i][j], 0, 0, 0);
             };
+            // plane pl of A is dead: group 0 takes group 1's fragment of this block, group 1 the next block's
+            auto refill_a = [&](int pl) {
+                if constexpr (i == 0 || NEXT) fa[pl] = afrag(roa, pl);
+            };
+            // plane pl of B is dead (second group only)
+            auto refill_b = [&](int pl) {
+                if constexpr (i == 1 && NEXT) {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) fb[pl][j] = bfrag(rob, pl, j);
+                }
+            };
+            mfmas(0, 1);
+            if constexpr (REFILL) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (BAR && i == 1) {
+                    // B(kb): every fragment of the block is on its way to registers; hipcc moves MFMAs across a
+                    // barrier that nothing pins
+                    __syncthreads();
+                    __builtin_amdgcn_sched_barrier(0);
+#ifdef DCP_X6_STAMPS
+                    X6_STAMP(st_t3);
+                    st_b += st_t3 - st_t2;
+#endif
+                }
+                refill_a(2);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            mfmas(1, STAGE_AFTER);
+            if constexpr (REFILL) {
+                __builtin_amdgcn_sched_barrier(0);
+                refill_b(2);
+            }
             if constexpr (STAGE) {
-                // the first products go out, then this wave splits and stores one panel of the block to stage
+                // the first products are out; now this wave splits and stores one panel of the block to stage
                 // and issues that panel's next loads while they (and the other waves' MFMAs) run; the sched
                 // barriers keep hipcc from sinking the staging to the end of the group
-                mfmas(0, STAGE_AFTER);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (i == 0) {
                     x6_lds_store<ALAY, BM, NT>(nxt, ra, tid);
-                    x6_gload<ALAY, BM, NT>(ra, p.A, p.lda, m0, knext, tid);
+                    x6_gload<ALAY, BM, NT, REFILL>(ra, p.A, p.lda, m0, knext, tid);
                 } else {
                     x6_lds_store<BLAY, BN, NT>(nxt + X6Panel<BM>::BYTES, rb, tid);
-                    x6_gload<BLAY, BN, NT>(rb, Bp, ldb, nB0, knext, tid);
+                    x6_gload<BLAY, BN, NT, REFILL>(rb, Bp, ldb, nB0, knext, tid);
                 }
+            }
+            if constexpr (REFILL || STAGE) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (REFILL) {
+                mfmas(STAGE_AFTER, 4);
                 __builtin_amdgcn_sched_barrier(0);
-                mfmas(STAGE_AFTER, 6);
+                refill_a(1);
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(4, 5);
+                __builtin_amdgcn_sched_barrier(0);
+                refill_b(1);
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(5, 6);
+#ifdef DCP_X6_STAMPS
+                if constexpr (BAR && i == 0) X6_STAMP(st_t2);
+                if constexpr (BAR && i == 1) X6_STAMP(st_t0);
+#endif
+                __builtin_amdgcn_sched_barrier(0);
+                // fb[h] first: the next block's first product reads it, fa[h] only its second
+                refill_b(0);
+                refill_a(0);
             } else {
-                mfmas(0, 6);
+                mfmas(STAGE_AFTER, 6);
             }
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -484,22 +658,36 @@ __global__ void __launch_bounds__(Cfg::NTHREADS, Cfg::MINW) gemm_bf16x6_kernel(G
     if constexpr (STAGES == 2) {
         for (int kb = 0; kb + 1 < nkb; ++kb) {
             const int cur = (kb & 1) * BUF;
-            kblock(cur, cur ^ BUF, kbeg + min(kb + 2, nkb - 1) * BK, std::true_type{}, std::false_type{});
+            kblock(cur, cur ^ BUF, kbeg + min(kb + 2, nkb - 1) * BK, 0, std::true_type{}, std::false_type{},
+                   std::false_type{});
             __syncthreads();
         }
-        if (nkb > 0) kblock(((nkb - 1) & 1) * BUF, 0, 0, std::false_type{}, std::false_type{});
+        if (nkb > 0)
+            kblock(((nkb - 1) & 1) * BUF, 0, 0, 0, std::false_type{}, std::false_type{}, std::false_type{});
     } else {
         int b0 = 0, b1 = BUF, b2 = 2 * BUF;   // byte offsets of the buffers of blocks kb, kb + 1, kb + 2
         for (int kb = 0; kb + 2 < nkb; ++kb) {
-            kblock(b0, b2, kbeg + min(kb + 3, nkb - 1) * BK, std::true_type{}, std::true_type{});
+            kblock(b0, b2, kbeg + min(kb + 3, nkb - 1) * BK, b1, std::true_type{}, std::true_type{},
+                   std::true_type{});
             const int t0 = b0;
             b0 = b1;
             b1 = b2;
             b2 = t0;
         }
-        if (nkb > 1) kblock(b0, 0, 0, std::false_type{}, std::true_type{});
-        if (nkb > 0) kblock(nkb > 1 ? b1 : b0, 0, 0, std::false_type{}, std::false_type{});
+        if (nkb > 1) kblock(b0, 0, 0, b1, std::false_type{}, std::true_type{}, std::true_type{});
+        if (nkb > 0) kblock(nkb > 1 ? b1 : b0, 0, 0, 0, std::false_type{}, std::false_type{}, std::false_type{});
     }
+
+#ifdef DCP_X6_STAMPS
+    if (blockIdx.x == 0 && lane == 0) {
+        unsigned long long* o = x6_stamp_buf + wave * 8;
+        o[0] = st_a;
+        o[1] = st_b;
+        o[2] = st_last - st_first;
+        o[3] = st_n;
+        o[4] = st_cost;
+    }
+#endif
 
     // ---- epilogue: the 32x32x16 bf16 MFMA has the C layout of the fp32 one:
     //      col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----
@@ -547,15 +735,23 @@ inline bool x6_epi_ok(const Epi& epi) {
 }
 
 // Whole tiles, whole 16-deep K blocks in every split, 16-byte aligned operands with leading dims % 4 == 0
-// (both forms load 16 bytes: 4 k of one row or 4 rows at one k), no stacked A.
-template <class Cfg>
+// (both forms load 16 bytes: 4 k of one row or 4 rows at one k), no stacked A.  The ring of three also wants a
+// thread's part of a panel address in 32 bits (x6_gload, SBASE): under `rows` rows of ld floats in a KMAJOR panel
+// (ld under about 4 Mi floats on the 256 x 256 tile), under 16 k rows in an XMAJOR one (ld under about 68 Mi floats).  A
+// product with a longer leading dimension used to run here and now takes what its caller does without this core:
+// x6_tier() falls to the 128 x 128 tile, which has no such bound, or to X6_NONE (the fp32 core, other last bits).
+template <class Cfg, int ALAY, int BLAY>
 inline bool x6_eligible(const GemmProblem& p) {
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const int n1 = p.B2 != nullptr ? p.n_b1 : p.N;
     bool ok = p.M > 0 && p.N > 0 && p.K > 0 && (p.M % Cfg::BM) == 0 && (n1 % Cfg::BN) == 0 &&
               ((p.N - n1) % Cfg::BN) == 0 && (p.K % 16) == 0 && p.A2 == nullptr && (p.lda % 4) == 0 &&
               (p.ldb % 4) == 0 && al16(p.A) && al16(p.B);
-    if (p.B2 != nullptr) ok = ok && (p.ldb2 % 4) == 0 && al16(p.B2);
+    auto off32 = [](int lay, int rows, long ld) {
+        return Cfg::STAGES != 3 || ((lay == KMAJOR ? (rows - 1) * ld + 16 : 15 * ld + rows) * 4 < (1L << 32));
+    };
+    ok = ok && off32(ALAY, Cfg::BM, p.lda) && off32(BLAY, Cfg::BN, p.ldb);
+    if (p.B2 != nullptr) ok = ok && (p.ldb2 % 4) == 0 && al16(p.B2) && off32(BLAY, Cfg::BN, p.ldb2);
     if (p.ksplits > 1) ok = ok && (p.klen % 16) == 0 && p.klen > 0;
     return ok;
 }
@@ -563,7 +759,7 @@ inline bool x6_eligible(const GemmProblem& p) {
 // Host launch.  Returns hipErrorInvalidValue when the problem is not eligible (callers check first).
 template <class Cfg, int ALAY, int BLAY, class Epi>
 inline hipError_t launch_gemm_bf16x6(hipStream_t stream, GemmProblem p, const Epi& epi) {
-    if (!x6_eligible<Cfg>(p) || !x6_epi_ok(epi)) return hipErrorInvalidValue;
+    if (!x6_eligible<Cfg, ALAY, BLAY>(p) || !x6_epi_ok(epi)) return hipErrorInvalidValue;
     if constexpr (epi_den_tail<Epi>::value) {
         // the tail takes the whole numerator: one split, one B segment; whole 16-deep K blocks of x.G.  The tail's
         // clamped loads would work from one K block per pass upward; 48 keeps the three stages of its prologue

@@ -561,25 +561,49 @@ int dcp_count_negative_f32(dcp_handle* h, const float* x, int64_t n, int64_t* co
 int dcp_count_negative_f64(dcp_handle* h, const double* x, int64_t n, int64_t* count) {
     return count_negative_api<double>(h, x, n, count);
 }
-int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B, float* C, int64_t M, int64_t N,
-                        int64_t K, int ksplits) {
-    if (!h) return DCP_ERR_INVALID;
-    if (!A || !B || !C) return fail(h, DCP_ERR_INVALID, "null array pointer");
-    if (M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
-        return fail(h, DCP_ERR_INVALID, "bad sizes");
-    if (form != FORM_NT && form != FORM_TN) return fail(h, DCP_ERR_INVALID, "bf16x6: form must be 0 (NT) or 2 (TN)");
-    DCP_HIP_OK(h, hipSetDevice(h->device));
-    GemmArgs<float> a;
+// the operands of the split-bf16 hooks: B in one segment (B2 null, n_b1 == N) or two (columns < n_b1 from B, the
+// others from B2, each segment dense in its own array), the split plan of dcp_gemm_f32
+static void bf16x6_hook_args(GemmArgs<float>& a, int form, const float* A, const float* B, const float* B2, int64_t M,
+                             int64_t N, int64_t n_b1, int64_t K, int ksplits) {
     a.A = A; a.B = B; a.M = (int)M; a.N = (int)N; a.K = (int)K;
     a.lda = (form == FORM_TN) ? M : K;
-    a.ldb = (form == FORM_NT) ? K : N;
-    float* slabs = nullptr;
-    if (ksplits > 1) {   // the same split plan as dcp_gemm_f32
+    a.ldb = (form == FORM_NT) ? K : n_b1;
+    if (B2) {
+        a.B2 = B2; a.n_b1 = (int)n_b1;
+        a.ldb2 = (form == FORM_NT) ? K : N - n_b1;
+    }
+    if (ksplits > 1) {
         const long kblocks = (K + 15) / 16;
         const long s = ksplits > kblocks ? kblocks : ksplits;
         a.klen = (int)(((kblocks + s - 1) / s) * 16);
         a.ksplits = (int)((K + a.klen - 1) / a.klen);
         a.split_planned = true;
+    }
+}
+
+int dcp_gemm_bf16x6_tier(int form, int64_t M, int64_t N, int64_t n_b1, int64_t K, int ksplits) {
+    if ((form != FORM_NT && form != FORM_TN) || M <= 0 || N <= 0 || K <= 0 || n_b1 <= 0 || n_b1 > N || M > INT32_MAX ||
+        N > INT32_MAX || K > INT32_MAX)
+        return X6_NONE;
+    alignas(16) static const float aligned[4] = {0, 0, 0, 0};   // x6_tier looks at the pointers' alignment only
+    GemmArgs<float> a;
+    bf16x6_hook_args(a, form, aligned, aligned, n_b1 < N ? aligned : nullptr, M, N, n_b1, K, ksplits);
+    return (form == FORM_NT) ? x6_tier<FORM_NT>(a) : x6_tier<FORM_TN>(a);
+}
+
+int dcp_gemm_bf16x6_seg_f32(dcp_handle* h, int form, const float* A, const float* B, const float* B2, float* C,
+                            int64_t M, int64_t N, int64_t n_b1, int64_t K, int ksplits) {
+    if (!h) return DCP_ERR_INVALID;
+    if (!A || !B || !C) return fail(h, DCP_ERR_INVALID, "null array pointer");
+    if (M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
+        return fail(h, DCP_ERR_INVALID, "bad sizes");
+    if (B2 ? (n_b1 <= 0 || n_b1 >= N) : n_b1 != N) return fail(h, DCP_ERR_INVALID, "bf16x6: bad first segment width");
+    if (form != FORM_NT && form != FORM_TN) return fail(h, DCP_ERR_INVALID, "bf16x6: form must be 0 (NT) or 2 (TN)");
+    DCP_HIP_OK(h, hipSetDevice(h->device));
+    GemmArgs<float> a;
+    bf16x6_hook_args(a, form, A, B, B2, M, N, n_b1, K, ksplits);
+    float* slabs = nullptr;
+    if (ksplits > 1) {
         DCP_TRY(ws_lay_out(h, [&](WsLayout& w) { w.take(slabs, (size_t)a.ksplits * M * N); }));
     }
     const bool ok = (form == FORM_NT) ? x6_tier<FORM_NT>(a) != X6_NONE : x6_tier<FORM_TN>(a) != X6_NONE;
@@ -598,6 +622,20 @@ int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B,
     }
     return DCP_OK;
 }
+int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B, float* C, int64_t M, int64_t N,
+                        int64_t K, int ksplits) {
+    return dcp_gemm_bf16x6_seg_f32(h, form, A, B, nullptr, C, M, N, N, K, ksplits);
+}
+#ifdef DCP_X6_STAMPS
+// diagnostic build only (gemm_mfma_bf16x6.hpp): the clock sums that the last 256 x 256 product launched from this
+// translation unit (dcp_gemm_bf16x6_f32) left behind, [16 waves][8]
+extern "C" int dcp_x6_stamps_read(unsigned long long* out) {
+    if (hipDeviceSynchronize() != hipSuccess) return DCP_ERR_HIP;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(dcp::x6_stamp_buf), sizeof(dcp::x6_stamp_buf)) == hipSuccess
+               ? DCP_OK
+               : DCP_ERR_HIP;
+}
+#endif
 int dcp_set_f32_product_mode(dcp_handle* h, int mode) {
     if (!h) return DCP_ERR_INVALID;
     const int prev = h->f32_product_mode;

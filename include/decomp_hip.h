@@ -182,6 +182,15 @@ int dcp_gemm_c128(dcp_handle* h, int form, const void* A, const void* B, void* C
 int dcp_gemm_bf16x6_f32(dcp_handle* h, int form, const float* A, const float* B, float* C,
                         int64_t M, int64_t N, int64_t K, int ksplits);
 
+/* Test hooks: the same product with B in two column segments, as the NMF statistics x^T [Y | x] has it: columns
+ * < n_b1 from B, the others from B2, each segment a dense array of its own (NT: [n_b1, K] and [N - n_b1, K]; TN:
+ * [K, n_b1] and [K, N - n_b1]).  B2 == NULL with n_b1 == N is dcp_gemm_bf16x6_f32.  dcp_gemm_bf16x6_tier says, from
+ * the shape alone (16-byte aligned operands taken for granted; n_b1 == N: one segment), which tile that call would
+ * run on: 1 = 256 x 256, 0 = 128 x 128, -1 = none (the call fails). */
+int dcp_gemm_bf16x6_seg_f32(dcp_handle* h, int form, const float* A, const float* B, const float* B2, float* C,
+                            int64_t M, int64_t N, int64_t n_b1, int64_t K, int ksplits);
+int dcp_gemm_bf16x6_tier(int form, int64_t M, int64_t N, int64_t n_b1, int64_t K, int ksplits);
+
 /* How the float32 NMF multiplicative-update step (l2 loss, no mask) forms its two large products, Y.D^T and
  * x^T [Y | x], on this handle: mode 0 (default) = split-bf16 core (bf16x6, see dcp_gemm_bf16x6_f32), mode 1 =
  * the exact fp32 MFMA core.  Every other product, dtype and loss always uses its usual core.  mode < 0 only
